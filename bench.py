@@ -47,10 +47,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# A context uses three HIP streams (pixel kernels + two component chains) that must overlap; HIP maps
-# streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share one serialise.
-# With torch's and RCCL's own streams in the process, leave room (must be set before HIP initialises).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
@@ -709,6 +705,37 @@ def c1_tool_leg(device_index, nfiles=256, jobs=4):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, points, levels, npoints):
+    """--dump-outputs: the corner lists the timed path hands its caller after its last step -> out_dir/<name>.npy, so
+    that two builds can be compared output for output on the identical (seeded) frames.  points [F,P,2] and levels
+    [F,P] as float64 (doubles as computed, levels exact); slots past a frame's count, which the library leaves
+    unspecified, hold 0 (points) and -1 (levels: never a pyramid level), so every value is finite.  npoints [F], the
+    candidate count as the library returned it (it may exceed P); frame_index [F], the frame of the step each row
+    belongs to.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the frames is written."""
+    import numpy as np
+    pts = points.cpu().numpy().astype(np.float64)
+    P = pts.shape[-2]
+    pts = pts.reshape(-1, P, 2)
+    lv = levels.cpu().numpy().reshape(-1, P).astype(np.float64)
+    n = npoints.cpu().numpy().reshape(-1).astype(np.int64)
+    F = len(n)
+    idx = np.arange(F)
+    per_frame = (P * 2 + P + 2) * 8
+    if F * per_frame > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(F, max(1, DUMP_LIMIT_BYTES // per_frame), replace=False))
+    pts, lv, n = pts[idx], lv[idx], n[idx]
+    dead = np.arange(P)[None, :] >= np.minimum(n, P)[:, None]
+    pts[dead] = 0.0
+    lv[dead] = -1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("points", pts), ("levels", lv), ("npoints", n.astype(np.float64)),
+                    ("frame_index", idx.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -750,7 +777,12 @@ def main():
                     help="bind this process to the cores of its GPU's NUMA node (always done for --gpus > 1)")
     ap.add_argument("--prime", type=int, default=30,
                     help="untimed set-up passes before the W warm-up steps (scratch allocation, clock ramp); reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the corner lists of the last one (rank 0: the gathered lists when "
+                         "there is a collective) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if torch.cuda.device_count() < args.gpus and not (args.rehearse and torch.cuda.device_count() >= 1):
@@ -879,6 +911,9 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:                      # (the region is fenced: the last step's outputs are complete)
+        last = (nstep[0] - 1) % NBUF
+        dump_outputs(args.dump_outputs, *(parallel.unpack_outputs(gathered[last], batch, P) if collective else outs[last]))
 
     found = int((npts >= gridn * gridn).sum().item())
     # Everything below is a LEG beside the timed region.  A leg that fails (a box without /dev/shm, a tool that was not

@@ -12,20 +12,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "mrgingham_amd")
 
 
-REFERENCE = "/root/reference"   # present in the build container only: then the shim is compiled against the REAL point.hh
-
-
 def _build(tmp_path):
     exe = str(tmp_path / "shim_main")
-    if os.path.exists(os.path.join(REFERENCE, "point.hh")):
-        points = REFERENCE
-    else:                            # the GPU box: a stand-in with the two point types the shim names (two ints / two doubles)
-        points = str(tmp_path)
-        (tmp_path / "point.hh").write_text(
-            "namespace mrgingham {\n"
-            "struct PointInt { int x, y; PointInt(int a = 0, int b = 0) { x = a; y = b; } };\n"
-            "struct PointDouble { double x, y; PointDouble(double a = 0, double b = 0) { x = a; y = b; } };\n"
-            "}\n")
+    # the reference's point.hh is not part of this repository: a stand-in with the two point types the shim names
+    # (two ints / two doubles, with the reference's constructors)
+    points = str(tmp_path)
+    (tmp_path / "point.hh").write_text(
+        "#pragma once\n"
+        "namespace mrgingham {\n"
+        "struct PointInt { int x, y; PointInt(int a = 0, int b = 0) { x = a; y = b; } };\n"
+        "struct PointDouble { double x, y; PointDouble(double a = 0, double b = 0) { x = a; y = b; } };\n"
+        "}\n")
     cmd = ["g++", "-std=c++11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "tests", "boundary"), "-I" + points,
            "-I" + os.path.join(ROOT, "include"),
            os.path.join(ROOT, "tests", "boundary", "shim_main.cpp"), "-o", exe, "-L" + LIBDIR, "-lmrgingham_amd",

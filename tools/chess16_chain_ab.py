@@ -4,7 +4,6 @@ level images on chess_v16_pyr_kernel, 16 = levels 3..1 on chess_v16_multi_kernel
 interleaved timing of the pipelined step and of the level-0 launch inside it."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import mrgingham_amd
 from mrgingham_amd import synth

@@ -1,5 +1,5 @@
 import sys, os, time
-sys.path.insert(0, os.getcwd()); os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+sys.path.insert(0, os.getcwd())
 import numpy as np, torch
 import mrgingham_amd
 from mrgingham_amd import synth

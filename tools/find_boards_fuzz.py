@@ -4,7 +4,6 @@ sizes and pipeline depth; every board and found level must equal the synchronous
 find_boards_pipeline 0, sparse_refine 0) -- double for double.  python tools/find_boards_fuzz.py [iterations] [seed]"""
 import sys, os, random
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch
 import mrgingham_amd

@@ -2,7 +2,6 @@
 the 16-bit preprocessing, and the staging paths on a ragged width.  python tools/latency_bench.py"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch
 import mrgingham_amd

@@ -9,7 +9,6 @@ Every rank computes the same plan without communicating (parallel.plan_mixed_str
 frames, runs mrgingham_amd_find_boards_batch once per resolution it was assigned, and sends
 (frame index, found level, board) records to rank 0 in one gather.  Prints ONE JSON line on rank 0."""
 import argparse, json, os, random, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np

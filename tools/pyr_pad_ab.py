@@ -2,7 +2,6 @@
 workgroups per frame of the refinement: python tools/pyr_pad_ab.py  (MRGINGHAM_AMD_LIB = the experiment library)"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import mrgingham_amd
 from mrgingham_amd import synth

@@ -2,7 +2,6 @@
 python tools/seg_ab.py W H [B]   -- pipelined level-0 detect calls, ms per step and us per ChESS launch."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import mrgingham_amd
 from mrgingham_amd import synth

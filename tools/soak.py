@@ -4,7 +4,6 @@ compared ON THE DEVICE with a reference computed one call at a time.  python too
 A race between the pixel stream, the component streams and the scratch-set rotation would show as a mismatch."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import mrgingham_amd
 from mrgingham_amd import synth

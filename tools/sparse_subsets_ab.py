@@ -2,7 +2,6 @@
 chain on 64 x 4096x3072 (10x10 and 14x14 boards) and the pipelined full detector; outputs compared with the dense chain's."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import mrgingham_amd
 from mrgingham_amd import synth

@@ -4,7 +4,6 @@ the response with the automatic path, the level-0 launch alone (clamp, no hot li
 and the pipelined chain (ms per step, level-0 launch inside it)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import mrgingham_amd
 from mrgingham_amd import synth

@@ -4,7 +4,6 @@ the single-image wrappers are hammered from many threads (contexts spread over t
 with the one computed up front.  python tools/stress_threads.py [seconds]"""
 import sys, os, time, threading
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch
 import mrgingham_amd

@@ -7,7 +7,6 @@ import sys, os, subprocess, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "child":
     sys.path.insert(0, ROOT)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import mrgingham_amd
     from mrgingham_amd import synth
