@@ -1,0 +1,346 @@
+// The context of libmrgingham_amd.so and the helpers that more than one of its host files calls.  Internal: not
+// installed, not part of include/.  The host side is cut by concern: api.hip (context lifetime, options, scratch sets,
+// status words, the _batch entry points), multi.hip (several devices), reference.hip (the reference's own C symbols
+// over one frame), boards.hip (find_boards: the level search, synchronous and pipelined).
+#pragma once
+#include <atomic>
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/mrgingham_amd.h"
+#include "common.h"
+#include "grid.h"
+#include "kernels.h"
+
+namespace mrg {
+
+constexpr int kMaxLevel = 10;  // find_chessboard_corners.cc:433-436
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+// Scratch of one pyramid level: level images, the dense response and the
+// component tables.  Levels have their own scratch because the pixel kernels of
+// level L-1 run while the component search of level L is still working.
+struct LevelScratch {
+    int w = 0, h = 0, nframes = 0, cap = 0, cand_cap = 0, sort_cap = 0, pitch = 0, shift = -1;
+    long long arena_cap = 0;
+    DevBuf img, resp, gidx, hot_xy, parent, comp_cnt, roots, comp_first, comp_box, arena, cand, sortkeys;
+};
+
+}  // namespace mrg
+
+// Host worker threads of a context (the grid finder of mrgingham_amd_find_boards_batch): started
+// once and parked on a condition variable, because spawning threads per call cost more than the
+// grid finder itself.
+struct HostPool {
+    std::vector<std::thread> threads;
+    std::mutex m;
+    std::condition_variable cv_start, cv_done;
+    std::function<void()> job;
+    long generation = 0;
+    int wanted = 0, running = 0;
+    bool stop = false;
+
+    void loop(int id) {
+        long seen = 0;
+        for (;;) {
+            std::unique_lock<std::mutex> lk(m);
+            cv_start.wait(lk, [&] { return stop || (generation != seen && id < wanted); });
+            if (stop) return;
+            seen = generation;
+            lk.unlock();
+            job();
+            lk.lock();
+            if (--running == 0) cv_done.notify_all();
+        }
+    }
+    // starts f on n pool threads (the caller is not one of them) and returns; wait() returns when they are done
+    void start(int n, const std::function<void()>& f) {
+        if (n <= 0) return;
+        {
+            std::unique_lock<std::mutex> lk(m);
+            while ((int)threads.size() < n) {
+                const int id = (int)threads.size();
+                threads.emplace_back([this, id] { loop(id); });
+            }
+            job = f;
+            wanted = n;
+            running = n;
+            ++generation;
+        }
+        cv_start.notify_all();
+    }
+    void wait() {
+        std::unique_lock<std::mutex> lk(m);
+        cv_done.wait(lk, [&] { return running == 0; });
+        wanted = 0;
+    }
+    // runs f on n threads (the caller is one of them) and returns when all of them are done
+    void run(int n, const std::function<void()>& f) {
+        if (n <= 1) { f(); return; }
+        start(n - 1, f);
+        f();
+        wait();
+    }
+    ~HostPool() {
+        {
+            std::unique_lock<std::mutex> lk(m);
+            stop = true;
+        }
+        cv_start.notify_all();
+        for (auto& t : threads) t.join();
+    }
+};
+
+constexpr int kMaxSets = 3;  // scratch sets a context can rotate through (option "scratch_sets": 2 or 3)
+
+struct mrgingham_amd_ctx {
+    int device = 0;
+    int nsets = 2;
+    bool nsets_fixed = false;  // option "scratch_sets" given: no automatic choice
+    double max_set_bytes = 0;
+    // HIP streams of a context: `pix` runs the pixel kernels (pyramid, ChESS) back to back, each
+    // over the whole batch; `ccs[set]` run the latency-bound component kernels (a serial chain
+    // detect -> refine -> refine ... per call) underneath them, one stream per scratch set so that
+    // the chains of consecutive calls overlap each other as well.  Events order cc(L) after pix(L).
+    hipStream_t pix = nullptr;
+    hipStream_t ccs[kMaxSets] = {};
+    // Device buffers the last call of each set wrote / read (caller-owned outputs and inputs):
+    // consecutive calls run on different component streams, so a call that touches a buffer the
+    // previous call wrote (or writes one it read) must wait for it explicitly.
+    struct Span { const char* p; size_t n; };
+    std::vector<Span> last_w[kMaxSets], last_r[kMaxSets];
+    hipEvent_t ev_pix[mrg::kMaxLevel + 1] = {};
+    // Level scratch exists `nsets` times (2, or 3 with option "scratch_sets"): call N+1 fills set (N+1) % nsets on
+    // the pixel stream while the component streams still work through the calls before it in the other sets.
+    // Two sets keep two component chains in flight, which hides them as long as a chain is shorter than two
+    // steps of the pixel kernels; small frames (64 x 640x480: chain 430 us, pixel kernels 62 us) and dense boards
+    // want three.
+    hipEvent_t ev_cc_done[kMaxSets] = {};
+    hipEvent_t ev_ext = nullptr;  // mrgingham_amd_after_stream
+    bool cc_pending[kMaxSets] = {};
+    int cur = 0;  // scratch set of the call being queued
+    std::string err;
+    // hot-pixel / component table capacity = level pixels >> shift entries per frame, shift = min(cap_shift,
+    // grown_shift[level]).  The default (1/128: 98 304 hot pixels for a 4096x3072 frame, whose bench frames have
+    // ~1.3e3 and whose textured ones ~7e4) keeps the tables at 0.35 B per pixel; a frame that needs more is
+    // reported (MRGINGHAM_AMD_ERR_CAPACITY at the sync) and the tables of its level GROW to what it asked for, so
+    // the same call succeeds when it is made again.
+    int cap_shift = 7;
+    int grown_shift[mrg::kMaxLevel + 1];
+    bool use_v0 = false;  // reference-shaped ChESS kernel instead of the tuned one
+    int sparse_subsets = 2;  // option "sparse_subsets": workgroups per frame of the sparse refinement (1 .. 4; 4 measures like 2)
+    int chess_variant_hot = 0;  // the levels of a chain (clamp + hot list): 16 = chess_v16_hot_kernel / chess_v16_multi_kernel, 0 = chess_v1
+    int pre_fused = 1;  // option "preprocess_fused": CLAHE blend + 3x3 blur in one kernel where the geometry allows (0: always two kernels, the A/B and test hook)
+    int chess_seg = 0, chess16_seg = 0;  // options "chess_seg" / "chess16_seg": rows per workgroup of the response kernels, 0 = automatic
+    int chess_variant = 0;  // the response without a hot list: 0 = chess_v16_kernel (chess16.hip) where it pays, 1 = chess_v1 always, 16 = chess_v16 wherever it can run
+    // levels 3..1 of a chain in one launch (set_option "multi_level_launch"): +1.5 % chain rate, but the
+    // component chains then start later and overlap the level-0 launch more (+5 % on that launch): off
+    // chain_batch: 0 = one ChESS launch per level; 1 = levels 3..1 in one launch (default: two kernel
+    // boundaries fewer per step, 1.129 -> 1.113 ms per 64 frames of 4096x3072); 2 = levels 0..3 in one
+    // launch (measured slower: 1.171 ms)
+    int multi_level = 1;
+    int last_fused = 0, last_merged = 0;  // mrgingham_amd_chain_info
+    // option "sparse_refine": chain_batch computes the response of the levels BELOW the start level only in the cells
+    // around the points it refines there (chain_batch_sparse)
+    int sparse_refine = 1;     // (default: where it pays)
+    bool sparse_seen = false;  // a chain has taken the sparse schedule (choose_sets)
+    mrg::DevBuf sparse_stat;   // [0]: frames the sparse schedule reported and the library repeated densely (mrgingham_amd_sparse_fallbacks)
+    int fuse_pyramid = 1;   // option "fuse_pyramid": chain calls take the level images 1..3 out of the level-0 response kernel
+    // component-chain schedule of chain_batch: 0 = every level's component kernels start as soon as
+    // that level's response is done; 1 (default) = levels 1 and 0 wait for the level-0 response (they then
+    // run underneath the NEXT call's pyramid and small levels instead of underneath this call's level 0:
+    // same step time, level-0 launch 668 -> 657 us); 2 = every level waits for the level-0 response
+    int cc_schedule = 1;
+    int cc_lds = 1;  // component search out of LDS for frames with few hot pixels (option "cc_lds"; bits 1-3: timing ablations)
+
+    mrg::LevelScratch lvs[kMaxSets][mrg::kMaxLevel + 1];
+    mrg::DevBuf counters2[kMaxSets];  // per scratch set: hot_cnt words [level][counters_nf], then status words, then path words
+    int counters_nf = 0;
+    struct PointScratch { mrg::DevBuf leader, need, nseeds, seeds, sroot, cand_xy, cand_counts, cell_list, cell_cnt, flag_list; } pts[kMaxSets];  // per scratch set
+    mrg::DevBuf aux_img, io_frame, io_out, io_counts;
+    void* io_res_pin = nullptr;  // page-locked: count + first candidates of the single-frame detector
+    // page-locked copies of the sets' status words ([level][counters_nf], what mrgingham_amd_sync inspects): they follow every
+    // op on its component stream (end_op), so that the sync behind it reads host memory instead of making a blocking copy
+    int32_t* status_pin[kMaxSets] = {};
+    size_t status_pin_words[kMaxSets] = {};
+    bool status_copied[kMaxSets] = {};  // the LAST op on the set left its words in status_pin
+    void* io_pin = nullptr;  // page-locked staging of mrgingham_ChESS_response_5's way back
+    size_t io_pin_bytes = 0;
+    hipEvent_t io_ev[4] = {};
+    mrg::DevBuf clk;  // two u64: shader cycles and constant-rate ticks of the probed workgroups (mrgingham_amd_sclk_mhz)
+    mrg::DevBuf pre_scratch, pre_tmp, pre_out, pre16_scratch, io_frame16, dbg_img, dbg_resp, blob_scratch, blob_nodes, blob_out;
+    mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
+    // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
+    // context of THIS context's device, created on first use -- not on the calling thread's default context, which
+    // lives on MRGINGHAM_AMD_DEVICE / device 0 and cannot touch another GPU's frames
+    mrgingham_amd_ctx* one = nullptr;
+    HostPool submit_pool;  // mrgingham_amd_chain_multi: the thread that queues this context's shard
+    HostPool pool;  // preprocessing: extrema + tile histograms + LUTs, CLAHE output before the blur
+    // mrgingham_amd_find_boards_submit / _collect: one job per scratch set (its level images stay in the set's scratch
+    // between the first pass and the refinement)
+    struct BoardsJob {
+        int state = 0;  // 0 free, 1 first pass queued, 2 host part done (refinement queued, or nothing to refine)
+        int ticket = -1, set = 0;
+        mrgingham_amd_frames fr{};
+        int gridn = 0, level_arg = 0, nthreads = 0, nlev = 0, levs[3] = {0, 0, 0}, cap = 0;
+        double* h_boards = nullptr;
+        signed char* h_found = nullptr;
+        signed char* h_levels = nullptr;  // optional: the refinement level of every corner, [frame][gridn^2]
+        bool do_refine = true;
+        hipEvent_t ev_a = nullptr, ev_b = nullptr;
+        hipEvent_t ev_a0 = nullptr, ev_b0 = nullptr;  // where the two device parts begin (mrgingham_amd_find_boards_stats)
+        bool refine_queued = false;
+        int top = 0;  // the highest level a board of the job was found at (levels below it are refined)
+        // device images of the pinned staging, laid out like it (fb_layout) so that each direction is ONE copy:
+        // d_cnt = counts | candidates (first pass), d_pts = boards | levels | point counts (refinement), d_pts0 = boards |
+        // levels as they went in (what the dense repeat of a sparse refinement starts from)
+        mrg::DevBuf d_cnt, d_pts, d_pts0;
+        void* pin = nullptr;  // pinned host staging: counts, candidates | boards, levels, point counts
+        size_t pin_bytes = 0;
+        // the host part in progress (fb_host_begin .. fb_host_end): candidate lists of frames re-run at full capacity,
+        // the frame counter of the grid-finder threads
+        std::vector<std::vector<int32_t>> big;
+        std::atomic<int> next{0};
+        bool grid_running = false;
+        int nworkers = 0;
+        mrgingham_amd_ctx* owner = nullptr;
+    } jobs[kMaxSets];
+    // mrgingham_amd_chain_multi: this context's shard of the outputs before it travels to the first context's device
+    mrg::DevBuf mg_pts, mg_lv, mg_np;
+    hipStream_t mg_stream = nullptr;
+    hipEvent_t mg_done = nullptr;
+    bool mg_pending = false;
+    int next_ticket = 0;
+    std::vector<std::pair<int, int>> done_tickets;  // (ticket, status) of jobs completed before they were collected
+    int fb_pipeline = 1;  // option "find_boards_pipeline"
+    // mrgingham_amd_find_boards_stats: host milliseconds by phase of submit / collect, batches, and what the grid-finder
+    // threads did (their thread-local clocks, grid.h, added up under the mutex when a worker leaves)
+    double fb_prof[10] = {};
+    long fb_prof_n = 0;
+    int fb_threads_used = 0;
+    double fb_dev_ms[2] = {0, 0};  // device milliseconds: first passes (submit .. candidates on the host), refinements
+    std::mutex fb_stat_mu;
+    mrg::GridPhaseClock fb_grid{0, 0, 0, 0, 0, 0};
+    int pts_nframes = 0, pts_pitch = 0;
+    // levels (and frame counts) whose status words must be checked at the next sync
+    int pending_frames[kMaxSets][mrg::kMaxLevel + 1] = {};
+
+    // dominant-kernel timing
+    bool timing = false;
+    bool clk_on = false;  // the engine-clock probe of the level-0 response launches (mrgingham_amd_sclk_mhz)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    std::vector<hipEvent_t> event_pool;
+    std::vector<int32_t> host_status;
+    std::vector<char> io_host_block;  // refine_on_device: the points block as it travels
+};
+
+namespace mrg {
+
+constexpr long long kSparsePaysPixels = 96ll << 20;  // option "sparse_refine" 1: calls with at least this many frame pixels
+
+// api.hip: errors, buffers, level scratch
+int fail(mrgingham_amd_ctx* ctx, int code, const char* fmt, ...);
+int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes);
+hipError_t copy_rows_async(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows,
+                           hipMemcpyKind kind, hipStream_t s);
+int level_dims(int W, int H, int level, int* w, int* h);
+int validate_frames(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* f);
+int ensure_level_set(mrgingham_amd_ctx* ctx, int set, int level, int nframes, int W, int H, int pitch);
+int choose_sets(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr);
+int ensure_level(mrgingham_amd_ctx* ctx, int level, int nframes, int W, int H, int pitch);
+int ensure_points(mrgingham_amd_ctx* ctx, int nframes, int pitch);
+
+// api.hip: the scratch-set rotation of a call, its status words, its pixel-stream and component-stream work
+void begin_op(mrgingham_amd_ctx* ctx, int max_level);
+void order_after_previous(mrgingham_amd_ctx* ctx, std::initializer_list<mrgingham_amd_ctx::Span> w,
+                          std::initializer_list<mrgingham_amd_ctx::Span> r);
+void end_op(mrgingham_amd_ctx* ctx);
+int harvest_status(mrgingham_amd_ctx* ctx, int set, int level, int* rc, bool quiet = false);
+void queue_level_images(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int max_level, bool levels_1_to_3 = true,
+                        bool gentle = false);
+LevelBatch level_batch_of(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level);
+LevelBatch queue_level_chess(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level);
+int queue_sparse_levels(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int top, RefineIO io,
+                        const SparseRestore& restore, bool dense_only = false);
+
+// reference.hip: one frame that lives on the device
+bool check_level_and_layout(const char* fn, int Nrows, int Ncols, int stride, int level);
+bool detect_one_frame_all(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr1, int level, std::vector<int32_t>& xy,
+                          int32_t* count_out, bool debug = false, const char* debug_image_filename = nullptr);
+int refine_on_device(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, double* points_xy, signed char* level,
+                     int Npoints, int image_pyramid_level, bool debug = false, const char* debug_image_filename = nullptr);
+
+// boards.hip
+struct GridScratch { std::vector<PointI> cand; std::vector<PointD> grid; };
+bool grid_of_candidates(const int32_t* xy, int n, int gridn, double* out, GridScratch* scratch = nullptr);
+int find_board_on_device(mrgingham_amd_ctx* ctx, const char* who, const mrgingham_amd_frames* fr, int gridn,
+                         int image_pyramid_level, bool do_refine, std::vector<PointD>& board, std::vector<signed char>& lv,
+                         bool debug = false, const char* debug_image_filename = nullptr);
+void fb_drain(mrgingham_amd_ctx* ctx);
+
+// accessors the chain path calls per level: inline
+static inline LevelScratch* cur_levels(mrgingham_amd_ctx* ctx) { return ctx->lvs[ctx->cur]; }
+static inline hipStream_t cur_cc(mrgingham_amd_ctx* ctx) { return ctx->ccs[ctx->cur]; }
+static inline int32_t* hot_cnt_of(mrgingham_amd_ctx* ctx, int level) {
+    return (int32_t*)ctx->counters2[ctx->cur].p + (size_t)level * ctx->counters_nf;
+}
+static inline int32_t* status_of(mrgingham_amd_ctx* ctx, int level) {
+    return (int32_t*)ctx->counters2[ctx->cur].p + (size_t)(kMaxLevel + 1 + level) * ctx->counters_nf;
+}
+static inline int32_t* path_of(mrgingham_amd_ctx* ctx, int level) {
+    return (int32_t*)ctx->counters2[ctx->cur].p + (size_t)(2 * (kMaxLevel + 1) + level) * ctx->counters_nf;
+}
+
+static inline CompTables tables_of(mrgingham_amd_ctx* ctx, int level) {
+    const LevelScratch& L = cur_levels(ctx)[level];
+    CompTables t;
+    t.cap = L.cap;
+    t.hot_cnt = hot_cnt_of(ctx, level);
+    t.hot_xy = (uint32_t*)L.hot_xy.p;
+    t.parent = (int32_t*)L.parent.p;
+    t.comp_cnt = (int32_t*)L.comp_cnt.p;
+    t.comp_box = (int4*)L.comp_box.p;
+    t.roots = (int32_t*)L.roots.p;
+    t.comp_first = (int32_t*)L.comp_first.p;
+    t.gidx = (uint2*)L.gidx.p;
+    t.gw = (L.w + 7) / 8;
+    t.gidx_pitch = (long long)t.gw * L.h;
+    t.arena = (uint32_t*)L.arena.p;
+    t.arena_cap = L.arena_cap;
+    t.cand_cap = L.cand_cap;
+    t.cand = (Cand*)L.cand.p;
+    t.sortkeys = (unsigned long long*)L.sortkeys.p;
+    t.sort_cap = L.sort_cap;
+    t.status = status_of(ctx, level);
+    t.path = path_of(ctx, level);
+    t.lds_path = ctx->cc_lds;
+    t.only = nullptr;
+    return t;
+}
+
+// The reference-symbol wrappers (and the calls that span several devices: chain_multi, sync_multi, stream_wait_multi,
+// gather_rccl) work on the calling thread's context, which may live on another device than the one the
+// CALLER has current (the k-th thread's context is on device k % devices): they put the caller's device back when they
+// return -- a worker thread of a multi-GPU host (PyTorch, ...) keeps the current device it had.
+struct CallerDevice {
+    int prev = -1;
+    CallerDevice() {
+        if (hipGetDevice(&prev) != hipSuccess) {
+            prev = -1;
+            (void)hipGetLastError();
+        }
+    }
+    ~CallerDevice() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+}  // namespace mrg

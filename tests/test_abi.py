@@ -114,8 +114,11 @@ def test_shipped_library_has_no_experiment_hooks():
                  b"chess_v16_pyr_kernel", b"chess_v16_multi_kernel", b"chess_v16_pair_kernel", b"chess16_pair"):
         assert name not in blob, name
     assert b"MRGINGHAM_AMD_DEVICE" in blob                  # the one variable it does read
-    for src in ("api.hip", "chess.hip", "cc.hip"):
-        text = open(os.path.join(here, "mrgingham_amd", "csrc", src)).read()
+    csrc = os.path.join(here, "mrgingham_amd", "csrc")
+    srcs = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")))
+    assert {"api.hip", "boards.hip", "chess.hip", "cc.hip"} <= set(srcs)
+    for src in srcs:
+        text = open(os.path.join(csrc, src)).read()
         lines = text.split("\n")
         depth = 0
         for ln in lines:                                    # every getenv outside MRGINGHAM_AMD_DEVICE sits in #ifdef MRG_EXPERIMENT

@@ -92,6 +92,28 @@ def test_find_board_negative_and_argument_paths():
     assert mrgingham_amd.find_board(img, debug_sequence="3,4") is not None
 
 
+
+def test_find_board_debug_path_equals_the_pipelined_path():
+    """find_board(debug=True) takes the level-by-level search (the reference's dumps need it), every other call
+    the pipelined detector: same boards, double for double."""
+    import glob
+    import os
+
+    def clean():
+        for f in glob.glob("/tmp/mrgingham-*"):
+            os.remove(f)
+
+    img = synth.board_frame(640, 480, 10, 2).numpy()
+    clean()
+    try:
+        for level in (-1, 1):
+            want = mrgingham_amd.find_board(img, image_pyramid_level=level)
+            got = mrgingham_amd.find_board(img, image_pyramid_level=level, debug=True)
+            assert want is not None and got is not None, level
+            assert np.array_equal(got, want), level
+    finally:
+        clean()
+
 def test_find_boards_batch_adaptive_levels():
     """Per-frame adaptive pyramid depth: frames whose grid is found at level 3 stop there, the others
     go on to levels 2, 1, 0; every board equals the single-frame detector's."""
