@@ -35,7 +35,8 @@ extern "C" {
  *      is a multiple of 8 bytes; the reference-symbol wrappers restore the caller's current HIP device.
  *   4  round 6: mrgingham_amd_sclk_mhz added; options "chess_seg" / "chess16_seg" are per context (they were process-wide) and
  *      mean balanced segments, option "preprocess_fused"; _gather_rccl, _chain_multi, _sync_multi, _stream_wait_multi restore
- *      the caller's current HIP device; _gather_rccl needs no RCCL header or library at build time and never loads a second RCCL. */
+ *      the caller's current HIP device; _gather_rccl needs no RCCL header or library at build time and never loads a second RCCL.
+ *      Later, additive: mrgingham_amd_preprocess16_batch (16-bit frames on the device; option "preprocess_fused" covers it). */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -258,6 +259,17 @@ int mrgingham_amd_box_blur_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_fra
  * images and must not alias the input.  OpenCV arithmetic: parity unpinned. */
 int mrgingham_amd_preprocess_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* frames, int do_clahe,
                                    int blur_radius, uint8_t* d_out, void* stream);
+
+/* The same for 16-bit frames (mrgingham-from-image.cc:85-92, :106-111): when do_clahe, cv::normalize(0, 65535,
+ * NORM_MINMAX) then CLAHE (clip limit 8, 8x8 tiles, 65 536 bins); convertTo(CV_8U, 255/65535); the box blur.
+ * frames: device uint16, frame f row y at d_frames + f*frame_pitch + y*stride (pitch and stride in ELEMENTS);
+ * d_out: nframes dense width x height bytes, must not alias the input.  Asynchronous on `stream` (NULL = default).
+ * Arguments are checked like mrgingham_amd_preprocess_batch's (MRGINGHAM_AMD_ERR_ARG, nothing written).  The tile
+ * tables take up to 24 MiB per frame (full-range data); a batch is worked through in chunks of frames whose tables stay
+ * within 1 GiB of context scratch.  Same bytes as mrgingham_amd_preprocess_image16 per frame. */
+int mrgingham_amd_preprocess16_batch(mrgingham_amd_ctx* ctx, const uint16_t* d_frames, int64_t frame_pitch, int nframes,
+                                     int width, int height, int stride, int do_clahe, int blur_radius,
+                                     uint8_t* d_out, void* stream);
 
 /* find_chessboard_corners_from_image_array for every frame of the batch at one
  * pyramid level.  Device outputs: d_xy holds nframes blocks of
@@ -487,6 +499,10 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *   "preprocess_fused"    1 (default): mrgingham_amd_preprocess_batch(do_clahe, blur_radius 1) -- the reference tool's default
  *                         chain -- blends the CLAHE tile LUTs and blurs in ONE pass over the frame where the geometry allows
  *                         (rows of 16-byte multiples, tiles at least 34 rows high); 0: always two kernels.  Same bytes.
+ *                         Also mrgingham_amd_preprocess16_batch (and the 16-bit images of _preprocess_image16 /
+ *                         _process_image_ex): 1 = three passes over the pixels (extrema, raw-value tile histograms,
+ *                         blend + blur), 0 = the one-image kernels (normalised 16-bit copy, 65 536-bin tables per tile,
+ *                         then the box blur as its own kernel).  Same bytes.
  * Builds made with -DMRG_EXPERIMENT (make -C mrgingham_amd/csrc EXPERIMENT=1 -> libmrgingham_amd_experiment.so)
  * additionally accept the timing ablations and phase clocks of tools/ ("cc_lds" bits 2, 4, 8, 16, 128, 512,
  * "cc_schedule", "chess_stage", "chess_multi_min_blocks", "chess_v0" = the reference-shaped ChESS kernel as an on-device
@@ -523,7 +539,7 @@ int mrgingham_amd_after_stream(mrgingham_amd_ctx* ctx, void* stream);
 void mrgingham_amd_set_kernel_timing(mrgingham_amd_ctx* ctx, int enable);
 double mrgingham_amd_chess_kernel_ms(mrgingham_amd_ctx* ctx, int* nlaunches);
 
-/* The engine clock the level-0 response kernels (and the fused blend + blur kernel of mrgingham_amd_preprocess_batch) ACTUALLY ran at, in MHz, averaged over the launches issued since the last
+/* The engine clock the level-0 response kernels (and the fused blend + blur kernels of mrgingham_amd_preprocess_batch / _preprocess16_batch) ACTUALLY ran at, in MHz, averaged over the launches issued since the last
  * call while kernel timing was enabled (1 or 2): workgroup 0 of each launch reads the shader-cycle counter (s_memtime) and the
  * constant-rate counter (s_memrealtime, hipDeviceAttributeWallClockRate) at its start and end and adds the two differences
  * to a pair of device counters -- four scalar instructions in one workgroup of the launch.  A VALU-bound kernel scales with

@@ -445,13 +445,28 @@ class Detector:
 
     def preprocess(self, frames, clahe=True, blur_radius=1):
         """The reference CLI's preprocessing (mrgingham-from-image.cc:71-111): normalize + CLAHE(8),
-        then a box blur; on torch's current stream."""
+        then a box blur; on torch's current stream.  uint8 [B,H,W] frames, or uint16 ones (the tool's 16-bit branch,
+        :85-92: normalize to 0..65535, CLAHE(8) on 16 bits, convertTo 8 bit with 255/65535) -> uint8 [B,H,W]."""
         t = self.torch
+        if frames.dtype == t.uint16:
+            return self._preprocess16(frames, clahe, blur_radius)
         fr, B, H, W = self._frames(frames)
         out = t.empty((B, H, W), dtype=t.uint8, device=frames.device)
         stream = t.cuda.current_stream(frames.device).cuda_stream
         self._check(self.L.mrgingham_amd_preprocess_batch(self.ctx, ctypes.byref(fr), int(bool(clahe)),
                                                           int(blur_radius), out.data_ptr(), stream))
+        return out
+
+    def _preprocess16(self, frames, clahe, blur_radius):
+        t = self.torch
+        if not frames.is_cuda or frames.dim() != 3 or frames.stride(2) != 1:
+            raise ValueError("16-bit frames: a [B,H,W] uint16 tensor on the device with unit column stride")
+        B, H, W = frames.shape
+        out = t.empty((B, H, W), dtype=t.uint8, device=frames.device)
+        stream = t.cuda.current_stream(frames.device).cuda_stream
+        self._check(self.L.mrgingham_amd_preprocess16_batch(
+            self.ctx, frames.data_ptr(), frames.stride(0) if B > 1 else H * frames.stride(1), B, W, H,
+            frames.stride(1) if H > 1 else W, int(bool(clahe)), int(blur_radius), out.data_ptr(), stream))
         return out
 
     def detect(self, frames, level, capacity=4096, sync=True, retry=True, out=None):

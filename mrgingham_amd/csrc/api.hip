@@ -1022,6 +1022,68 @@ int mrgingham_amd_preprocess_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_f
     return 0;
 }
 
+int mrgingham_amd_preprocess16_batch(mrgingham_amd_ctx* ctx, const uint16_t* d_frames, int64_t frame_pitch, int nframes,
+                                     int width, int height, int stride, int do_clahe, int blur_radius, uint8_t* d_out,
+                                     void* stream) {
+    if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
+    if ((!d_frames && nframes > 0) || nframes < 0 || width < 0 || height < 0 || stride < width || frame_pitch < 0)
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad frame batch descriptor");
+    if (width > 32767 || height > 32767)
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "frames larger than 32767 pixels per side are not supported");
+    if (blur_radius < 0 || blur_radius > 64 || !d_out) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad blur radius or output");
+    if (do_clahe && (width < 8 || height < 8))
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "CLAHE needs a frame of at least 8x8 pixels");
+    if (nframes == 0 || width == 0 || height == 0) return 0;
+    MRG_HIP_CHECK(hipSetDevice(ctx->device));
+    return queue_preprocess16(ctx, d_frames, frame_pitch, nframes, width, height, stride, do_clahe, blur_radius, d_out,
+                              (hipStream_t)stream);  // (the stream used as given: NULL is HIP's default stream)
+}
+
+}  // extern "C"
+
+// the work of mrgingham_amd_preprocess16_batch, its arguments checked (and frames of any size: the tile grid of a frame
+// below 8 pixels per side is 8 tiles of one pixel, as the one-image path of the command-line tool has always taken it)
+int mrg::queue_preprocess16(mrgingham_amd_ctx* ctx, const uint16_t* d_frames, int64_t frame_pitch, int nframes, int width, int height,
+                       int stride, int do_clahe, int blur_radius, uint8_t* d_out, hipStream_t s) {
+    if (blur_radius < 0 || blur_radius > 64) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad blur radius");
+    const size_t frame_bytes = (size_t)width * height;
+    const int chunk = preprocess16_batch_chunk_frames();
+    const int nf = nframes < chunk ? nframes : chunk;
+    int rc;
+    if (ctx->pre_fused) {
+        uint8_t* tmp = nullptr;
+        if (do_clahe && (rc = ensure(ctx, ctx->pre16_scratch, preprocess16_batch_scratch_bytes(nf)))) return rc;
+        if (blur_radius > 1) {
+            if ((rc = ensure(ctx, ctx->pre_tmp, frame_bytes * nframes))) return rc;
+            tmp = (uint8_t*)ctx->pre_tmp.p;
+        }
+        if (!launch_preprocess16_batch(d_frames, (long long)frame_pitch, nframes, width, height, stride, do_clahe != 0, blur_radius,
+                                       d_out, ctx->pre16_scratch.p, tmp, s, ctx->clk_on ? (unsigned long long*)ctx->clk.p : nullptr))
+            return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "frame too small to tile");
+    } else {
+        // option "preprocess_fused" 0: the one-image kernels (preprocess16.hip) + launch_box_blur, chunk by chunk
+        if (do_clahe && (rc = ensure(ctx, ctx->pre16_scratch, preprocess16_scratch_bytes(nf, width, height)))) return rc;
+        uint8_t* eight = d_out;
+        if (blur_radius > 0) {
+            if ((rc = ensure(ctx, ctx->pre_tmp, frame_bytes * nf))) return rc;
+            eight = (uint8_t*)ctx->pre_tmp.p;
+        }
+        for (int f0 = 0; f0 < nframes; f0 += nf) {
+            const int n = nframes - f0 < nf ? nframes - f0 : nf;
+            uint8_t* o = d_out + (size_t)f0 * frame_bytes;
+            if (!launch_preprocess16(d_frames + (size_t)f0 * frame_pitch, (long long)frame_pitch, n, width, height, stride,
+                                     do_clahe != 0, 8.0, blur_radius > 0 ? eight : o, ctx->pre16_scratch.p, s))
+                return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "frame too small to tile");
+            if (blur_radius > 0)
+                launch_box_blur(FrameBatch{eight, (long long)frame_bytes, width, height, width}, blur_radius, o, 0, n, s);
+        }
+    }
+    MRG_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
 int mrgingham_amd_detect_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level, int32_t* d_xy,
                                int capacity_per_frame, int32_t* d_counts) {
     int rc = validate_frames(ctx, fr);

@@ -257,6 +257,8 @@ int ensure_level_set(mrgingham_amd_ctx* ctx, int set, int level, int nframes, in
 int choose_sets(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr);
 int ensure_level(mrgingham_amd_ctx* ctx, int level, int nframes, int W, int H, int pitch);
 int ensure_points(mrgingham_amd_ctx* ctx, int nframes, int pitch);
+int queue_preprocess16(mrgingham_amd_ctx* ctx, const uint16_t* d_frames, int64_t frame_pitch, int nframes, int width, int height,
+                       int stride, int do_clahe, int blur_radius, uint8_t* d_out, hipStream_t s);
 
 // api.hip: the scratch-set rotation of a call, its status words, its pixel-stream and component-stream work
 void begin_op(mrgingham_amd_ctx* ctx, int max_level);

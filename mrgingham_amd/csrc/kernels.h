@@ -74,6 +74,18 @@ size_t preprocess16_scratch_bytes(int nframes, int w, int h);
 bool launch_preprocess16(const uint16_t* frames, long long pitch, int nframes, int w, int h, int stride, bool do_clahe,
                          double clip_limit, uint8_t* out8, void* scratch, hipStream_t s);
 
+// preprocess16_batch.hip: the same for a batch, in three passes over the pixels (extrema, raw-value tile histograms, blend +
+// blur).  The tables of a frame take kTableEntries x 6 bytes (64 tiles x 65 536 values: laid out for full-range data), so
+// the call works through the batch in chunks of preprocess16_batch_chunk_frames() frames whose tables stay within
+// kPreprocess16TableBudget; `scratch` holds preprocess16_batch_scratch_bytes(min(nframes, chunk)).  `tmp` (dense w x h bytes
+// per frame) is used for blur radii other than 0 and 1 only.  `clk`: the engine-clock probe of the blend launches.
+constexpr size_t kPreprocess16TableBudget = (size_t)1 << 30;
+int preprocess16_batch_chunk_frames();
+size_t preprocess16_batch_scratch_bytes(int chunk_frames);
+bool launch_preprocess16_batch(const uint16_t* frames, long long pitch, int nframes, int w, int h, int stride, bool do_clahe,
+                               int blur_radius, uint8_t* out, void* scratch, uint8_t* tmp, hipStream_t s,
+                               unsigned long long* clk = nullptr);
+
 // blobs.hip: cv::SimpleBlobDetector as find_blobs.cc:14-46 configures it (device border following, host filters)
 struct BlobScratchLayout {
     int wpr;

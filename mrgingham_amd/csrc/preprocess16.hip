@@ -7,27 +7,13 @@
 // Not a throughput path (16-bit calibration images arrive one at a time); kept simple.
 #include "common.h"
 #include "kernels.h"
+#include "pre16.h"
 
 namespace mrg {
 
 namespace {
 
-constexpr int kTiles16 = 8, kBins16 = 65536;
-
-__device__ __forceinline__ int reflect101_16(int i, int n) {
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
-    return i;
-}
-
-__device__ __forceinline__ unsigned sat_rint(float v, float hi) {  // saturate_cast<>(cvRound(v)): round half to even
-    const float r = __builtin_rintf(v);
-    return (unsigned)(r < 0.f ? 0.f : (r > hi ? hi : r));
-}
-
-struct Geom16 {
-    int w, h, ew, eh, tw, th;
-};
+using namespace pre16;
 
 __global__ __launch_bounds__(256) void minmax16_kernel(const uint16_t* in, long long pitch, int w, int h, int stride,
                                                        unsigned* mm) {
@@ -183,21 +169,11 @@ bool launch_preprocess16(const uint16_t* frames, long long pitch, int nframes, i
         hipLaunchKernelGGL(convert16to8_kernel, dim3(blocks, nframes), dim3(256), 0, s, frames, pitch, w, h, stride, out8);
         return true;
     }
-    Geom16 g{w, h, w, h, 0, 0};
-    if (w % kTiles16 != 0 || h % kTiles16 != 0) {
-        g.ew = w + (kTiles16 - w % kTiles16);
-        g.eh = h + (kTiles16 - h % kTiles16);
-    }
-    g.tw = g.ew / kTiles16;
-    g.th = g.eh / kTiles16;
+    const Geom16 g = geom16(w, h);
     if (g.tw <= 0 || g.th <= 0) return false;
     const long long area = (long long)g.tw * g.th;
     const float lut_scale = (float)(kBins16 - 1) / (float)area;
-    int clip = 0;
-    if (clip_limit > 0.0) {
-        clip = (int)(clip_limit * (double)area / kBins16);
-        if (clip < 1) clip = 1;
-    }
+    const int clip = clip16(clip_limit, area);
     char* p = (char*)scratch;
     unsigned* mm = (unsigned*)p;                      p += (((size_t)nframes * 8 + 255) / 256) * 256;
     uint16_t* norm = (uint16_t*)p;                    p += (((size_t)nframes * w * h * 2 + 255) / 256) * 256;

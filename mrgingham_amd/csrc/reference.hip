@@ -230,21 +230,14 @@ static bool blobs_of_host_frame(int Nrows, int Ncols, int stride, const char* im
 static bool preprocess16_on_device(mrgingham_amd_ctx* ctx, const uint16_t* image, int width, int height, int stride,
                                    int do_clahe, int blur_radius, mrgingham_amd_frames* fr) {
     const size_t npx = (size_t)width * height;
-    if (ensure(ctx, ctx->io_frame16, npx * 2 + 64) || ensure(ctx, ctx->pre_tmp, npx + 64) || ensure(ctx, ctx->pre_out, npx + 64) ||
-        ensure(ctx, ctx->pre16_scratch, preprocess16_scratch_bytes(1, width, height)))
-        return false;
+    if (ensure(ctx, ctx->io_frame16, npx * 2 + 64) || ensure(ctx, ctx->pre_out, npx + 64)) return false;
     if (copy_rows_async(ctx->io_frame16.p, (size_t)width * 2, image, (size_t)stride * 2, (size_t)width * 2, height,
                         hipMemcpyHostToDevice, ctx->pix) != hipSuccess)
         return false;
-    uint8_t* eight = (uint8_t*)(blur_radius > 0 ? ctx->pre_tmp.p : ctx->pre_out.p);
-    if (!launch_preprocess16((const uint16_t*)ctx->io_frame16.p, (long long)npx, 1, width, height, width, do_clahe != 0,
-                             8.0, eight, ctx->pre16_scratch.p, ctx->pix))
+    if (queue_preprocess16(ctx, (const uint16_t*)ctx->io_frame16.p, (int64_t)npx, 1, width, height, width, do_clahe, blur_radius,
+                           (uint8_t*)ctx->pre_out.p, ctx->pix))
         return false;
-    *fr = mrgingham_amd_frames{eight, (int64_t)npx, 1, width, height, width};
-    if (blur_radius > 0) {
-        if (mrgingham_amd_box_blur_batch(ctx, fr, blur_radius, (uint8_t*)ctx->pre_out.p, ctx->pix)) return false;
-        fr->frames = (const uint8_t*)ctx->pre_out.p;
-    }
+    *fr = mrgingham_amd_frames{(const uint8_t*)ctx->pre_out.p, (int64_t)npx, 1, width, height, width};
     return true;
 }
 
