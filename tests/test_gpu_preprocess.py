@@ -32,14 +32,14 @@ def _frames(kind, H, W, n, seed):
     ("noise", 101, 128),
     ("board", 1080, 1920),
     ("noise", 600, 1296),    # the fused blend + blur kernel: two 1024-column workgroups, the second partial; 16 rows per wave
-    ("ramp", 272, 2064),     # ... three of them, 8 rows per wave, cells 162 px wide (nine across a workgroup)
+    ("ramp", 272, 2064),     # ... three of them, 8 rows per wave, cells 258 px wide (up to five across a workgroup)
 ])
 @pytest.mark.parametrize("clahe,blur", [(True, 1), (True, 0), (False, 1), (False, 2), (True, 3)])
 def test_preprocess_matches_oracle(kind, H, W, clahe, blur):
     import torch
     import mrgingham_amd
     from oracle import oracle
-    frames = _frames(kind, H, W, 3 if H * W < 1000000 else 1, seed=H + W)   # (the oracle takes 7 s per 2 MP frame)
+    frames = _frames(kind, H, W, 3, seed=H + W)
     det = mrgingham_amd.Detector(0)
     got = det.preprocess(torch.from_numpy(frames).cuda(), clahe=clahe, blur_radius=blur)
     torch.cuda.synchronize()
@@ -52,11 +52,14 @@ def test_preprocess_matches_oracle(kind, H, W, clahe, blur):
 @pytest.mark.parametrize("H,W", [(3072, 4096), (1080, 1920), (1536, 2048), (1440, 2560), (800, 1280), (2160, 4096), (1042, 1936), (274, 48)])
 def test_fused_blend_and_blur_equals_the_two_kernels(H, W):
     """mrgingham-from-image.cc:71-111 as ONE pass (clahe_blur3_kernel) against the blend and the blur as two kernels
-    (option preprocess_fused 0), which the oracle pins at the small sizes above: identical bytes at full sizes, on
-    noise (every blend weight and every rounding case gets used) and on a board; batch of 3 with a strided view."""
+    (option preprocess_fused 0): identical bytes at full sizes, on noise (every blend weight and every rounding case gets
+    used) and on a board; batch of 3 with a strided view.  Both against the oracle too: the two paths share the
+    histogram and LUT kernels."""
+    import concurrent.futures
     import torch
     import mrgingham_amd
     from mrgingham_amd import synth
+    from oracle import oracle
     g = torch.Generator().manual_seed(H * 7 + W)
     noise = (torch.rand((H, W + 16), generator=g) * torch.rand((H, 1), generator=g) * 255).to(torch.uint8)
     frames = torch.stack([noise, torch.roll(noise, 5, 1), torch.zeros_like(noise)]).cuda()
@@ -69,6 +72,14 @@ def test_fused_blend_and_blur_equals_the_two_kernels(H, W):
     torch.cuda.synchronize()
     assert torch.equal(one, two), (H, W, int((one.int() - two.int()).abs().max()), int((one != two).sum()))
     det.close()
+    host = view.cpu().numpy()
+    oracle.lib()
+    with concurrent.futures.ThreadPoolExecutor(max_workers=3) as pool:   # (ctypes releases the GIL)
+        want = list(pool.map(lambda f: oracle.preprocess(f, clahe=True, blur_radius=1), host))
+    one, two = one.cpu().numpy(), two.cpu().numpy()
+    for i in range(3):
+        assert np.array_equal(one[i], want[i]), (H, W, i, int((one[i] != want[i]).sum()))
+        assert np.array_equal(two[i], want[i]), (H, W, i, int((two[i] != want[i]).sum()))
 
 
 def test_preprocess_strided_input_and_no_ops():
