@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X corner-candidate path (contract: see the task brief).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic frames that
 already live in HBM: for each of B = 64 frames of 4096x3072 (10x10 board, the
@@ -15,10 +15,21 @@ fenced by a full device sync + barrier on both sides), so the component search
 of step N overlaps the pixel kernels of step N+1.  Weak scaling: every rank owns its own B
 frames.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set-up, the W warm-up
+steps, the K timed steps, --dump-outputs, and the line itself with:
+
   roofline      dominant kernel = the level-0 ChESS response kernel; achieved =
                 algorithmic bytes per launch (3 B/px: u8 read once + int16
                 written once) / average launch duration measured
                 with hipEvents on the stream each launch ran on.
+  sclk_mhz      the engine clock the timed level-0 launches actually ran at
+                (mrgingham_amd_sclk_mhz: s_memtime / s_memrealtime inside the
+                kernel), and `frac_at_2400mhz` = frac * 2400 / sclk_mhz: the
+                kernels are VALU-bound, so a slow box shows here, not in the code.
+
+`--full` adds the legs beside the timed region, each of which takes runs of its
+own (the --no-* options switch single ones off again):
+
   cpu_baseline  the C oracle (a port of the reference's algorithm) running the
                 same schedule on a bounded sample of the same frames, one frame
                 per host thread at a time like the reference CLI's --jobs: T = 1
@@ -31,10 +42,9 @@ frames.  Rank 0 prints ONE JSON line.
                 detect), preprocess (the reference tool's default CLAHE + blur on
                 the bench frames), c5_mixed_one_rank (1-12 MP stream through the
                 pipelined detector), c1_tool (the built tool on 640x480 files).
-  sclk_mhz      the engine clock the timed level-0 launches actually ran at
-                (mrgingham_amd_sclk_mhz: s_memtime / s_memrealtime inside the
-                kernel), and `frac_at_2400mhz` = frac * 2400 / sclk_mhz: the
-                kernels are VALU-bound, so a slow box shows here, not in the code.
+  chess_pass_alone, sparse_refine, find_boards
+                (N = 1) the plain ChESS pass alone, the same workload with option
+                sparse_refine, and the full detector: see their functions.
 
 `python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment)
 starts the N ranks itself, one process per GPU, on a free local port.
@@ -745,24 +755,29 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c3_4096x3072_chain", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="frames per GPU per step (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the timed region (cpu_baseline, end_to_end, chess_pass_alone, "
+                         "sparse_refine, find_boards, configs); a plain run prints the headline line alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--max-points", type=int, default=256)
     ap.add_argument("--distinct", type=int, default=0,
                     help="render only this many distinct frames and repeat them to fill the batch (used for the "
                          "rocprofv3 --pmc passes, where tracing the ~37k tiny kernels of the frame generator is "
                          "the bottleneck); default: every frame distinct")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the host-fed leg")
     ap.add_argument("--sparse-refine", action="store_true",
                     help="run the TIMED steps with option sparse_refine (not the judged configuration: `config.sparse_refine` "
                          "says so, and `roofline` then describes the kernel that reads the frames, pyramid_fast_kernel)")
     ap.add_argument("--no-find-boards", action="store_true",
-                    help="skip the leg that times the full detector (level search + host grid finder + refinement; N = 1 only)")
+                    help="with --full: skip the leg that times the full detector (level search + host grid finder + "
+                         "refinement; N = 1 only)")
     ap.add_argument("--no-sparse-leg", action="store_true",
-                    help="skip the extra leg that times the same workload with option sparse_refine (N = 1 only)")
+                    help="with --full: skip the extra leg that times the same workload with option sparse_refine (N = 1 only)")
     ap.add_argument("--no-chess-alone", action="store_true",
-                    help="skip the leg that times the plain ChESS pass alone (level 0, no clamp; N = 1 only)")
+                    help="with --full: skip the leg that times the plain ChESS pass alone (level 0, no clamp; N = 1 only)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the `configs` legs (BASELINE configs 1, 2, 5 and the preprocessing chain as short legs; N = 1 only)")
+                    help="with --full: skip the `configs` legs (BASELINE configs 1, 2, 5 and the preprocessing chain as "
+                         "short legs; N = 1 only)")
     ap.add_argument("--scratch-sets", type=int, default=0,
                     help="option scratch_sets of the library (0 = its default: chosen from the batch shape): calls' component "
                          "searches in flight")
@@ -916,8 +931,8 @@ def main():
         dump_outputs(args.dump_outputs, *(parallel.unpack_outputs(gathered[last], batch, P) if collective else outs[last]))
 
     found = int((npts >= gridn * gridn).sum().item())
-    # Everything below is a LEG beside the timed region.  A leg that fails (a box without /dev/shm, a tool that was not
-    # built, ...) reports {"error": ...} in its place: it must never cost the run its JSON line.
+    # Everything below is a LEG beside the timed region, run with --full only.  A leg that fails (a box without /dev/shm,
+    # a tool that was not built, ...) reports {"error": ...} in its place: it must never cost the run its JSON line.
     def leg(fn, *a, **kw):
         try:
             if os.environ.get("MRG_BENCH_FAIL_LEG") == getattr(fn, "__name__", ""):   # (tests: a leg that breaks)
@@ -934,7 +949,7 @@ def main():
     # the host-fed leg on EVERY rank (each rank feeds its own GPU from its own pinned buffer, all at once: what
     # the node's PCIe / memory topology gives when all GPUs are fed together); rank 0 reports min / max over ranks
     e2e = None
-    if not args.no_end_to_end:
+    if args.full and not args.no_end_to_end:
         if collective:
             dist.barrier()
         e2e = end_to_end(det, frames, start_level, P) if collective else leg(end_to_end, det, frames, start_level, P)
@@ -948,17 +963,18 @@ def main():
                        what=e2e["what"] + "; all ranks at once, `value` = sum over ranks")
     fused, merged = det.chain_info()                         # (of the timed steps: before the sparse leg makes its calls)
     scratch_gib = det.scratch_bytes() / 2**30                # (likewise: a context that runs sparse chains keeps a third set)
+    solo = world == 1 and args.full                          # the legs of one rank
     alone = None
-    if world == 1 and not args.no_chess_alone:
+    if solo and not args.no_chess_alone:
         alone = leg(chess_pass_alone_leg, det, frames)
     sparse = None
-    if world == 1 and start_level >= 1 and not args.no_sparse_leg and not args.sparse_refine:
+    if solo and start_level >= 1 and not args.no_sparse_leg and not args.sparse_refine:
         sparse = leg(sparse_leg, det, frames, start_level, P, 100)   # (its own length: not the timed region of the contract)
     fboards = None
-    if world == 1 and not args.no_find_boards:
+    if solo and not args.no_find_boards:
         fboards = leg(find_boards_leg, local_rank, frames, gridn)
     configs = None
-    if world == 1 and not args.no_configs:
+    if solo and not args.no_configs:
         configs = {"preprocess": leg(preprocess_leg, det, frames)}
         torch.cuda.empty_cache()
         configs["c2_level0"] = leg(c2_level0_leg, local_rank)
@@ -966,7 +982,7 @@ def main():
         torch.cuda.empty_cache()
         configs["c1_tool"] = leg(c1_tool_leg, local_rank)
         configs["what"] = ("the other BASELINE configs that fit one GPU, and the reference tool's preprocessing chain, as short "
-                           "legs of the default command; none of them is `value`")
+                           "legs of `--full`; none of them is `value`")
     bindings = None
     if collective and binding is not None:
         objs = [None] * world
@@ -1114,6 +1130,7 @@ def main():
             res["backend"] = "nccl"
         res["scratch_sets"] = args.scratch_sets or "auto"
         res["setup_prime_steps"] = args.prime
+        res["full"] = bool(args.full)                        # whether the legs beside the timed region ran
         res["timed_region_s"] = dt
         res["notes"] = ("steps are queued back to back (streaming pipeline); the first few dozen passes of a process "
                         "run ~5-7 % below the steady state (clock ramp), which is why `setup_prime_steps` untimed "
@@ -1134,7 +1151,7 @@ def main():
             res["configs"] = configs
         if bindings is not None or binding is not None:
             res["cpu_binding"] = bindings if bindings is not None else [binding]
-        if world == 1 and not args.no_cpu_baseline:
+        if solo and not args.no_cpu_baseline:
             nhost = min(batch, 64)
             try:
                 res["cpu_baseline"] = cpu_baseline(frames[:nhost].cpu().numpy(), start_level)

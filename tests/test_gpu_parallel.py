@@ -51,11 +51,23 @@ def test_bench_under_a_launcher_environment():
     assert res["n_gpus"] == 1 and res["ranks_seen"] == 1
 
 
+def test_plain_bench_runs_no_legs():
+    """Without --full (and without any --no-* option) the run is set-up, warm-up, the timed steps and the line: the
+    headline keys and the timed steps' roofline are there, none of the legs beside the timed region ran."""
+    res = _bench("--gpus", "1", "--workload", "c1_640x480_chain", "--steps", "6", "--warmup", "2", "--prime", "3")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in res, key
+    assert res["full"] is False and res["steps"] == 6 and res["value"] > 0
+    assert res["roofline"]["launches_timed"] == 6
+    for key in ("cpu_baseline", "end_to_end", "chess_pass_alone", "sparse_refine", "find_boards", "configs"):
+        assert key not in res, key
+
+
 def test_bench_line_survives_a_leg_that_breaks():
     """The legs beside the timed region (chess_pass_alone, sparse_refine, find_boards, configs.*, end_to_end) run guarded: one that
     throws is reported in its place and the ONE json line still comes out with every key of the contract."""
-    res = _bench("--gpus", "1", "--workload", "c1_640x480_chain", "--steps", "6", "--warmup", "2", "--prime", "3", "--no-cpu-baseline",
-                 "--no-find-boards", "--no-sparse-leg", env_extra={"MRG_BENCH_FAIL_LEG": "c5_mixed_leg"})
+    res = _bench("--gpus", "1", "--full", "--workload", "c1_640x480_chain", "--steps", "6", "--warmup", "2", "--prime", "3",
+                 "--no-cpu-baseline", "--no-find-boards", "--no-sparse-leg", env_extra={"MRG_BENCH_FAIL_LEG": "c5_mixed_leg"})
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline"):
         assert key in res, key
@@ -83,7 +95,7 @@ def test_bench_rehearsal_two_ranks_on_one_gpu():
     global frame index), `ranks_seen`, the gather compared with rank 0's own lists AND with a re-render of rank 1's
     shard, the per-rank host-fed leg aggregated over ranks, one JSON line on stdout -- marked so that it can never be
     read as a scaling measurement."""
-    res = _bench("--gpus", "2", "--rehearse", "--workload", "c1_640x480_chain", "--steps", "6", "--warmup", "2",
+    res = _bench("--gpus", "2", "--rehearse", "--full", "--workload", "c1_640x480_chain", "--steps", "6", "--warmup", "2",
                  "--prime", "3", "--no-cpu-baseline")
     assert res["rehearsal"] is True and res["backend"] == "gloo" and res["physical_gpus"] == 1
     assert res["metric"].startswith("REHEARSAL")
@@ -178,7 +190,7 @@ def test_bench_refuses_more_ranks_than_devices():
 
 
 def test_bench_end_to_end_leg_small():
-    res = _bench("--gpus", "1", "--workload", "c1_640x480_chain", "--steps", "4", "--warmup", "1", "--prime", "2",
+    res = _bench("--gpus", "1", "--full", "--workload", "c1_640x480_chain", "--steps", "4", "--warmup", "1", "--prime", "2",
                  "--no-cpu-baseline")
     e = res["end_to_end"]
     assert e["value"] > 0 and e["h2d_GBs"] > 0 and e["frames_with_points_last_step"] == 64
@@ -241,7 +253,7 @@ def test_bench_c4_shard_of_256_frames_with_the_gather():
     """BASELINE config 4 as a bench workload: 256 frames per GPU (2048 at N = 8), the step ends in the ONE gather
     of the corner lists (a one-rank RCCL group here), the host-fed leg runs on the rank with the collective up,
     and the rank binds itself to its GPU's NUMA node."""
-    res = _bench("--gpus", "1", "--workload", "c4_4096x3072_shard256", "--force-gather", "--bind-numa", "--steps", "3",
+    res = _bench("--gpus", "1", "--full", "--workload", "c4_4096x3072_shard256", "--force-gather", "--bind-numa", "--steps", "3",
                  "--warmup", "1", "--prime", "2", "--no-cpu-baseline")
     assert res["config"]["frames_per_gpu"] == 256 and res["scaling"] == "weak"
     assert res["gather_checked"] is True and res["config"]["frames_with_full_grid_last_step"] == 256

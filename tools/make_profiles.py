@@ -16,9 +16,9 @@ strip = lambda t: re.sub(r"/tmp/[^ ]*?/gpurun_out/", "gpurun_out/", t)
 
 # 1. kernel trace of the bench command
 tb, b = json.loads(rd("trace_bench.json")), json.loads(rd("bench.json"))
-hdr = (f"# rocprofv3 --kernel-trace --stats -- python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-find-boards   (round {RND[1:]}, final kernels; tools/collect_profiles.sh {tag})\n"
+hdr = (f"# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-find-boards   (round {RND[1:]}, final kernels; tools/collect_profiles.sh {tag})\n"
        f"# bench.py under the tracer: {tb['value']:.0f} frames/s, {tb['ms_per_step']:.3f} ms/step, level-0 ChESS launch {tb['roofline']['avg_launch_ms']*1e3:.1f} us by hipEvents (trace below: every launch of the process incl. set-up passes and warm-up; the quartile line is closer to the steady state)\n"
-       f"# bench.py with its defaults (200 steps) without the tracer, same box, same build: {b['value']:.0f} frames/s, {b['ms_per_step']:.3f} ms/step, level-0 ChESS launch {b['roofline']['avg_launch_ms']*1e3:.1f} us -> {b['roofline']['achieved']:.0f} GB/s = {b['roofline']['frac']*100:.1f} % of 8 TB/s\n")
+       f"# bench.py --full with its default steps (200) without the tracer, same box, same build: {b['value']:.0f} frames/s, {b['ms_per_step']:.3f} ms/step, level-0 ChESS launch {b['roofline']['avg_launch_ms']*1e3:.1f} us -> {b['roofline']['achieved']:.0f} GB/s = {b['roofline']['frac']*100:.1f} % of 8 TB/s\n")
 open(os.path.join(P, f"{RND}_bench_kernel_trace.txt"), "w").write(hdr + strip(rd("bench_kernel_trace.txt")))
 open(os.path.join(P, f"{RND}_bench.json"), "w").write(rd("bench.json"))
 
@@ -105,9 +105,9 @@ if os.path.exists(os.path.join(R, "pmc_sqp1.txt")):
         "source": f"profiles/{RND}_bench_sq_counters.txt"}, open(os.path.join(P, "chess_l0_valu.json"), "w"), indent=1)
 for n, out in [("cluttered_kernel_trace.txt", f"{RND}_cluttered_kernel_trace.txt")]:
     if os.path.exists(os.path.join(R, n)):
-        open(os.path.join(P, out), "w").write("# rocprofv3 --kernel-trace --stats -- python bench.py --workload c3_cluttered --steps 40 --warmup 5 --no-cpu-baseline --no-end-to-end\n" + strip(rd(n)))
+        open(os.path.join(P, out), "w").write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --workload c3_cluttered --steps 40 --warmup 5 --no-cpu-baseline --no-end-to-end\n" + strip(rd(n)))
 if os.path.exists(os.path.join(R, "sparse_kernel_trace.txt")):
-    open(os.path.join(P, f"{RND}_sparse_kernel_trace.txt"), "w").write("# rocprofv3 --kernel-trace --stats -- python bench.py --sparse-refine --steps 40 --warmup 5 --no-cpu-baseline --no-end-to-end\n" + strip(rd("sparse_kernel_trace.txt")))
+    open(os.path.join(P, f"{RND}_sparse_kernel_trace.txt"), "w").write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --sparse-refine --steps 40 --warmup 5 --no-cpu-baseline --no-end-to-end\n" + strip(rd("sparse_kernel_trace.txt")))
 for n in ("bench_cluttered.json", "bench_c4.json", "bench_14x14.json", "bench_sparse.json", "bench_sparse_c4.json"):
     if os.path.exists(os.path.join(R, n)) and rd(n).strip():
         open(os.path.join(P, f"{RND}_{n}"), "w").write(rd(n))
@@ -125,8 +125,8 @@ if os.path.exists(os.path.join(R, "chess_alone_kernel_trace.txt")):
 if os.path.exists(os.path.join(R, "c2_kernel_trace.txt")):
     c2 = json.loads(rd("bench_c2.json").strip().splitlines()[-1])
     open(os.path.join(P, f"{RND}_c2_kernel_trace.txt"), "w").write(
-        "# rocprofv3 --kernel-trace --stats -- python bench.py --workload c2_1920x1080_level0 --steps 40 --warmup 5 --no-cpu-baseline --no-find-boards --no-end-to-end\n"
-        f"# BASELINE config 2 (64 x 1920x1080, level-0 detect).  bench.py with its defaults, untraced, same box: {c2['value']:.0f} frames/s, {c2['ms_per_step']:.4f} ms/step, level-0 launch "
+        "# rocprofv3 --kernel-trace --stats -- python bench.py --full --workload c2_1920x1080_level0 --steps 40 --warmup 5 --no-cpu-baseline --no-find-boards --no-end-to-end\n"
+        f"# BASELINE config 2 (64 x 1920x1080, level-0 detect).  bench.py --full with its default steps, untraced, same box: {c2['value']:.0f} frames/s, {c2['ms_per_step']:.4f} ms/step, level-0 launch "
         f"{c2['roofline']['avg_launch_ms']*1e3:.1f} us = {c2['roofline']['frac']*100:.1f} % of 8 TB/s on 3 B/px; chess_pass_alone {c2['chess_pass_alone']['avg_launch_ms']*1e3:.1f} us = {c2['chess_pass_alone']['frac']*100:.1f} %\n"
         + strip(rd("c2_kernel_trace.txt")))
     open(os.path.join(P, f"{RND}_bench_c2.json"), "w").write(rd("bench_c2.json"))
