@@ -36,7 +36,9 @@ extern "C" {
  *   4  round 6: mrgingham_amd_sclk_mhz added; options "chess_seg" / "chess16_seg" are per context (they were process-wide) and
  *      mean balanced segments, option "preprocess_fused"; _gather_rccl, _chain_multi, _sync_multi, _stream_wait_multi restore
  *      the caller's current HIP device; _gather_rccl needs no RCCL header or library at build time and never loads a second RCCL.
- *      Later, additive: mrgingham_amd_preprocess16_batch (16-bit frames on the device; option "preprocess_fused" covers it). */
+ *      Later, additive: mrgingham_amd_preprocess16_batch (16-bit frames on the device; option "preprocess_fused" covers it).
+ *      Later, additive: mrgingham_amd_blobs_batch, _find_circle_grids_batch, _blobs_stats (the blob path over a batch on the
+ *      device); option "blob_chunk_frames". */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -427,6 +429,36 @@ int mrgingham_amd_find_boards_stats(mrgingham_amd_ctx* ctx, double* out, int n, 
  * out6 = calls, found, then the four microsecond sums. */
 int mrgingham_amd_grid_clock(double* out6, int reset);
 
+/* find_blobs_from_image_array (find_blobs.cc:14-46) for every frame of a device-resident batch.
+ * HOST outputs (the last stage of the detector runs on the host): h_xy = nframes blocks of capacity_per_frame
+ * interleaved (x,y)*1000 int pairs in SimpleBlobDetector's output order, h_counts[f] = keypoints of frame f
+ * (may exceed capacity_per_frame: then only the first capacity_per_frame were stored; -1: see ERR_CAPACITY).
+ * Synchronous.  Same integers as find_chessboard_corners_from_image_array_C(.., doblobs = true) per frame.
+ * Frames up to 32767 x 65535; h_xy may be NULL only with capacity 0; nthreads: host threads of the per-contour filters
+ * (<= 0: all cores, at most 32).  The device follows the borders of all 17 thresholds of a CHUNK of frames at once
+ * (one launch of every kernel and three round trips per chunk, whatever its frame count); a batch is worked through in
+ * chunks whose bit planes stay within 1 GiB of context scratch.  A frame with more than 2^27 border starts (pure noise
+ * at tens of megapixels) has no result: its count is -1, the other frames are delivered, and the call returns
+ * MRGINGHAM_AMD_ERR_CAPACITY.  Completes find_boards jobs in flight first; restores the caller's current HIP device. */
+int mrgingham_amd_blobs_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* frames, int32_t* h_xy,
+                              int capacity_per_frame, int32_t* h_counts, int nthreads);
+
+/* find_circle_grid_from_image_array (bridge.cc:104-113) for every frame: blobs, then the host grid finder on the
+ * context's host threads, no refinement.  h_boards / h_found as mrgingham_amd_find_boards_batch; h_found[f] is 0
+ * or -1.  The grid finder sees ALL keypoints of a frame (no capacity). */
+int mrgingham_amd_find_circle_grids_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* frames, int gridn,
+                                          double* h_boards, signed char* h_found, int nthreads);
+
+/* What the two calls above did on this context since the last reset: out[0 .. n) receives up to
+ * MRGINGHAM_AMD_BLOBS_STATS doubles:
+ *   [0] calls   [1] chunks   [2] nodes (border starts) followed   [3] contours downloaded   [4] contour points downloaded
+ *   [5] device milliseconds of the chunks' kernels (hipEvents; counted only while mrgingham_amd_set_kernel_timing is on)
+ *   [6] host milliseconds of the filters and the grouping   [7] frames
+ * (the one-image blob path of the reference symbols counts too, on the calling thread's context).  Returns
+ * MRGINGHAM_AMD_BLOBS_STATS, or an error code. */
+#define MRGINGHAM_AMD_BLOBS_STATS 8
+int mrgingham_amd_blobs_stats(mrgingham_amd_ctx* ctx, double* out, int n, int reset);
+
 /* TEST HOOK: which implementation of the component search handled each frame of the most recent call at
  * `level`: h_paths[f] = 1 out of LDS, 0 the global-memory kernels (hot pixels that cannot be cut into bands
  * of at most 2048, more than 512 multi-pixel components per band / points, or more LIFO demand than the LDS
@@ -489,6 +521,8 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         `value` is measured with).  Same outputs on every frame: a frame the sparse kernels cannot take
  *                         -- a component that leaves the cells around its point, more than 512 points -- is repeated densely
  *                         by the library, on the device, inside the same call (mrgingham_amd_sparse_fallbacks counts them).
+ *   "blob_chunk_frames"   test hook: 0 (default) = mrgingham_amd_blobs_batch / _find_circle_grids_batch cut a batch into chunks
+ *                         by their scratch budget; n > 0 = at most n frames per chunk.  Results never depend on it.
  *   "find_boards_pipeline" 1 (default): mrgingham_amd_find_boards_batch / _submit / _collect as described there; 0: the
  *                         synchronous schedule (one level at a time for the whole batch, dense refinement) -- same results
  *   "chess_seg", "chess16_seg"  rows per workgroup of the ChESS kernels of THIS context (chess_v1* / chess_v16; 0 = cost model,

@@ -39,6 +39,7 @@ EXPORTS = [
     "mrgingham_amd_thread_device", "mrgingham_amd_host_alloc", "mrgingham_amd_host_free", "mrgingham_amd_host_register",
     "mrgingham_amd_host_unregister", "mrgingham_amd_shard_range", "mrgingham_amd_chain_multi", "mrgingham_amd_sync_multi",
     "mrgingham_amd_stream_wait_multi", "mrgingham_amd_kernel_id", "mrgingham_amd_set_wait_policy",
+    "mrgingham_amd_blobs_batch", "mrgingham_amd_find_circle_grids_batch", "mrgingham_amd_blobs_stats",
 ]
 
 
@@ -110,6 +111,10 @@ def lib():
     L.mrgingham_amd_find_boards_batch.argtypes = [c_vp, FP, c_int, c_int, c_vp, c_vp, c_int]
     L.mrgingham_amd_find_boards_submit.argtypes = [c_vp, FP, c_int, c_int, c_vp, c_vp, c_int]
     L.mrgingham_amd_find_boards_collect.argtypes = [c_vp, c_int]
+    if hasattr(L, "mrgingham_amd_blobs_batch"):    # (an older A/B build behind MRGINGHAM_AMD_LIB has not got them:
+        L.mrgingham_amd_blobs_batch.argtypes = [c_vp, FP, c_vp, c_int, c_vp, c_int]   # calling one fails in ctypes)
+        L.mrgingham_amd_find_circle_grids_batch.argtypes = [c_vp, FP, c_int, c_vp, c_vp, c_int]
+        L.mrgingham_amd_blobs_stats.argtypes = [c_vp, c_vp, c_int, c_int]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]
     L.mrgingham_amd_host_alloc.argtypes = [ctypes.c_size_t]

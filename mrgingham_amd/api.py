@@ -339,6 +339,7 @@ class Detector:
         if not self.ctx:
             raise RuntimeError("mrgingham_amd_create failed")
         self._options = {}
+        self._blobs_cap = 256    # keypoints per frame Detector.blobs makes room for (grows to the largest count seen)
         self._fb_live = {}       # find_boards jobs in flight: ticket -> (boards, found, frames), see find_boards_submit
 
     def close(self):
@@ -584,14 +585,56 @@ class Detector:
             issue()
         return nref
 
-    def find_boards(self, frames, gridn=10, image_pyramid_level=-1, nthreads=0):
-        """Full detector over a batch: -> (boards float64 [B, gridn*gridn, 2] (numpy, host),
-        found_level int8 [B], -1 where no board was found).  Synchronous."""
+    def blobs(self, frames, nthreads=0):
+        """The blob detector (find_blobs_from_image_array, find_blobs.cc:14-46: what find_points(blobs=True) gives one
+        host image) over a batch on the device: -> a list of B int32 numpy arrays [n_f, 2], (x, y) * 1000 in
+        SimpleBlobDetector's output order.  Synchronous; the last stage of the detector runs on `nthreads` host threads
+        (0: all cores, at most 32)."""
         t = self.torch
+        if not (isinstance(frames, t.Tensor) and frames.is_cuda and frames.dtype == t.uint8 and frames.dim() == 3
+                and (frames.shape[2] <= 1 or frames.stride(2) == 1)):
+            raise ValueError("blobs: a [B,H,W] uint8 tensor on the device with unit column stride")
+        fr, B, H, W = self._frames(frames)
+        if B == 0:
+            return []
+        t.cuda.current_stream(frames.device).synchronize()
+        counts = np.zeros((B,), dtype=np.int32)
+        cap = self._blobs_cap
+        while True:
+            xy = np.empty((B, cap, 2), dtype=np.int32)
+            rc = self.L.mrgingham_amd_blobs_batch(self.ctx, ctypes.byref(fr), xy.ctypes.data, cap, counts.ctypes.data,
+                                                  int(nthreads))
+            self._check(rc)
+            if counts.max() <= cap:
+                return [xy[f, :counts[f]].copy() for f in range(B)]
+            cap = self._blobs_cap = int(counts.max())   # (more keypoints than guessed: again, sized to the largest; remembered)
+
+    BLOBS_STATS = ("calls", "chunks", "nodes", "contours", "points", "device_ms", "host_ms", "frames")
+
+    def blobs_stats(self, reset=True):
+        """mrgingham_amd_blobs_stats as a dict (totals since the last reset; device_ms only while kernel timing is on)."""
+        out = np.zeros(len(self.BLOBS_STATS), dtype=np.float64)
+        n = self.L.mrgingham_amd_blobs_stats(self.ctx, out.ctypes.data, len(out), int(bool(reset)))
+        if n < 0:
+            self._check(n)
+        return dict(zip(self.BLOBS_STATS, out.tolist()))
+
+    def find_boards(self, frames, gridn=10, image_pyramid_level=-1, nthreads=0, blobs=False):
+        """Full detector over a batch: -> (boards float64 [B, gridn*gridn, 2] (numpy, host),
+        found_level int8 [B], -1 where no board was found).  Synchronous.  blobs=True (level 0 only): a grid of dark
+        circles instead of a chessboard -- the blob detector, then the grid finder, no refinement
+        (find_circle_grid_from_image_array, bridge.cc:104-113); found is 0 or -1."""
+        t = self.torch
+        if blobs and image_pyramid_level != 0:
+            raise RuntimeError("blob detector requires that image_pyramid_level == 0")
         fr, B, H, W = self._frames(frames)
         boards = np.full((B, gridn * gridn, 2), np.nan, dtype=np.float64)
         found = np.full((B,), -1, dtype=np.int8)
         t.cuda.current_stream(frames.device).synchronize()
+        if blobs:
+            self._check(self.L.mrgingham_amd_find_circle_grids_batch(self.ctx, ctypes.byref(fr), int(gridn),
+                                                                     boards.ctypes.data, found.ctypes.data, int(nthreads)))
+            return boards, found
         self._check(self.L.mrgingham_amd_find_boards_batch(self.ctx, ctypes.byref(fr), int(gridn),
                                                            int(image_pyramid_level), boards.ctypes.data,
                                                            found.ctypes.data, int(nthreads)))

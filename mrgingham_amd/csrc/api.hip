@@ -680,6 +680,8 @@ void mrgingham_amd_destroy(mrgingham_amd_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_cc_done)
         if (e) hipEventDestroy(e);
     if (ctx->ev_ext) hipEventDestroy(ctx->ev_ext);
+    for (hipEvent_t e : ctx->blob_ev)
+        if (e) hipEventDestroy(e);
     if (ctx->io_pin) hipHostFree(ctx->io_pin);
     if (ctx->io_res_pin) hipHostFree(ctx->io_res_pin);
     for (int k = 0; k < kMaxSets; ++k)
@@ -840,6 +842,11 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
     }
     if (!strcmp(name, "fuse_pyramid")) { ctx->fuse_pyramid = value != 0; return 0; }
     if (!strcmp(name, "find_boards_pipeline")) { ctx->fb_pipeline = value != 0; return 0; }
+    if (!strcmp(name, "blob_chunk_frames")) {
+        if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "blob_chunk_frames: 0 (by the scratch budget) or a frame count");
+        ctx->blob_chunk_frames = value;
+        return 0;
+    }
     if (!strcmp(name, "sparse_refine")) {
         if (value < 0 || value > 2) return MRGINGHAM_AMD_ERR_ARG;
         ctx->sparse_refine = value;

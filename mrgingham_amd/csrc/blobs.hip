@@ -11,10 +11,17 @@
 // border start candidates of every plane and the border following itself (in parallel: arcs between candidates,
 // then pointer jumping over the cycles of arcs, see below), with the contour-area sum of contourMoments (Green's
 // theorem: exact in integers, order-independent) for the area filter.  Borders that pass it get their points
-// written, every arc its own stretch.  The host finishes the few survivors in double precision (the other
-// moments, inertia, convex hull, colour, median radius, grouping): microseconds, like the grid finder that
+// written, every arc its own stretch, with the other five moment sums (integers too) and the pixel at the rounded
+// centre that the colour filter asks for.  The host finishes the few survivors in double precision (inertia, convex
+// hull, colour, median radius, grouping) and needs no copy of the pixels: microseconds, like the grid finder that
 // consumes the result.
+//
+// ONE pipeline for one frame and for a batch: a chunk of frames is `frames x 17` bit planes in one node space (plane =
+// frame * 17 + threshold), every kernel is launched once per chunk, and the one-frame entry (blob_detect) is the chunk
+// of one frame.  See blob_detect_batch.
 #include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -23,8 +30,7 @@
 #include <thread>
 #include <vector>
 
-#include "common.h"
-#include "kernels.h"
+#include "ctx.h"
 
 namespace mrg {
 
@@ -34,9 +40,23 @@ constexpr int kNumThresh = 17;            // 50, 60, .. 210 (minThreshold 50, ma
 constexpr int kThresh0 = 50, kThreshStep = 10;
 
 struct BitPlanes {
-    const uint32_t* bits;  // [kNumThresh][h][wpr]
+    const uint32_t* bits;  // [planes][h][wpr], plane = frame * kNumThresh + threshold
     int w, h, wpr;
 };
+
+// The device words of one chunk of `nf` frames (P = nf * kNumThresh planes); the host reads all of them in one copy.
+struct BlobCounters {
+    int* err;         // [nf]  != 0: the frame has a border arc longer than kMaxArc
+    int* plane_cnt;   // [P]   nodes of the plane
+    int* plane_base;  // [P]   first node of the plane
+    int* rec_cnt;     // [nf]  contours of the frame that pass the area filter ...
+    int* pts_cnt;     // [nf]  ... and their points
+    int* rec_base;    // [nf]  first record / first point of the frame in the chunk's arrays
+    int* pts_base;    // [nf]
+    int* rec_cur;     // [nf]  write cursors within the frame's stretch
+    int* pts_cur;     // [nf]
+};
+constexpr int blob_counter_words(int nf) { return nf * (7 + 2 * kNumThresh); }
 
 // direction codes of the border follower: 0 = +x, then counter-clockwise on the screen (y down)
 __device__ __constant__ int kDX[8] = {1, 1, 0, -1, -1, -1, 0, 1};
@@ -55,11 +75,13 @@ __device__ __forceinline__ int first_ccw(uint32_t m, int s) {
     return (s + 1 + (__ffs((int)r) - 1)) & 7;
 }
 
-// one thread = 32 pixels of a row -> one word of each of the 17 planes
-__global__ __launch_bounds__(256) void blob_bitplanes_kernel(const uint8_t* img, int stride, int w, int h, int wpr,
-                                                             uint32_t* bits) {
-    const int wx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+// one thread = 32 pixels of a row of frame blockIdx.z -> one word of each of the frame's 17 planes
+__global__ __launch_bounds__(256) void blob_bitplanes_kernel(const uint8_t* img, long long frame_pitch, int stride, int w, int h,
+                                                             int wpr, uint32_t* bits) {
+    const int wx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
     if (wx >= wpr) return;
+    img += f * frame_pitch;
+    bits += (long long)f * kNumThresh * h * wpr;
     uint32_t word[kNumThresh];
 #pragma unroll
     for (int t = 0; t < kNumThresh; ++t) word[t] = 0;
@@ -151,16 +173,18 @@ struct BlobNodes {         // per node (= candidate = arc), N of them; planes on
     uint32_t* next;        // the node whose start state the arc ends in (itself: a border of one arc; a dead node: itself)
     unsigned long long* a00;  // the arc's share of the contourMoments sum a00 (wrap-around)
     uint32_t* n;           // steps = points of the arc; 0 = dead node
-    uint32_t* jmp;         // pointer jumping (leader rounds)
+    uint32_t* jmp;         // pointer jumping (leader rounds); afterwards, at the owner: the contour's record
     uint32_t* leader;      // the smallest node of the cycle
     uint32_t* ptr[2];      // list ranking (double-buffered): successor 2^r arcs on, kNoNode at the end of the list
     unsigned long long* sa[2];  // ... a00 summed from this arc to the end of the list
     uint32_t* sn[2];       // ... points from this arc to the end of the list
     int32_t* off;          // per node: first point of its contour in the point arena (at the owner; -1: contour rejected)
+    uint16_t* plane;       // the node's plane within the chunk
 };
-constexpr size_t kBlobNodeBytes = 4 + 4 + 8 + 4 + 4 + 4 + 8 + 16 + 8 + 4;  // 64
+constexpr size_t kBlobNodeBytes = 4 + 4 + 8 + 4 + 4 + 4 + 8 + 16 + 8 + 4 + 2;  // 66
+constexpr int kMaxChunkFrames = 65535 / kNumThresh;  // (plane ids are 16 bits, and a grid dimension)
 
-// pass 1: candidates per word (exclusive prefix within the row) and per row.  One workgroup per (row, plane).
+// pass 1: candidates per word (exclusive prefix within the row) and per row.  One workgroup per (row, plane of the chunk).
 __global__ __launch_bounds__(256) void blob_count_kernel(BitPlanes bp, uint32_t* wordpre, uint32_t* rowcnt) {
     __shared__ uint32_t part[256];
     __shared__ uint32_t carry;
@@ -197,9 +221,8 @@ __global__ __launch_bounds__(256) void blob_count_kernel(BitPlanes bp, uint32_t*
 }
 
 // pass 2: first node of every row WITHIN its plane and the nodes per plane (one workgroup per plane), then the first
-// node of every plane and the total (blob_bases_kernel).  counters: [3] = N, [4 + t] = nodes of plane t,
-// [4 + kNumThresh + t] = first node of plane t.
-__global__ __launch_bounds__(256) void blob_rowscan_kernel(int h, const uint32_t* rowcnt, uint32_t* rowoff, int* counters) {
+// node of every plane of the chunk (blob_bases_kernel; the host adds up the total).
+__global__ __launch_bounds__(256) void blob_rowscan_kernel(int h, const uint32_t* rowcnt, uint32_t* rowoff, int* plane_cnt) {
     __shared__ uint32_t part[256];
     __shared__ uint32_t carry;
     const int tid = threadIdx.x, t = blockIdx.x;
@@ -221,16 +244,34 @@ __global__ __launch_bounds__(256) void blob_rowscan_kernel(int h, const uint32_t
         if (tid == 255) carry += part[255];
         __syncthreads();
     }
-    if (tid == 0) counters[4 + t] = (int)carry;
+    if (tid == 0) plane_cnt[t] = (int)carry;
 }
-__global__ void blob_bases_kernel(int* counters) {
-    if (threadIdx.x != 0) return;
-    uint32_t base = 0;
-    for (int t = 0; t < kNumThresh; ++t) {
-        counters[4 + kNumThresh + t] = (int)base;
-        base += (uint32_t)counters[4 + t];
+// exclusive prefix sums of n counts (wrap-around: the host checks the total before anything is indexed with them);
+// workgroup b takes the pair (cnt_b, base_b): the planes' nodes, or the frames' records and points
+__global__ __launch_bounds__(256) void blob_bases_kernel(const int* cnt0, int* base0, const int* cnt1, int* base1, int n) {
+    __shared__ uint32_t part[256];
+    __shared__ uint32_t carry;
+    const int tid = threadIdx.x;
+    const int* cnt = blockIdx.x ? cnt1 : cnt0;
+    int* base = blockIdx.x ? base1 : base0;
+    if (tid == 0) carry = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        const uint32_t c = i < n ? (uint32_t)cnt[i] : 0u;
+        part[tid] = c;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const uint32_t v = tid >= d ? part[tid - d] : 0u;
+            __syncthreads();
+            part[tid] += v;
+            __syncthreads();
+        }
+        if (i < n) base[i] = (int)(carry + part[tid] - c);
+        __syncthreads();
+        if (tid == 255) carry += part[255];
+        __syncthreads();
     }
-    counters[3] = (int)base;
 }
 
 // node of candidate (x, type) of row y of plane t; `r1` = the row as 34 bits around word x >> 5 (row34)
@@ -244,9 +285,9 @@ __device__ __forceinline__ uint32_t node_of(const BitPlanes& bp, int t, int x, i
            __popc(hole & below) + (type ? (outer >> b) & 1u : 0u);
 }
 
-// pass 3: the keys of the nodes, in place (thread per word)
+// pass 3: the keys and the plane ids of the nodes, in place (thread per word)
 __global__ __launch_bounds__(256) void blob_keys_kernel(BitPlanes bp, const uint32_t* wordpre, const uint32_t* rowoff, uint32_t* key,
-                                                        const int* counters) {
+                                                        uint16_t* plane, const int* plane_base) {
     const int wx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, t = blockIdx.z;
     if (wx >= bp.wpr) return;
     const uint32_t* row = bp.bits + ((long long)t * bp.h + y) * bp.wpr;
@@ -254,24 +295,25 @@ __global__ __launch_bounds__(256) void blob_keys_kernel(BitPlanes bp, const uint
     if (cur == 0) return;
     uint32_t outer, hole;
     word_candidates(cur, wx > 0 ? row[wx - 1] >> 31 : 0u, wx + 1 < bp.wpr ? row[wx + 1] & 1u : 0u, wx, bp.w, outer, hole);
-    uint32_t k = (uint32_t)counters[4 + kNumThresh + t] + rowoff[t * bp.h + y] + wordpre[((long long)t * bp.h + y) * bp.wpr + wx];
+    uint32_t k = (uint32_t)plane_base[t] + rowoff[t * bp.h + y] + wordpre[((long long)t * bp.h + y) * bp.wpr + wx];
     uint32_t both = outer | hole;
     while (both) {
         const int i = __ffs(both) - 1;
         both &= both - 1;
         const uint32_t xy = ((uint32_t)y << 16) | ((uint32_t)(wx * 32 + i) << 1);
-        if ((outer >> i) & 1u) key[k++] = xy;
-        if ((hole >> i) & 1u) key[k++] = xy | 1u;
+        if ((outer >> i) & 1u) { plane[k] = (uint16_t)t; key[k++] = xy; }
+        if ((hole >> i) & 1u) { plane[k] = (uint16_t)t; key[k++] = xy | 1u; }
     }
 }
 
 // The arc that starts at candidate `key` of plane t.  WRITE = false: -> (next node, steps, a00 share); a dead node
 // (a single pixel, or the hole-type twin of an outer-type candidate in the same state) has 0 steps and is its own
-// successor.  WRITE = true: stores the arc's points ((y << 16) | x) to pts[0 .. steps).
+// successor.  WRITE = true: stores the arc's points ((y << 16) | x) to pts[0 .. steps) and adds the arc's share of the
+// other five contourMoments sums (a10, a01, a20, a11, a02: wrap-around integers like a00) to sums[0 .. 5).
 template <bool WRITE>
 __device__ __forceinline__ void blob_arc(const BitPlanes& bp, int t, uint32_t key, uint32_t self, const uint32_t* wordpre,
                                          const uint32_t* rowoff, uint32_t plane_base, uint32_t& next, uint32_t& steps,
-                                         unsigned long long& a00, uint32_t* pts, int* err) {
+                                         unsigned long long& a00, uint32_t* pts, unsigned long long* sums, int* err) {
     const int x0 = (int)((key >> 1) & 0x7fffu), y0 = (int)(key >> 16), is_hole = (int)(key & 1u);
     next = self;
     steps = 0;
@@ -309,7 +351,16 @@ __device__ __forceinline__ void blob_arc(const BitPlanes& bp, int t, uint32_t ke
         }
         const int x4 = x3 + k * kDX[s], y4 = y3 + kDY[s];
         if (WRITE) {
-            for (int j = 0; j < k; ++j) pts[n + j] = ((uint32_t)y3 << 16) | (uint32_t)(x3 + j * kDX[s]);
+            for (int j = 0; j < k; ++j) {  // the pair (point -> next point) of every step, as moments.cpp's contourMoments adds it
+                const long long xa = x3 + j * kDX[s], ya = y3, xb = xa + kDX[s], yb = y4;  // (a run is horizontal: y4 == y3)
+                pts[n + j] = ((uint32_t)y3 << 16) | (uint32_t)xa;
+                const long long dxy = xa * yb - xb * ya, xii = xa + xb, yii = ya + yb;
+                sums[0] += (unsigned long long)(dxy * xii);
+                sums[1] += (unsigned long long)(dxy * yii);
+                sums[2] += (unsigned long long)(dxy * (xa * xii + xb * xb));
+                sums[3] += (unsigned long long)(dxy * (xa * (yii + ya) + xb * (yii + yb)));
+                sums[4] += (unsigned long long)(dxy * (ya * yii + yb * yb));
+            }
         } else {
             // contourMoments, the pairs (point -> next point) of the k steps: x * y' - x' * y each; in a horizontal run - y or + y
             a00 += k == 1 ? (unsigned long long)((long long)x3 * y4 - (long long)x4 * y3)
@@ -336,23 +387,16 @@ __device__ __forceinline__ void blob_arc(const BitPlanes& bp, int t, uint32_t ke
     steps = n;
 }
 
-__device__ __forceinline__ int plane_of(uint32_t node, const int* counters) {
-    int t = 0;
-#pragma unroll
-    for (int u = 1; u < kNumThresh; ++u) t += node >= (uint32_t)counters[4 + kNumThresh + u];
-    return t;
-}
-
-// pass 4: every arc
+// pass 4: every arc (N = the nodes of the chunk, as the host added them up)
 __global__ __launch_bounds__(256) void blob_arcs_kernel(BitPlanes bp, const uint32_t* wordpre, const uint32_t* rowoff, BlobNodes nd,
-                                                        int* counters) {
-    const uint32_t N = (uint32_t)counters[3];
+                                                        uint32_t N, BlobCounters cn) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= N) return;
     uint32_t next, steps;
     unsigned long long a00;
-    const int t = plane_of(i, counters);
-    blob_arc<false>(bp, t, nd.key[i], i, wordpre, rowoff, (uint32_t)counters[4 + kNumThresh + t], next, steps, a00, nullptr, counters + 2);
+    const int t = nd.plane[i];
+    blob_arc<false>(bp, t, nd.key[i], i, wordpre, rowoff, (uint32_t)cn.plane_base[t], next, steps, a00, nullptr, nullptr,
+                    cn.err + t / kNumThresh);
     nd.next[i] = next;
     nd.n[i] = steps;
     nd.a00[i] = a00;
@@ -364,8 +408,7 @@ __global__ __launch_bounds__(256) void blob_arcs_kernel(BitPlanes bp, const uint
 // pointer arrays, which are free until pass 6): a round must see a node's minimum and its pointer from the SAME round,
 // or the minimum it takes over may not cover the stretch the pointer skips.
 __global__ __launch_bounds__(256) void blob_leader_round_kernel(const uint32_t* jmp, const uint32_t* lead, uint32_t* jmp_out,
-                                                                uint32_t* lead_out, const int* counters) {
-    const uint32_t N = (uint32_t)counters[3];
+                                                                uint32_t* lead_out, uint32_t N) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= N) return;
     const uint32_t j = jmp[i];
@@ -374,8 +417,7 @@ __global__ __launch_bounds__(256) void blob_leader_round_kernel(const uint32_t* 
 }
 
 // pass 6: the cycle cut open at its owner, then R rounds of list ranking (suffix sums towards the end of the list)
-__global__ __launch_bounds__(256) void blob_rank_init_kernel(BlobNodes nd, const int* counters) {
-    const uint32_t N = (uint32_t)counters[3];
+__global__ __launch_bounds__(256) void blob_rank_init_kernel(BlobNodes nd, uint32_t N) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= N) return;
     const uint32_t nx = nd.next[i];
@@ -384,8 +426,7 @@ __global__ __launch_bounds__(256) void blob_rank_init_kernel(BlobNodes nd, const
     nd.sn[0][i] = nd.n[i];
     nd.off[i] = -1;
 }
-__global__ __launch_bounds__(256) void blob_rank_round_kernel(BlobNodes nd, int from, const int* counters) {
-    const uint32_t N = (uint32_t)counters[3];
+__global__ __launch_bounds__(256) void blob_rank_round_kernel(BlobNodes nd, int from, uint32_t N) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= N) return;
     const int to = from ^ 1;
@@ -404,55 +445,88 @@ __global__ __launch_bounds__(256) void blob_rank_round_kernel(BlobNodes nd, int 
 
 struct BlobContour {      // one border that passed the area filter
     uint32_t key;         // its start (raster position and type): the order of discovery
-    int32_t t;            // threshold index
+    int32_t t;            // on the device: the plane within the chunk; on the host (blob_chunk_host): the threshold index
     int32_t n;            // points
-    uint32_t points_off;  // first point in the arena
-    long long a00, a10, a01, a20, a11, a02;  // contourMoments sums (a00 from the device, the rest from the points on the host)
+    uint32_t points_off;  // first point in the chunk's arena
+    long long a00, a10, a01, a20, a11, a02;  // contourMoments sums: a00 from the list ranking, the rest from the re-walk of the arcs
+    int32_t pix;          // the frame's pixel at the rounded centre (filterByColor); -1: no centre, or one outside the frame
+    int32_t pad;
 };
 
 // pass 7: the owners: filterByArea on m00 = |a00| / 2 (minArea 20 <= m00 < maxArea 80000, exact in integers).
-// WRITE = false: how many contours pass and how many points they have (counters [0], [1]) -- the host sizes the
-// record and point arrays from that; WRITE = true: a record and a place in the point arena for each of them.
+// WRITE = false: how many contours of every frame pass and how many points they have -- the host sizes the record
+// and point arrays from that, blob_bases_kernel gives every frame its stretch of both; WRITE = true: a record and a
+// place in the point arena for each of them.
 template <bool WRITE>
-__global__ __launch_bounds__(256) void blob_records_kernel(BlobNodes nd, int rk, BlobContour* recs, int* counters) {
-    const uint32_t N = (uint32_t)counters[3];
+__global__ __launch_bounds__(256) void blob_records_kernel(BlobNodes nd, int rk, BlobContour* recs, uint32_t N, BlobCounters cn) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= N || nd.leader[i] != i || nd.n[i] == 0) return;
     const long long a00 = (long long)nd.sa[rk][i];
     const long long a = a00 < 0 ? -a00 : a00;
     if (a < 2 * 20 || a >= 2 * 80000) return;
     const int n = (int)nd.sn[rk][i];
+    const int plane = nd.plane[i], f = plane / kNumThresh;
     if (!WRITE) {
-        atomicAdd(counters + 0, 1);
-        atomicAdd(counters + 1, n);
+        atomicAdd(cn.rec_cnt + f, 1);
+        atomicAdd(cn.pts_cnt + f, n);
         return;
     }
     BlobContour c;
     c.key = nd.key[i];
-    c.t = plane_of(i, counters);
+    c.t = plane;
     c.n = n;
     c.a00 = a00;
     c.a10 = c.a01 = c.a20 = c.a11 = c.a02 = 0;
-    const int r = atomicAdd(counters + 5 + 2 * kNumThresh, 1);
-    c.points_off = (unsigned)atomicAdd(counters + 6 + 2 * kNumThresh, n);
+    c.pix = -1;
+    c.pad = 0;
+    const uint32_t r = (uint32_t)cn.rec_base[f] + (uint32_t)atomicAdd(cn.rec_cur + f, 1);
+    c.points_off = (uint32_t)cn.pts_base[f] + (uint32_t)atomicAdd(cn.pts_cur + f, n);
     nd.off[i] = (int)c.points_off;
+    nd.jmp[i] = r;
     recs[r] = c;
 }
 
 // pass 8: the points of the contours that passed, every arc its own stretch: the arc's offset in its contour is
-// what precedes it in the list from the owner = total - (points from this arc to the end)
+// what precedes it in the list from the owner = total - (points from this arc to the end).  The re-walk also yields the
+// arc's share of the five moment sums the list ranking does not carry: exact and order-independent, so every arc adds
+// its own to the contour's record.
 __global__ __launch_bounds__(256) void blob_points_kernel(BitPlanes bp, const uint32_t* wordpre, const uint32_t* rowoff, BlobNodes nd,
-                                                          int rk, uint32_t* pts, int* counters) {
-    const uint32_t N = (uint32_t)counters[3];
+                                                          int rk, uint32_t* pts, BlobContour* recs, uint32_t N) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= N || nd.n[i] == 0) return;
     const uint32_t L = nd.leader[i];
+    if (L == kNoNode) return;  // (every border has an outer-type start, so this cannot be: a guard for the index below)
     const int off = nd.off[L];
     if (off < 0) return;
     const uint32_t total = nd.sn[rk][L], at = total - nd.sn[rk][i];
     uint32_t next, steps;
-    unsigned long long a00;
-    blob_arc<true>(bp, plane_of(i, counters), nd.key[i], i, wordpre, rowoff, 0u, next, steps, a00, pts + off + at, nullptr);
+    unsigned long long a00, sums[5] = {0, 0, 0, 0, 0};
+    blob_arc<true>(bp, nd.plane[i], nd.key[i], i, wordpre, rowoff, 0u, next, steps, a00, pts + (uint32_t)off + at, sums, nullptr);
+    unsigned long long* dst = (unsigned long long*)&recs[nd.jmp[L]].a10;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) atomicAdd(dst + k, sums[k]);
+}
+
+// pass 9: filterByColor needs the frame's pixel at the rounded centre of every contour: the centre with the SAME IEEE
+// double operations, in the same order, as contour_to_center below (the library is built with -ffp-contract=off for
+// host and device; only *, / and round-to-nearest-even are used), then one pixel fetched.  Everything else about the
+// contour stays on the host.
+__global__ __launch_bounds__(256) void blob_colour_kernel(BlobContour* recs, int nrecs, const uint8_t* img, long long frame_pitch,
+                                                          int stride, int w, int h) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nrecs) return;
+    const BlobContour c = recs[r];
+    const double a00 = (double)c.a00, a10 = (double)c.a10, a01 = (double)c.a01;
+    const double sg = a00 > 0 ? 1.0 : -1.0;
+    const double m00 = a00 * (sg * 0.5), m10 = a10 * (sg * 0.16666666666666666666666666666667);
+    const double m01 = a01 * (sg * 0.16666666666666666666666666666667);
+    int pix = -1;
+    if (m00 != 0.0) {
+        const double x = rint(m10 / m00), y = rint(m01 / m00);  // cvRound
+        if (x >= 0. && x < (double)w && y >= 0. && y < (double)h)
+            pix = img[(c.t / kNumThresh) * frame_pitch + (long long)(int)y * stride + (int)x];
+    }
+    recs[r].pix = pix;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -494,8 +568,7 @@ double hull_area(std::vector<IPt> s) {  // area of the convex hull of the point 
 }
 
 // blobdetector.cpp findBlobs for one contour that passed the area filter
-bool contour_to_center(const BlobContour& c, const uint32_t* pts, const uint8_t* img, int w, int h, int stride,
-                       Center* out) {
+bool contour_to_center(const BlobContour& c, const uint32_t* pts, Center* out) {
     // contourMoments: scale the sums, then completeMomentState
     const double a00 = (double)c.a00, a10 = (double)c.a10, a01 = (double)c.a01;
     const double a20 = (double)c.a20, a11 = (double)c.a11, a02 = (double)c.a02;
@@ -532,10 +605,9 @@ bool contour_to_center(const BlobContour& c, const uint32_t* pts, const uint8_t*
     out->confidence = ratio * ratio;
     {  // filterByColor, blobColor 0: the binarised pixel at the rounded centre must be dark.  (blobdetector.cpp checks it
        // after the convexity; the filters are independent conditions, and this one spares the contours of the WHITE
-       // regions -- half of all -- their convex hull)
-        const int ix = (int)std::nearbyint(out->x), iy = (int)std::nearbyint(out->y);  // cvRound
-        if (ix < 0 || ix >= w || iy < 0 || iy >= h) return false;
-        if (img[(size_t)iy * stride + ix] > kThresh0 + kThreshStep * c.t) return false;
+       // regions -- half of all -- their convex hull).  The pixel at (cvRound(x), cvRound(y)) comes from the device:
+       // blob_colour_kernel
+        if (c.pix < 0 || c.pix > kThresh0 + kThreshStep * c.t) return false;
     }
     std::vector<IPt> p((size_t)c.n);
     for (int i = 0; i < c.n; ++i) p[i] = IPt{(int)(pts[i] & 0xffffu), (int)(pts[i] >> 16)};
@@ -559,183 +631,19 @@ bool contour_to_center(const BlobContour& c, const uint32_t* pts, const uint8_t*
     return true;
 }
 
-// contourMoments' integer sums of a closed contour from its points, wrap-around like the arithmetic of the device
-// (the exact results fit; moments.cpp accumulates the same terms in double)
-void contour_sums(BlobContour& c, const uint32_t* pts) {
-    unsigned long long a00 = 0, a10 = 0, a01 = 0, a20 = 0, a11 = 0, a02 = 0;
-    for (int i = 0; i < c.n; ++i) {
-        const uint32_t p = pts[i], q = pts[i + 1 < c.n ? i + 1 : 0];
-        const long long xa = (long long)(p & 0xffffu), ya = (long long)(p >> 16), xb = (long long)(q & 0xffffu), yb = (long long)(q >> 16);
-        const long long dxy = xa * yb - xb * ya, xii = xa + xb, yii = ya + yb;
-        a00 += (unsigned long long)dxy;
-        a10 += (unsigned long long)(dxy * xii);
-        a01 += (unsigned long long)(dxy * yii);
-        a20 += (unsigned long long)(dxy * (xa * xii + xb * xb));
-        a11 += (unsigned long long)(dxy * (xa * (yii + ya) + xb * (yii + yb)));
-        a02 += (unsigned long long)(dxy * (ya * yii + yb * yb));
-    }
-    c.a00 = (long long)a00; c.a10 = (long long)a10; c.a01 = (long long)a01;
-    c.a20 = (long long)a20; c.a11 = (long long)a11; c.a02 = (long long)a02;
-}
-
 }  // namespace
 
-size_t blob_scratch_bytes(int w, int h, BlobScratchLayout* lay) {
-    BlobScratchLayout L;
-    L.wpr = (w + 31) / 32;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    L.o_counters = take(64 * sizeof(int));
-    L.o_bits = take((size_t)kNumThresh * h * L.wpr * 4);
-    L.o_wordpre = take((size_t)kNumThresh * h * L.wpr * 4);
-    L.o_rowcnt = take((size_t)kNumThresh * h * 4);
-    L.o_rowoff = take((size_t)kNumThresh * h * 4);
-    if (lay) *lay = L;
-    return off;
-}
 
-// d_img: the frame on the device; h_img: the same pixels on the host (colour filter).  `node_scratch(bytes)` and
-// `out_scratch(bytes)` return device memory of at least that size for the per-candidate arrays and for the records and
-// points of the contours that pass the area filter (how many there are is only known after they have been counted:
-// no capacity to run out of).  Appends the keypoints as (x, y) * 1000 ints in SimpleBlobDetector's output order.
-// false on a device error or when the frame has more borders than the scratch holds (err says which).
-bool blob_detect(const uint8_t* d_img, int d_stride, const uint8_t* h_img, int h_stride, int w, int h, void* scratch,
-                 const std::function<void*(size_t)>& node_scratch, const std::function<void*(size_t)>& out_scratch, hipStream_t s,
-                 std::vector<int32_t>& xy_out, std::string& err) {
-    if (w <= 0 || h <= 0) return true;
-    if (w > 32767 || h > 65535) { err = "blob detector: frames up to 32767 x 65535"; return false; }
-    BlobScratchLayout L;
-    blob_scratch_bytes(w, h, &L);
-    char* base = (char*)scratch;
-    int* counters = (int*)(base + L.o_counters);  // [0] records, [1] points, [2] error, [3] nodes, [4 + t] of plane t, [21 + t] first of plane t, [39], [40] write cursors
-    uint32_t* bits = (uint32_t*)(base + L.o_bits);
-    uint32_t* wordpre = (uint32_t*)(base + L.o_wordpre);
-    uint32_t* rowcnt = (uint32_t*)(base + L.o_rowcnt);
-    uint32_t* rowoff = (uint32_t*)(base + L.o_rowoff);
-    BlobContour* recs = nullptr;
-    uint32_t* pts = nullptr;
-    const BitPlanes bp{bits, w, h, L.wpr};
-    hipMemsetAsync(counters, 0, 64 * sizeof(int), s);
-    const dim3 grid_rows((L.wpr + 255) / 256, h);
-    hipLaunchKernelGGL(blob_bitplanes_kernel, grid_rows, dim3(256), 0, s, d_img, d_stride, w, h, L.wpr, bits);
-    hipLaunchKernelGGL(blob_count_kernel, dim3(h, kNumThresh), dim3(256), 0, s, bp, wordpre, rowcnt);
-    hipLaunchKernelGGL(blob_rowscan_kernel, dim3(kNumThresh), dim3(256), 0, s, h, (const uint32_t*)rowcnt, rowoff, counters);
-    hipLaunchKernelGGL(blob_bases_kernel, dim3(1), dim3(64), 0, s, counters);
-    int hc[64];
-    if (hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        err = "blob detector: device error";
-        return false;
-    }
-    const long long N = (uint32_t)hc[3];
-    if (N > (1ll << 27)) { err = "blob detector: more border starts than it takes (pure noise?)"; return false; }
-    if (N > 0) {
-        char* nb = (char*)node_scratch((size_t)N * kBlobNodeBytes + 16 * 256);
-        if (!nb) { err = "blob detector: out of device memory"; return false; }
-        BlobNodes nd;
-        size_t off = 0;
-        auto take = [&](size_t bytes) { char* p = nb + off; off += (bytes * (size_t)N + 255) / 256 * 256; return p; };
-        nd.a00 = (unsigned long long*)take(8);
-        nd.sa[0] = (unsigned long long*)take(8);
-        nd.sa[1] = (unsigned long long*)take(8);
-        nd.key = (uint32_t*)take(4);
-        nd.next = (uint32_t*)take(4);
-        nd.n = (uint32_t*)take(4);
-        nd.jmp = (uint32_t*)take(4);
-        nd.leader = (uint32_t*)take(4);
-        nd.ptr[0] = (uint32_t*)take(4);
-        nd.ptr[1] = (uint32_t*)take(4);
-        nd.sn[0] = (uint32_t*)take(4);
-        nd.sn[1] = (uint32_t*)take(4);
-        nd.off = (int32_t*)take(4);
-        int maxn = 1;
-        for (int t = 0; t < kNumThresh; ++t) maxn = std::max(maxn, hc[4 + t]);
-        int rounds = 1;  // 2^rounds >= the longest cycle (in arcs) there can be
-        while ((1ll << rounds) < maxn) ++rounds;
-        const dim3 gn((unsigned)((N + 255) / 256));
-        hipLaunchKernelGGL(blob_keys_kernel, dim3(grid_rows.x, grid_rows.y, kNumThresh), dim3(256), 0, s, bp, (const uint32_t*)wordpre,
-                           (const uint32_t*)rowoff, nd.key, (const int*)counters);
-        hipLaunchKernelGGL(blob_arcs_kernel, gn, dim3(256), 0, s, bp, (const uint32_t*)wordpre, (const uint32_t*)rowoff, nd, counters);
-        for (int r = 0; r < (rounds + 1) / 2 * 2; ++r)  // (an even number: the result is back in (jmp, leader))
-            if (r & 1)
-                hipLaunchKernelGGL(blob_leader_round_kernel, gn, dim3(256), 0, s, (const uint32_t*)nd.ptr[0], (const uint32_t*)nd.ptr[1],
-                                   nd.jmp, nd.leader, (const int*)counters);
-            else
-                hipLaunchKernelGGL(blob_leader_round_kernel, gn, dim3(256), 0, s, (const uint32_t*)nd.jmp, (const uint32_t*)nd.leader,
-                                   nd.ptr[0], nd.ptr[1], (const int*)counters);
-        hipLaunchKernelGGL(blob_rank_init_kernel, gn, dim3(256), 0, s, nd, (const int*)counters);
-        int rk = 0;
-        for (int r = 0; r < rounds; ++r, rk ^= 1)
-            hipLaunchKernelGGL(blob_rank_round_kernel, gn, dim3(256), 0, s, nd, rk, (const int*)counters);
-        // how many contours pass the area filter, and how many points they have: the arrays for them are sized from that
-        hipLaunchKernelGGL(blob_records_kernel<false>, gn, dim3(256), 0, s, nd, rk, recs, counters);
-        if (hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            err = "blob detector: device error";
-            return false;
-        }
-        if (hc[2]) { err = "blob detector: a border arc longer than 2^20 steps"; return false; }
-        if (hc[0] > 0) {
-            const size_t rec_bytes = ((size_t)hc[0] * sizeof(BlobContour) + 255) / 256 * 256;
-            char* ob = (char*)out_scratch(rec_bytes + (size_t)hc[1] * 4);
-            if (!ob) { err = "blob detector: out of device memory"; return false; }
-            recs = (BlobContour*)ob;
-            pts = (uint32_t*)(ob + rec_bytes);
-            hipLaunchKernelGGL(blob_records_kernel<true>, gn, dim3(256), 0, s, nd, rk, recs, counters);
-            hipLaunchKernelGGL(blob_points_kernel, gn, dim3(256), 0, s, bp, (const uint32_t*)wordpre, (const uint32_t*)rowoff, nd, rk,
-                               pts, counters);
-        }
-    } else {
-        hc[0] = hc[1] = 0;
-    }
-    std::vector<BlobContour> hrec((size_t)hc[0]);
-    std::vector<uint32_t> hpts((size_t)hc[1]);
-    if ((hc[0] && hipMemcpyAsync(hrec.data(), recs, hrec.size() * sizeof(BlobContour), hipMemcpyDeviceToHost, s) != hipSuccess) ||
-        (hc[1] && hipMemcpyAsync(hpts.data(), pts, hpts.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        err = "blob detector: download failed";
-        return false;
-    }
-    // contours of a threshold in cv::findContours' RETR_LIST order: discovery order (raster order of the
-    // starts), reversed
-    std::sort(hrec.begin(), hrec.end(), [](const BlobContour& a, const BlobContour& b) {
-        return a.t != b.t ? a.t < b.t : a.key > b.key;
-    });
-    // the per-contour filters (moments, hull, radius: independent, ~40 ns per contour point) on a few host threads;
-    // the grouping below walks the results in order
-    std::vector<Center> centers(hrec.size());
-    std::vector<char> keep(hrec.size(), 0);
-    {
-        auto work = [&](size_t lo, size_t hi) {
-            for (size_t k = lo; k < hi; ++k) {
-                contour_sums(hrec[k], hpts.data() + hrec[k].points_off);
-                keep[k] = contour_to_center(hrec[k], hpts.data() + hrec[k].points_off, h_img, w, h, h_stride, &centers[k]);
-            }
-        };
-        const unsigned hw = std::thread::hardware_concurrency();
-        const size_t nthr = std::min<size_t>(std::min<size_t>(hw ? hw : 1, 16), hpts.size() / 16384 + 1);
-        if (nthr <= 1) {
-            work(0, hrec.size());
-        } else {  // contiguous ranges of about equal point counts
-            std::vector<std::thread> pool;
-            size_t lo = 0, acc = 0, part = 1;
-            for (size_t k = 0; k < hrec.size(); ++k) {
-                acc += (size_t)hrec[k].n;
-                if (acc * nthr >= hpts.size() * part && part < nthr) {
-                    pool.emplace_back(work, lo, k + 1);
-                    lo = k + 1;
-                    ++part;
-                }
-            }
-            work(lo, hrec.size());
-            for (std::thread& th : pool) th.join();
-        }
-    }
-    std::vector<std::vector<Center>> groups;  // blobdetector.cpp detect(): centres of one blob across thresholds
+namespace {
+
+// blobdetector.cpp detect() for one frame: the centres of one blob across thresholds grouped, the keypoints of the
+// groups appended as (x, y) * 1000 ints.  rec[0 .. n): the frame's contours, threshold ascending.
+void group_keypoints(const BlobContour* rec, const Center* centers, const char* keep, size_t n, std::vector<int32_t>& xy_out) {
+    std::vector<std::vector<Center>> groups;
     size_t i = 0;
     for (int t = 0; t < kNumThresh; ++t) {
         std::vector<Center> cur;
-        for (; i < hrec.size() && hrec[i].t == t; ++i)
+        for (; i < n && rec[i].t == t; ++i)
             if (keep[i]) cur.push_back(centers[i]);
         std::vector<std::vector<Center>> fresh;
         for (const Center& c : cur) {
@@ -773,7 +681,267 @@ bool blob_detect(const uint8_t* d_img, int d_stride, const uint8_t* h_img, int h
         xy_out.push_back((int)((double)tx + 0.5));
         xy_out.push_back((int)((double)ty + 0.5));
     }
-    return true;
+}
+
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// plane scratch of a chunk of nf frames: the counters, then bit planes, word prefixes, row counts and row offsets of
+// its nf * 17 planes
+struct ChunkLayout {
+    int wpr;
+    size_t o_counters, o_bits, o_wordpre, o_rowcnt, o_rowoff, bytes;
+};
+ChunkLayout chunk_layout(int w, int h, int nf) {
+    ChunkLayout L;
+    L.wpr = (w + 31) / 32;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t planes = (size_t)nf * kNumThresh;
+    L.o_counters = take((size_t)blob_counter_words(nf) * sizeof(int));
+    L.o_bits = take(planes * h * L.wpr * 4);
+    L.o_wordpre = take(planes * h * L.wpr * 4);
+    L.o_rowcnt = take(planes * h * 4);
+    L.o_rowoff = take(planes * h * 4);
+    L.bytes = off;
+    return L;
+}
+
+constexpr int kBadNodes = 1, kBadArc = 2;  // why a frame has no result (blob_detect_batch)
+
+// Frames [f0, f0 + nf) of the batch as ONE chunk: every kernel once, three round trips (node counts; record and point
+// counts; records and points), the filters of all its contours on `nthreads` host threads, the grouping per frame.
+// 0: xy[f0 ..] hold the keypoints (a lone frame with an arc above kMaxArc: bad[f0] = kBadArc instead); 1: more nodes or
+// points than one node space takes, or an arc above kMaxArc somewhere in a chunk of several frames -- the caller
+// splits the chunk; < 0: an error code.
+int blob_chunk(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int f0, int nf, int nthreads, std::vector<int32_t>* xy,
+               char* bad) {
+    const int w = fr->width, h = fr->height, P = nf * kNumThresh, nwords = blob_counter_words(nf);
+    const ChunkLayout L = chunk_layout(w, h, nf);
+    int rc;
+    if ((rc = ensure(ctx, ctx->blob_scratch, L.bytes))) return rc;
+    hipStream_t s = ctx->pix;
+    char* base = (char*)ctx->blob_scratch.p;
+    int* words = (int*)(base + L.o_counters);
+    auto counters_at = [&](int* p) {
+        BlobCounters c;
+        c.err = p;
+        c.plane_cnt = c.err + nf;
+        c.plane_base = c.plane_cnt + P;
+        c.rec_cnt = c.plane_base + P;
+        c.pts_cnt = c.rec_cnt + nf;
+        c.rec_base = c.pts_cnt + nf;
+        c.pts_base = c.rec_base + nf;
+        c.rec_cur = c.pts_base + nf;
+        c.pts_cur = c.rec_cur + nf;
+        return c;
+    };
+    const BlobCounters cn = counters_at(words);
+    std::vector<int> hwords((size_t)nwords);
+    const BlobCounters hc = counters_at(hwords.data());
+    uint32_t* bits = (uint32_t*)(base + L.o_bits);
+    uint32_t* wordpre = (uint32_t*)(base + L.o_wordpre);
+    uint32_t* rowcnt = (uint32_t*)(base + L.o_rowcnt);
+    uint32_t* rowoff = (uint32_t*)(base + L.o_rowoff);
+    const BitPlanes bp{bits, w, h, L.wpr};
+    const uint8_t* img = fr->frames + (size_t)f0 * fr->frame_pitch;
+    // device time of the chunk's kernels (kernel timing on): events around each of the three stretches of kernels
+    const bool timed = ctx->timing;
+    if (timed)
+        for (hipEvent_t& e : ctx->blob_ev)
+            if (!e) MRG_HIP_CHECK(hipEventCreate(&e));
+    auto kernels_begin = [&] { if (timed) hipEventRecord(ctx->blob_ev[0], s); };
+    auto kernels_end = [&] { if (timed) hipEventRecord(ctx->blob_ev[1], s); };
+    // the counters back on the host: one copy, one synchronisation
+    auto round_trip = [&]() -> int {
+        if (hipMemcpyAsync(hwords.data(), words, (size_t)nwords * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return fail(ctx, MRGINGHAM_AMD_ERR_DEVICE, "blob detector: device error (%s)", hipGetErrorString(hipGetLastError()));
+        float ms = 0.f;
+        if (timed && hipEventElapsedTime(&ms, ctx->blob_ev[0], ctx->blob_ev[1]) == hipSuccess) ctx->blob_stat[5] += ms;
+        return 0;
+    };
+
+    hipMemsetAsync(words, 0, (size_t)nwords * sizeof(int), s);
+    kernels_begin();
+    const dim3 grid_rows((L.wpr + 255) / 256, h, nf);
+    hipLaunchKernelGGL(blob_bitplanes_kernel, grid_rows, dim3(256), 0, s, img, (long long)fr->frame_pitch, fr->stride, w, h, L.wpr, bits);
+    hipLaunchKernelGGL(blob_count_kernel, dim3(h, P), dim3(256), 0, s, bp, wordpre, rowcnt);
+    hipLaunchKernelGGL(blob_rowscan_kernel, dim3(P), dim3(256), 0, s, h, (const uint32_t*)rowcnt, rowoff, cn.plane_cnt);
+    hipLaunchKernelGGL(blob_bases_kernel, dim3(1), dim3(256), 0, s, (const int*)cn.plane_cnt, cn.plane_base, (const int*)nullptr,
+                       (int*)nullptr, P);
+    kernels_end();
+    if ((rc = round_trip())) return rc;
+    long long N = 0;
+    int maxn = 1;
+    for (int p = 0; p < P; ++p) {
+        N += hc.plane_cnt[p];
+        maxn = std::max(maxn, hc.plane_cnt[p]);
+    }
+    if (N > (1ll << 27)) return 1;
+    ctx->blob_stat[1] += 1;
+    ctx->blob_stat[2] += (double)N;
+    size_t R = 0, Np = 0;
+    std::vector<BlobContour> hrec;
+    std::vector<uint32_t> hpts;
+    if (N > 0) {
+        if ((rc = ensure(ctx, ctx->blob_nodes, (size_t)N * kBlobNodeBytes + 16 * 256))) return rc;
+        char* nb = (char*)ctx->blob_nodes.p;
+        BlobNodes nd;
+        size_t off = 0;
+        auto take = [&](size_t bytes) { char* p = nb + off; off += (bytes * (size_t)N + 255) / 256 * 256; return p; };
+        nd.a00 = (unsigned long long*)take(8);
+        nd.sa[0] = (unsigned long long*)take(8);
+        nd.sa[1] = (unsigned long long*)take(8);
+        nd.key = (uint32_t*)take(4);
+        nd.next = (uint32_t*)take(4);
+        nd.n = (uint32_t*)take(4);
+        nd.jmp = (uint32_t*)take(4);
+        nd.leader = (uint32_t*)take(4);
+        nd.ptr[0] = (uint32_t*)take(4);
+        nd.ptr[1] = (uint32_t*)take(4);
+        nd.sn[0] = (uint32_t*)take(4);
+        nd.sn[1] = (uint32_t*)take(4);
+        nd.off = (int32_t*)take(4);
+        nd.plane = (uint16_t*)take(2);
+        int rounds = 1;  // 2^rounds >= the longest cycle (in arcs) there can be: the largest plane of the chunk
+        while ((1ll << rounds) < maxn) ++rounds;
+        const uint32_t n32 = (uint32_t)N;
+        const dim3 gn((unsigned)((N + 255) / 256));
+        kernels_begin();
+        hipLaunchKernelGGL(blob_keys_kernel, dim3(grid_rows.x, h, P), dim3(256), 0, s, bp, (const uint32_t*)wordpre,
+                           (const uint32_t*)rowoff, nd.key, nd.plane, (const int*)cn.plane_base);
+        hipLaunchKernelGGL(blob_arcs_kernel, gn, dim3(256), 0, s, bp, (const uint32_t*)wordpre, (const uint32_t*)rowoff, nd, n32, cn);
+        for (int r = 0; r < (rounds + 1) / 2 * 2; ++r)  // (an even number: the result is back in (jmp, leader))
+            if (r & 1)
+                hipLaunchKernelGGL(blob_leader_round_kernel, gn, dim3(256), 0, s, (const uint32_t*)nd.ptr[0], (const uint32_t*)nd.ptr[1],
+                                   nd.jmp, nd.leader, n32);
+            else
+                hipLaunchKernelGGL(blob_leader_round_kernel, gn, dim3(256), 0, s, (const uint32_t*)nd.jmp, (const uint32_t*)nd.leader,
+                                   nd.ptr[0], nd.ptr[1], n32);
+        hipLaunchKernelGGL(blob_rank_init_kernel, gn, dim3(256), 0, s, nd, n32);
+        int rk = 0;
+        for (int r = 0; r < rounds; ++r, rk ^= 1) hipLaunchKernelGGL(blob_rank_round_kernel, gn, dim3(256), 0, s, nd, rk, n32);
+        // how many contours of every frame pass the area filter, and how many points they have: the arrays for them are
+        // sized from that, and every frame gets its own stretch of both
+        hipLaunchKernelGGL(blob_records_kernel<false>, gn, dim3(256), 0, s, nd, rk, (BlobContour*)nullptr, n32, cn);
+        hipLaunchKernelGGL(blob_bases_kernel, dim3(2), dim3(256), 0, s, (const int*)cn.rec_cnt, cn.rec_base, (const int*)cn.pts_cnt,
+                           cn.pts_base, nf);
+        kernels_end();
+        if ((rc = round_trip())) return rc;
+        for (int f = 0; f < nf; ++f)
+            if (hc.err[f]) {  // (its lists are cut: nothing of the chunk's record counts can be trusted)
+                if (nf > 1) return 1;
+                bad[f0] = kBadArc;
+                return 0;
+            }
+        for (int f = 0; f < nf; ++f) {
+            R += (size_t)(uint32_t)hc.rec_cnt[f];
+            Np += (size_t)(uint32_t)hc.pts_cnt[f];
+        }
+        if (Np > 0x7fffffffull) return 1;  // (point offsets are 31 bits)
+        if (R > 0) {
+            const size_t rec_bytes = (R * sizeof(BlobContour) + 255) / 256 * 256;
+            if ((rc = ensure(ctx, ctx->blob_out, rec_bytes + Np * 4))) return rc;
+            BlobContour* recs = (BlobContour*)ctx->blob_out.p;
+            uint32_t* pts = (uint32_t*)((char*)ctx->blob_out.p + rec_bytes);
+            kernels_begin();
+            hipLaunchKernelGGL(blob_records_kernel<true>, gn, dim3(256), 0, s, nd, rk, recs, n32, cn);
+            hipLaunchKernelGGL(blob_points_kernel, gn, dim3(256), 0, s, bp, (const uint32_t*)wordpre, (const uint32_t*)rowoff, nd, rk,
+                               pts, recs, n32);
+            hipLaunchKernelGGL(blob_colour_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, recs, (int)R, img,
+                               (long long)fr->frame_pitch, fr->stride, w, h);
+            kernels_end();
+            hrec.resize(R);
+            hpts.resize(Np);
+            if (hipMemcpyAsync(hrec.data(), recs, R * sizeof(BlobContour), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                (Np && hipMemcpyAsync(hpts.data(), pts, Np * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+                hipStreamSynchronize(s) != hipSuccess)
+                return fail(ctx, MRGINGHAM_AMD_ERR_DEVICE, "blob detector: download failed (%s)", hipGetErrorString(hipGetLastError()));
+            float ms = 0.f;
+            if (timed && hipEventElapsedTime(&ms, ctx->blob_ev[0], ctx->blob_ev[1]) == hipSuccess) ctx->blob_stat[5] += ms;
+        }
+    }
+    ctx->blob_stat[3] += (double)R;
+    ctx->blob_stat[4] += (double)Np;
+
+    // host: per frame its contours in cv::findContours' RETR_LIST order per threshold (discovery order = raster order of the
+    // starts, reversed); the per-contour filters (moments, hull, radius: independent, ~40 ns per contour point) of the
+    // whole chunk; the grouping per frame
+    const double t_host = now_ms();
+    std::vector<size_t> first((size_t)nf + 1, 0);
+    for (int f = 0; f < nf; ++f) first[f + 1] = first[f] + (size_t)(uint32_t)hc.rec_cnt[f];
+    std::vector<Center> centers(R);
+    std::vector<char> keep(R, 0);
+    constexpr size_t kBlock = 32;  // contours a thread takes at a time
+    std::atomic<size_t> next_sort{0}, next_block{0}, next_group{0};
+    auto sort_frames = [&] {
+        for (size_t f; (f = next_sort.fetch_add(1)) < (size_t)nf;) {
+            for (size_t k = first[f]; k < first[f + 1]; ++k) hrec[k].t %= kNumThresh;
+            std::sort(hrec.begin() + first[f], hrec.begin() + first[f + 1],
+                      [](const BlobContour& a, const BlobContour& b) { return a.t != b.t ? a.t < b.t : a.key > b.key; });
+        }
+    };
+    auto filter_blocks = [&] {
+        for (size_t b; (b = next_block.fetch_add(1)) * kBlock < R;)
+            for (size_t k = b * kBlock; k < std::min(R, (b + 1) * kBlock); ++k)
+                keep[k] = contour_to_center(hrec[k], hpts.data() + hrec[k].points_off, &centers[k]);
+    };
+    auto group_frames = [&] {
+        for (size_t f; (f = next_group.fetch_add(1)) < (size_t)nf;)
+            group_keypoints(hrec.data() + first[f], centers.data() + first[f], keep.data() + first[f], first[f + 1] - first[f], xy[f0 + f]);
+    };
+    const int nthr = (int)std::min<size_t>((size_t)nthreads, Np / 16384 + 1);
+    ctx->pool.run(std::min(nthr, nf), sort_frames);
+    ctx->pool.run(nthr, filter_blocks);
+    ctx->pool.run(std::min(nthr, nf), group_frames);
+    ctx->blob_stat[6] += now_ms() - t_host;
+    return 0;
+}
+
+// chunk [f0, f0 + nf), halved for as long as it does not fit one node space; a lone frame that does not is left out
+int blob_chunk_split(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int f0, int nf, int nthreads, std::vector<int32_t>* xy,
+                     char* bad) {
+    const int rc = blob_chunk(ctx, fr, f0, nf, nthreads, xy, bad);
+    if (rc != 1) return rc;
+    if (nf == 1) {
+        bad[f0] = kBadNodes;
+        return 0;
+    }
+    const int half = nf / 2;
+    const int ra = blob_chunk_split(ctx, fr, f0, half, nthreads, xy, bad);
+    return ra ? ra : blob_chunk_split(ctx, fr, f0 + half, nf - half, nthreads, xy, bad);
+}
+
+}  // namespace
+
+// find_blobs_from_image_array (find_blobs.cc:14-46) for every frame of a batch on the context's device: xy[f] receives
+// frame f's keypoints as (x, y) * 1000 ints in SimpleBlobDetector's output order.  The batch is worked through in chunks
+// of frames whose plane scratch stays within ctx->blob_plane_budget (option "blob_chunk_frames": at most that many frames).
+// Returns 0; MRGINGHAM_AMD_ERR_CAPACITY when a frame has more border starts than a node space takes (2^27) or an arc above
+// 2^20 steps -- bad[f] != 0 for such a frame, the others are delivered --; another error code when the device fails.
+// Synchronous; the sizes have been checked by the caller (sides up to 32767 x 65535).
+int blob_detect_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int nthreads, std::vector<std::vector<int32_t>>& xy,
+                      std::vector<char>& bad) {
+    const int B = fr->nframes;
+    xy.assign((size_t)B, std::vector<int32_t>());
+    bad.assign((size_t)B, 0);
+    if (B <= 0 || fr->width <= 0 || fr->height <= 0) return 0;
+    fb_drain(ctx);  // (their grid finder runs on the pool the filters use)
+    const size_t per_frame = chunk_layout(fr->width, fr->height, 1).bytes;
+    int chunk = (int)std::min<size_t>(std::max<size_t>(ctx->blob_plane_budget / per_frame, 1), (size_t)kMaxChunkFrames);
+    if (ctx->blob_chunk_frames > 0) chunk = std::min(chunk, ctx->blob_chunk_frames);
+    ctx->blob_stat[0] += 1;
+    ctx->blob_stat[7] += B;
+    for (int f0 = 0; f0 < B; f0 += chunk) {
+        const int rc = blob_chunk_split(ctx, fr, f0, std::min(chunk, B - f0), nthreads, xy.data(), bad.data());
+        if (rc) return rc;
+    }
+    for (int f = 0; f < B; ++f)
+        if (bad[f])
+            return fail(ctx, MRGINGHAM_AMD_ERR_CAPACITY, "%s",
+                        bad[f] == kBadArc ? "blob detector: a border arc longer than 2^20 steps"
+                                          : "blob detector: more border starts than it takes (pure noise?)");
+    return 0;
 }
 
 }  // namespace mrg

@@ -83,7 +83,7 @@ static void add_elapsed_ms(double& total, hipEvent_t a, hipEvent_t b) {
 
 // grid-finder threads of the find_boards calls: <= 0 = one per core the process may use, at most 32 (the grid finder
 // takes ~0.1 ms per frame and level: a few dozen threads cover a batch)
-static int fb_threads(int nthreads) {
+int host_threads(int nthreads) {
     if (nthreads <= 0) {
         nthreads = (int)std::thread::hardware_concurrency();
         if (nthreads > 32) nthreads = 32;
@@ -104,7 +104,7 @@ static int find_boards_sync_levels(mrgingham_amd_ctx* ctx, const mrgingham_amd_f
     int rc = 0;
     const int B = fr->nframes, N = gridn * gridn;
     const int cap = 4 * N + 64;  // candidates kept per frame for the grid finder
-    nthreads = fb_threads(nthreads);
+    nthreads = host_threads(nthreads);
 
     DevBuf &d_xy = ctx->fb_xy, &d_cnt = ctx->fb_cnt, &d_pts = ctx->fb_pts, &d_lv = ctx->fb_lv, &d_np = ctx->fb_np;
     if ((rc = ensure(ctx, d_xy, (size_t)B * cap * 8)) || (rc = ensure(ctx, d_cnt, (size_t)B * 4)) ||
@@ -363,7 +363,7 @@ static int fb_host_begin(mrgingham_amd_ctx* ctx, mrgingham_amd_ctx::BoardsJob& j
             int grew = 0;
             harvest_status(ctx, job.set, job.levs[li], &grew, true);
         }
-    const int nthreads = fb_threads(job.nthreads);
+    const int nthreads = host_threads(job.nthreads);
     job.next.store(0);
     job.nworkers = (nthreads < B ? nthreads : B) - 1;  // + the calling thread, in fb_host_end
     job.owner = ctx;

@@ -1,7 +1,8 @@
 // The context of libmrgingham_amd.so and the helpers that more than one of its host files calls.  Internal: not
 // installed, not part of include/.  The host side is cut by concern: api.hip (context lifetime, options, scratch sets,
 // status words, the _batch entry points), multi.hip (several devices), reference.hip (the reference's own C symbols
-// over one frame), boards.hip (find_boards: the level search, synchronous and pipelined).
+// over one frame), boards.hip (find_boards: the level search, synchronous and pipelined), blobs_api.hip (the blob
+// detector and the circle-grid finder over a batch).
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -177,6 +178,12 @@ struct mrgingham_amd_ctx {
     hipEvent_t io_ev[4] = {};
     mrg::DevBuf clk;  // two u64: shader cycles and constant-rate ticks of the probed workgroups (mrgingham_amd_sclk_mhz)
     mrg::DevBuf pre_scratch, pre_tmp, pre_out, pre16_scratch, io_frame16, dbg_img, dbg_resp, blob_scratch, blob_nodes, blob_out;
+    // blob detector (blobs.hip): a batch is worked through in chunks of frames whose plane scratch (blob_scratch) stays
+    // within the budget; option "blob_chunk_frames" (test hook): at most that many frames per chunk, 0 = by budget
+    size_t blob_plane_budget = (size_t)1 << 30;
+    int blob_chunk_frames = 0;
+    hipEvent_t blob_ev[2] = {};  // around a chunk's kernels while kernel timing is on
+    double blob_stat[8] = {};    // mrgingham_amd_blobs_stats (+ [7]: frames)
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
     // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
     // context of THIS context's device, created on first use -- not on the calling thread's default context, which
@@ -279,6 +286,11 @@ bool detect_one_frame_all(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr
                           int32_t* count_out, bool debug = false, const char* debug_image_filename = nullptr);
 int refine_on_device(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, double* points_xy, signed char* level,
                      int Npoints, int image_pyramid_level, bool debug = false, const char* debug_image_filename = nullptr);
+
+// blobs.hip: cv::SimpleBlobDetector as find_blobs.cc:14-46 configures it (device border following, host filters)
+int blob_detect_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int nthreads, std::vector<std::vector<int32_t>>& xy,
+                      std::vector<char>& bad);
+int host_threads(int nthreads);
 
 // boards.hip
 struct GridScratch { std::vector<PointI> cand; std::vector<PointD> grid; };

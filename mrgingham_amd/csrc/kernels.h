@@ -86,16 +86,6 @@ bool launch_preprocess16_batch(const uint16_t* frames, long long pitch, int nfra
                                int blur_radius, uint8_t* out, void* scratch, uint8_t* tmp, hipStream_t s,
                                unsigned long long* clk = nullptr);
 
-// blobs.hip: cv::SimpleBlobDetector as find_blobs.cc:14-46 configures it (device border following, host filters)
-struct BlobScratchLayout {
-    int wpr;
-    size_t o_counters, o_bits, o_wordpre, o_rowcnt, o_rowoff;
-};
-size_t blob_scratch_bytes(int w, int h, BlobScratchLayout* lay);
-bool blob_detect(const uint8_t* d_img, int d_stride, const uint8_t* h_img, int h_stride, int w, int h, void* scratch,
-                 const std::function<void*(size_t)>& node_scratch, const std::function<void*(size_t)>& out_scratch, hipStream_t s,
-                 std::vector<int32_t>& xy_out, std::string& err);
-
 // cc.hip
 struct DetectOut {
     int32_t* xy;      // [nframes*capacity*2]

@@ -199,19 +199,18 @@ bool check_level_and_layout(const char* fn, int Nrows, int Ncols, int stride, in
     return true;
 }
 
-// find_blobs_from_image_array (find_blobs.cc:14-46) on a frame that lives on the device as `fr` (one frame) and
-// on the host as h_img: candidates as (x, y) * 1000 ints.
-static bool blobs_on_device(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, const uint8_t* h_img, int h_stride,
-                            std::vector<int32_t>& xy) {
-    if (ensure(ctx, ctx->blob_scratch, blob_scratch_bytes(fr->width, fr->height, nullptr))) return false;
-    std::string err;
-    auto nodes = [&](size_t bytes) -> void* { return ensure(ctx, ctx->blob_nodes, bytes) ? nullptr : ctx->blob_nodes.p; };
-    auto outs = [&](size_t bytes) -> void* { return ensure(ctx, ctx->blob_out, bytes) ? nullptr : ctx->blob_out.p; };
-    if (!blob_detect(fr->frames, fr->stride, h_img, h_stride, fr->width, fr->height, ctx->blob_scratch.p, nodes, outs, ctx->pix, xy,
-                     err)) {
-        fail(ctx, MRGINGHAM_AMD_ERR_CAPACITY, "%s", err.c_str());
+// find_blobs_from_image_array (find_blobs.cc:14-46) on a frame that lives on the device as `fr` (one frame): candidates
+// as (x, y) * 1000 ints.  The batch detector with a batch of one; a few host threads for the filters, as ever.
+static bool blobs_on_device(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, std::vector<int32_t>& xy) {
+    if (fr->width > 32767 || fr->height > 65535) {
+        fail(ctx, MRGINGHAM_AMD_ERR_CAPACITY, "blob detector: frames up to 32767 x 65535");
         return false;
     }
+    std::vector<std::vector<int32_t>> per_frame;
+    std::vector<char> bad;
+    const unsigned hw = std::thread::hardware_concurrency();
+    if (blob_detect_batch(ctx, fr, (int)std::min(hw ? hw : 1u, 16u), per_frame, bad)) return false;
+    xy.insert(xy.end(), per_frame[0].begin(), per_frame[0].end());
     return true;
 }
 
@@ -222,7 +221,7 @@ static bool blobs_of_host_frame(int Nrows, int Ncols, int stride, const char* im
     if (!ctx) return false;
     mrgingham_amd_frames fr;
     return upload_frame(ctx, imagebuffer, Nrows, Ncols, stride, &fr) == 0 &&
-           blobs_on_device(ctx, &fr, (const uint8_t*)imagebuffer, stride, xy);
+           blobs_on_device(ctx, &fr, xy);
 }
 
 // The 16-bit preprocessing of one host frame, mrgingham-from-image.cc:85-92 ([normalize to 0..65535 + CLAHE on 16 bits]
@@ -693,12 +692,8 @@ int mrgingham_amd_process_image_ex(const void* image, int bits, int width, int h
     std::vector<signed char> lv;
     if (o->do_blobs) {
         // mrgingham-from-image.cc:153-160: find_circle_grid_from_image_array on the preprocessed image, "level" 0
-        std::vector<uint8_t> host(npx);
         std::vector<int32_t> bxy;
-        if (copy_rows_async(host.data(), width, fr.frames, fr.stride, width, height, hipMemcpyDeviceToHost, ctx->pix) !=
-                hipSuccess ||
-            hipStreamSynchronize(ctx->pix) != hipSuccess || !blobs_on_device(ctx, &fr, host.data(), width, bxy))
-            return -2;
+        if (!blobs_on_device(ctx, &fr, bxy)) return -2;
         if (!grid_of_candidates(bxy.data(), (int)(bxy.size() / 2), o->gridn, xy_out)) return -1;
         if (levels_out) memset(levels_out, 0, (size_t)o->gridn * o->gridn);
         return 0;
