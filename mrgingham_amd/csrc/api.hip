@@ -1,6 +1,7 @@
-// Host side of libmrgingham_amd.so, the context itself: its lifetime and options, kernel timing, the scratch sets and
-// status words, sync and the stream hand-offs, and the _batch entry points (chain_batch with its sparse schedule).
-// multi.hip, reference.hip and boards.hip hold the rest of the host side (ctx.h).
+// Host side of libmrgingham_amd.so, the context itself: its lifetime and options, the kernel-timing read-out, the scratch
+// sets and status words, sync and the stream hand-offs, and the pixel-only _batch entry points (response, level images,
+// blur, preprocessing).  chain.hip (what the detector puts on the streams), multi.hip, reference.hip, boards.hip and
+// blobs_api.hip hold the rest of the host side (ctx.h).
 // See include/mrgingham_amd.h for the contract of every entry point.
 #include <stdarg.h>
 #include <stdio.h>
@@ -113,6 +114,22 @@ int ensure_level_set(mrgingham_amd_ctx* ctx, int set, int level, int nframes, in
             MRG_HIP_CHECK(hipMemset(ctx->counters2[k].p, 0, ctx->counters2[k].bytes));
             ctx->status_copied[k] = false;  // (the layout of the words changes with counters_nf)
         }
+        // the page-locked mirrors of the status words (end_op copies into them) change size with it: here, where the
+        // device is idle and nothing is queued.  A mirror that cannot be had stays away until the next growth (the sync
+        // then makes a blocking copy: harvest_set)
+        const size_t words = (size_t)(kMaxLevel + 1) * cnf;
+        for (int k = 0; k < kMaxSets; ++k) {
+            if (ctx->status_pin[k]) hipHostFree(ctx->status_pin[k]);
+            ctx->status_pin[k] = nullptr;
+            ctx->status_pin_words[k] = 0;
+            void* p = nullptr;
+            if (hipHostMalloc(&p, words * sizeof(int32_t), hipHostMallocDefault) == hipSuccess) {
+                ctx->status_pin[k] = (int32_t*)p;
+                ctx->status_pin_words[k] = words;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
         ctx->counters_nf = cnf;
     }
     if ((rc = ensure(ctx, L.hot_xy, nf * (size_t)cap * 4))) return rc;
@@ -192,7 +209,6 @@ int ensure_level(mrgingham_amd_ctx* ctx, int level, int nframes, int W, int H, i
     return rc;
 }
 
-constexpr int kCellsPerPoint = 9;  // sparse refinement: distinct cells the 3 x 3 seeds of one point can mark (2 x 2 each, one pixel apart)
 // Per-call point scratch shared by the levels (the component kernels of the levels of one call
 // run one after the other on that call's component stream); one copy per scratch set.
 int ensure_points(mrgingham_amd_ctx* ctx, int nframes, int pitch) {
@@ -217,99 +233,6 @@ int ensure_points(mrgingham_amd_ctx* ctx, int nframes, int pitch) {
     ctx->pts_nframes = nframes;
     ctx->pts_pitch = pitch;
     return 0;
-}
-
-static hipEvent_t timing_event(mrgingham_amd_ctx* ctx) {
-    hipEvent_t e;
-    if (!ctx->event_pool.empty()) { e = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
-    else hipEventCreate(&e);
-    return e;
-}
-
-static void launch_chess_any(mrgingham_amd_ctx* ctx, const LevelBatch& lb, const CompTables& t, int n, bool clamp,
-                             bool hot, hipStream_t s, bool time_it) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (time_it && ctx->timing) {
-        e0 = timing_event(ctx);
-        e1 = timing_event(ctx);
-        hipEventRecord(e0, s);
-    }
-    if (lb.w > 0 && lb.h > 0 && n > 0) {
-#ifdef MRG_EXPERIMENT
-        if (ctx->use_v0) launch_chess_v0(lb, t, 0, n, clamp, hot, s);
-        else
-#endif
-        if (!hot && ((ctx->chess_variant == 0 && chess16_pays(lb, n)) || (ctx->chess_variant == 16 && chess16_ok(lb)))) launch_chess16(lb, 0, n, clamp, s, ctx->chess16_seg);
-#ifdef MRG_EXPERIMENT
-        else if (hot && (ctx->chess_variant_hot & 16) && !t.only && chess16_ok(lb)) launch_chess16_hot(lb, t, 0, n, s);
-#endif
-        else launch_chess(lb, t, 0, n, clamp, hot, s, ctx->chess_seg);
-    }
-    if (e0) {
-        hipEventRecord(e1, s);
-        ctx->events.emplace_back(e0, e1);
-    }
-}
-
-// Every detect / refine / chain call starts here: the pixel stream must not
-// overwrite level scratch the component stream of the previous call still reads.
-void begin_op(mrgingham_amd_ctx* ctx, int max_level) {
-    (void)max_level;
-    ctx->cur = (ctx->cur + 1) % ctx->nsets;  // this set was last used nsets calls ago
-    ctx->status_copied[ctx->cur] = false;    // (until this op's end_op has queued its copy)
-    if (ctx->cc_pending[ctx->cur]) hipStreamWaitEvent(ctx->pix, ctx->ev_cc_done[ctx->cur], 0);
-    // The hot-pixel counters of this set are zero here: they are zeroed at allocation and again by
-    // end_op behind the component kernels that consumed them -- on the component stream, off the
-    // pixel stream's critical path.  (Status words only ever accumulate; mrgingham_amd_sync reads
-    // and clears them.)
-}
-// Registers the caller-owned device buffers this call writes (w) and reads (r) and makes its
-// component stream wait for the previous call (which runs on the OTHER component stream) when
-// they overlap anything that call wrote or read-then-we-write.  Call after begin_op.
-void order_after_previous(mrgingham_amd_ctx* ctx, std::initializer_list<mrgingham_amd_ctx::Span> w,
-                          std::initializer_list<mrgingham_amd_ctx::Span> r) {
-    const int cur = ctx->cur;
-    auto overlaps = [](const mrgingham_amd_ctx::Span& a, const mrgingham_amd_ctx::Span& b) {
-        return a.p && b.p && a.n && b.n && a.p < b.p + b.n && b.p < a.p + a.n;
-    };
-    for (int prev = 0; prev < kMaxSets; ++prev) {  // every call that may still be running on another component stream
-        if (prev == cur || !ctx->cc_pending[prev]) continue;
-        bool dep = false;
-        for (const auto& pw : ctx->last_w[prev]) {
-            for (const auto& x : w) dep |= overlaps(x, pw);
-            for (const auto& x : r) dep |= overlaps(x, pw);
-        }
-        for (const auto& pr : ctx->last_r[prev])
-            for (const auto& x : w) dep |= overlaps(x, pr);
-        if (dep) hipStreamWaitEvent(ctx->ccs[cur], ctx->ev_cc_done[prev], 0);
-    }
-    ctx->last_w[cur].assign(w.begin(), w.end());
-    ctx->last_r[cur].assign(r.begin(), r.end());
-}
-void end_op(mrgingham_amd_ctx* ctx) {
-    hipMemsetAsync(ctx->counters2[ctx->cur].p, 0, (size_t)(kMaxLevel + 1) * ctx->counters_nf * sizeof(int32_t),
-                   cur_cc(ctx));
-    hipEventRecord(ctx->ev_cc_done[ctx->cur], cur_cc(ctx));
-    ctx->cc_pending[ctx->cur] = true;
-    // the set's status words, behind everything of this op that can set one (behind the event too: whoever waits for
-    // the op does not wait for the copy; mrgingham_amd_sync waits for the stream)
-    const int set = ctx->cur;
-    const size_t words = (size_t)(kMaxLevel + 1) * (size_t)ctx->counters_nf;
-    if (ctx->status_pin_words[set] < words) {
-        if (ctx->status_pin[set]) hipHostFree(ctx->status_pin[set]);
-        ctx->status_pin[set] = nullptr;
-        ctx->status_pin_words[set] = 0;
-        void* p = nullptr;
-        if (hipHostMalloc(&p, words * sizeof(int32_t), hipHostMallocDefault) == hipSuccess) {
-            ctx->status_pin[set] = (int32_t*)p;
-            ctx->status_pin_words[set] = words;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    ctx->status_copied[set] = ctx->status_pin[set] != nullptr && words > 0 &&
-                              hipMemcpyAsync(ctx->status_pin[set], status_of(ctx, 0), words * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                             cur_cc(ctx)) == hipSuccess;
 }
 
 // The status words of one (scratch set, level) as the host has them (`host`: nact words), inspected; `words` = where they
@@ -391,7 +314,7 @@ static int harvest_set(mrgingham_amd_ctx* ctx, int set, int* rc) {
     }
     const size_t cnf = (size_t)ctx->counters_nf, nwords = (size_t)(hi - lo + 1) * cnf;
     const int32_t* host;
-    const bool pinned = ctx->status_copied[set] && ctx->status_pin[set] && ctx->status_pin_words[set] >= (size_t)(kMaxLevel + 1) * cnf;
+    const bool pinned = ctx->status_copied[set];  // (end_op's copy: the whole block, sized by counters_nf like the words)
     if (pinned) {  // (the set's stream has been waited for: the copy end_op queued has landed)
         host = ctx->status_pin[set] + (size_t)lo * cnf;
     } else {
@@ -413,12 +336,11 @@ static int harvest_set(mrgingham_amd_ctx* ctx, int set, int* rc) {
     return 0;
 }
 
-// Level images of levels [1, max_level] of the batch into the level scratch, on the pixel stream.
 // One level image (level >= 1) of the batch into `out` (dense, frames back to back): levels 1..3 through the
 // one-pass pyramid kernel restricted to that level (16 x 8 source blocks per thread, 16-byte loads; the
 // per-pixel kernel took 425 us for level 1 of 64 frames of 4096x3072, this one reads the frames at HBM speed),
 // which falls back to the per-pixel kernels itself for ragged shapes.
-static void launch_one_level_image(const mrgingham_amd_frames* fr, int level, uint8_t* out, int w, int h, hipStream_t s) {
+void launch_one_level_image(const mrgingham_amd_frames* fr, int level, uint8_t* out, int w, int h, hipStream_t s) {
     const FrameBatch fb{fr->frames, fr->frame_pitch, fr->width, fr->height, fr->stride};
     if (level <= 3) {
         PyramidOut po{};
@@ -429,144 +351,6 @@ static void launch_one_level_image(const mrgingham_amd_frames* fr, int level, ui
     } else {
         launch_decimate(fb, level, out, (long long)w * h, w, h, 0, fr->nframes, s);
     }
-}
-
-static PyramidOut pyramid_out_of(mrgingham_amd_ctx* ctx, int max_level) {
-    PyramidOut po{};
-    const int top = max_level < 3 ? max_level : 3;
-    for (int L = 1; L <= top; ++L) {
-        po.out[L - 1] = (uint8_t*)cur_levels(ctx)[L].img.p;
-        po.w[L - 1] = cur_levels(ctx)[L].w;
-        po.h[L - 1] = cur_levels(ctx)[L].h;
-    }
-    return po;
-}
-// `levels_1_to_3` false: those come out of the level-0 response kernel (launch_chess_pyramid)
-void queue_level_images(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int max_level, bool levels_1_to_3,
-                        bool gentle) {
-    const FrameBatch fb{fr->frames, fr->frame_pitch, fr->width, fr->height, fr->stride};
-    const int top = max_level < 3 ? max_level : 3;
-    if (top >= 1 && levels_1_to_3) launch_pyramid(fb, pyramid_out_of(ctx, max_level), top, fr->nframes, ctx->pix, gentle);
-    for (int L = 4; L <= max_level; ++L)
-        launch_decimate(fb, L, (uint8_t*)cur_levels(ctx)[L].img.p, (long long)cur_levels(ctx)[L].w * cur_levels(ctx)[L].h,
-                        cur_levels(ctx)[L].w, cur_levels(ctx)[L].h, 0, fr->nframes, ctx->pix);
-}
-
-// ChESS response (+ hot list) of one level for the whole batch on the pixel
-// stream; records ev_pix[level].  Level images of levels > 0 must already be queued.
-LevelBatch level_batch_of(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level) {
-    LevelScratch& L = cur_levels(ctx)[level];
-    LevelBatch lb;
-    lb.nframes = fr->nframes;
-    lb.w = L.w;
-    lb.h = L.h;
-    if (level == 0) {
-        lb.img = fr->frames;
-        lb.img_pitch = fr->frame_pitch;
-        lb.img_stride = fr->stride;
-    } else {
-        lb.img = (const uint8_t*)L.img.p;
-        lb.img_pitch = (long long)L.w * L.h;
-        lb.img_stride = L.w;
-    }
-    lb.resp = (int16_t*)L.resp.p;
-    lb.resp_pitch = (long long)L.w * L.h;
-    if (level == 0 && ctx->clk_on) lb.clk = (unsigned long long*)ctx->clk.p;  // (mrgingham_amd_sclk_mhz)
-    return lb;
-}
-LevelBatch queue_level_chess(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level) {
-    const LevelBatch lb = level_batch_of(ctx, fr, level);
-    launch_chess_any(ctx, lb, tables_of(ctx, level), fr->nframes, true, true, ctx->pix, level == 0);
-    hipEventRecord(ctx->ev_pix[level], ctx->pix);
-    if (fr->nframes > ctx->pending_frames[ctx->cur][level]) ctx->pending_frames[ctx->cur][level] = fr->nframes;
-    return lb;
-}
-
-
-// SPARSE REFINEMENT of the points in `io` (at pyramid level `top`, level images of all levels in the current set's
-// scratch) through levels top-1 .. 0, on the current set's component stream, level by level: list the cells around the
-// points (sparse_cells_kernel for the first level, the refinement kernel of the level above for the others) ->
-// response + hot masks in those cells (chess_cells_kernel) -> refinement out of LDS on exactly those hot pixels
-// (window mode, `marked<BOXED = true>`).  A frame the LDS kernel cannot take (a blob that reaches the edge of its
-// cells, > 512 points, > 2048 hot pixels in the cells that no band cut separates) sets kStatusSparse in its status
-// words -- at that level and, because nobody lists its cells any more, at every level below -- and is REPEATED DENSELY
-// behind the last sparse level, on the device, before the call completes: its points go back to where they started
-// (`restore`), the ordinary response kernel computes its levels and the global-memory refinement replays them, on
-// the flagged frames alone (see the end of this function), and the flags are cleared.  So the outputs are the dense
-// schedule's on every frame, with no host round trip and nothing for the caller to repeat.
-// `dense_only`: no sparse pass at all -- the ordinary kernels on every frame, level by level, on the component stream
-// (the refinement of find_boards_submit when the sparse schedule is switched off or does not pay).
-int queue_sparse_levels(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int top, RefineIO io,
-                        const SparseRestore& restore, bool dense_only) {
-    auto& ps = ctx->pts[ctx->cur];
-    const int nf = fr->nframes;
-    hipStream_t cc = cur_cc(ctx);
-    LevelBatch lbs[kMaxLevel + 1];
-    if (dense_only) {
-        for (int L = top - 1; L >= 0; --L) {
-            lbs[L] = level_batch_of(ctx, fr, L);
-            const CompTables t = tables_of(ctx, L);
-            launch_chess_any(ctx, lbs[L], t, nf, true, true, cc, false);
-            launch_cc_refine(lbs[L], t, L, io, 0, nf, cc);
-            if (nf > ctx->pending_frames[ctx->cur][L]) ctx->pending_frames[ctx->cur][L] = nf;
-        }
-        return 0;
-    }
-    const int list_pitch = kCellsPerPoint * io.pitch;
-    io.subsets = ctx->sparse_subsets;
-    uint32_t* const lists[2] = {(uint32_t*)ps.cell_list.p, (uint32_t*)ps.cell_list.p + (size_t)nf * list_pitch};
-    io.list_pitch = list_pitch;
-    int32_t* cnt = (int32_t*)ps.cell_cnt.p;  // [level][frame][kCellHdr]
-    for (int L = top - 1; L >= 0; --L) {
-        lbs[L] = level_batch_of(ctx, fr, L);
-        CompTables t = tables_of(ctx, L);
-        t.lds_path |= kLdsPathSparse;
-        io.cell_list = lists[L & 1];
-        io.next_list = lists[(L & 1) ^ 1];
-        io.cell_cnt = cnt + (size_t)L * nf * kCellHdr;
-        // the cells of this level: listed by the refinement kernel of the level above, by a kernel of its own
-        // for the first one (its points come out of the detection / from the caller)
-        if (L == top - 1)
-            launch_sparse_cells(lbs[L], t, L, io, io.cell_list, cnt + (size_t)L * nf * kCellHdr, list_pitch, 0, nf, cc, cnt, nf);
-        launch_chess_cells(lbs[L], t, io.cell_list, io.cell_cnt, list_pitch, 0, nf, cc);
-        io.next_cnt = nullptr;
-        if (L > 0) {
-            const LevelScratch& nx = cur_levels(ctx)[L - 1];
-            io.next_cnt = cnt + (size_t)(L - 1) * nf * kCellHdr;
-            io.next_w = nx.w;
-            io.next_h = nx.h;
-            io.next_max_items = tables_of(ctx, L - 1).gidx_pitch / 4;
-        }
-        launch_cc_refine(lbs[L], t, L, io, 0, nf, cc);
-        if (nf > ctx->pending_frames[ctx->cur][L]) ctx->pending_frames[ctx->cur][L] = nf;
-    }
-    // the dense repeat of what was reported (flag = the level-0 status word: a frame given up at any level is given up
-    // at every level below it): three small launches -- the flagged frames as a list; their dense responses at every
-    // level (one grid, laid out for kOnlySlots frames whatever the batch); per listed frame restore + the refinement of
-    // every level + clear.  Every kernel boundary of this chain costs ~10 us whether or not a frame is flagged, and a
-    // full-size grid of the response kernel that finds nothing to do still waits for LDS and registers on a chip the
-    // pixel stream keeps full: eleven full-size launches were 8 % of a sparse step.
-    int32_t* flags = status_of(ctx, 0);
-    int32_t* list = (int32_t*)ps.flag_list.p;
-    launch_sparse_flag_list(flags, nf, list, cc);
-    RefineIO dio = io;
-    dio.cell_list = nullptr;
-    dio.cell_cnt = nullptr;
-    dio.list_pitch = 0;
-    dio.next_cnt = nullptr;
-    LevelBatch mlb[kRefineLevelsMax];   // largest level first (launch_chess_multi)
-    CompTables mt[kRefineLevelsMax], lt[kRefineLevelsMax];
-    for (int L = 0; L < top; ++L) {
-        lt[L] = tables_of(ctx, L);
-        mlb[L] = lbs[L];
-        mt[L] = lt[L];
-        mt[L].only = list;
-    }
-    const bool merged = top >= 2 && chess_multi_ok(mlb, top, nf) && launch_chess_multi(mlb, mt, top, nf, cc, ctx->chess_seg);
-    if (!merged)
-        for (int L = top - 1; L >= 0; --L) launch_chess(lbs[L], mt[L], 0, nf, true, true, cc, ctx->chess_seg);
-    launch_cc_refine_flagged_levels(lbs, lt, top, dio, restore, list, flags, ctx->counters_nf, (int32_t*)ctx->sparse_stat.p, cc);
-    return 0;
 }
 
 }  // namespace mrg
@@ -1088,330 +872,3 @@ int mrg::queue_preprocess16(mrgingham_amd_ctx* ctx, const uint16_t* d_frames, in
     MRG_HIP_CHECK(hipGetLastError());
     return 0;
 }
-
-extern "C" {
-
-int mrgingham_amd_detect_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level, int32_t* d_xy,
-                               int capacity_per_frame, int32_t* d_counts) {
-    int rc = validate_frames(ctx, fr);
-    if (rc) return rc;
-    fb_drain(ctx);
-    int w, h;
-    if (level_dims(fr->width, fr->height, level, &w, &h))
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "Got an unreasonable image_pyramid_level = %d", level);
-    if (fr->nframes == 0) return 0;
-    if (!d_xy || !d_counts || capacity_per_frame < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "NULL outputs");
-    MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    if ((rc = choose_sets(ctx, fr))) return rc;
-    if ((rc = ensure_level(ctx, level, fr->nframes, fr->width, fr->height, 0))) return rc;
-    begin_op(ctx, level);
-    if (level > 0) {
-        launch_one_level_image(fr, level, (uint8_t*)cur_levels(ctx)[level].img.p, w, h, ctx->pix);
-    }
-    const LevelBatch lb = queue_level_chess(ctx, fr, level);
-    order_after_previous(ctx, {{(const char*)d_xy, (size_t)fr->nframes * capacity_per_frame * 8},
-                               {(const char*)d_counts, (size_t)fr->nframes * 4}}, {});
-    MRG_HIP_CHECK(hipStreamWaitEvent(cur_cc(ctx), ctx->ev_pix[level], 0));
-    launch_cc_detect(lb, tables_of(ctx, level), level, DetectOut{d_xy, capacity_per_frame, d_counts}, 0,
-                     fr->nframes, cur_cc(ctx));
-    end_op(ctx);
-    MRG_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int mrgingham_amd_refine_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level, double* d_points,
-                               signed char* d_levels, const int32_t* d_npoints, int points_pitch,
-                               int32_t* d_nrefined) {
-    int rc = validate_frames(ctx, fr);
-    if (rc) return rc;
-    fb_drain(ctx);
-    int w, h;
-    if (level_dims(fr->width, fr->height, level, &w, &h))
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "Got an unreasonable image_pyramid_level = %d", level);
-    if (fr->nframes == 0) return 0;
-    if (!d_points || !d_levels || !d_npoints || points_pitch <= 0)
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "NULL point buffers");
-    MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    if ((rc = choose_sets(ctx, fr))) return rc;
-    if ((rc = ensure_level(ctx, level, fr->nframes, fr->width, fr->height, points_pitch))) return rc;
-    if ((rc = ensure_points(ctx, fr->nframes, points_pitch))) return rc;
-    begin_op(ctx, level);
-    if (level > 0) {
-        launch_one_level_image(fr, level, (uint8_t*)cur_levels(ctx)[level].img.p, w, h, ctx->pix);
-    }
-    const LevelBatch lb = queue_level_chess(ctx, fr, level);
-    auto& ps = ctx->pts[ctx->cur];
-    RefineIO io{d_points, d_levels, d_npoints, points_pitch, d_nrefined, (int32_t*)ps.leader.p,
-                (int32_t*)ps.need.p, (int32_t*)ps.nseeds.p, (uint32_t*)ps.seeds.p, (int32_t*)ps.sroot.p};
-    const size_t np = (size_t)fr->nframes * points_pitch;
-    order_after_previous(ctx, {{(const char*)d_points, np * 16}, {(const char*)d_levels, np},
-                               {(const char*)d_nrefined, d_nrefined ? (size_t)fr->nframes * 4 : 0}},
-                         {{(const char*)d_npoints, (size_t)fr->nframes * 4}});
-    MRG_HIP_CHECK(hipStreamWaitEvent(cur_cc(ctx), ctx->ev_pix[level], 0));
-    launch_cc_refine(lb, tables_of(ctx, level), level, io, 0, fr->nframes, cur_cc(ctx));
-    end_op(ctx);
-    MRG_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int mrgingham_amd_chain_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int start_level,
-                              double* d_points, signed char* d_levels, int32_t* d_npoints, int points_pitch) {
-    int rc = validate_frames(ctx, fr);
-    if (rc) return rc;
-    fb_drain(ctx);
-    int w, h;
-    if (level_dims(fr->width, fr->height, start_level, &w, &h))
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "Got an unreasonable image_pyramid_level = %d", start_level);
-    if (fr->nframes == 0) return 0;
-    if (!d_points || !d_levels || !d_npoints || points_pitch <= 0)
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "NULL point buffers");
-    MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    // (option "sparse_refine" 1 = where it pays: the dense response of a small call is cheaper than the longer chain --
-    // measured crossover at 80-100 Mpx per call, e.g. 64 x 1280x960 or 8 x 4096x3072; 2 = always)
-    const bool sparse_pays = ctx->sparse_refine == 2 || (long long)fr->width * fr->height * fr->nframes >= kSparsePaysPixels;
-    const bool sparse_now = ctx->sparse_refine && sparse_pays && start_level >= 1 && start_level <= kRefineLevelsMax &&
-                            !ctx->use_v0 && ctx->cc_lds;
-    if (sparse_now) ctx->sparse_seen = true;
-    if ((rc = choose_sets(ctx, fr))) return rc;
-    for (int L = 0; L <= start_level; ++L)
-        if ((rc = ensure_level(ctx, L, fr->nframes, fr->width, fr->height, points_pitch))) return rc;
-    if ((rc = ensure_points(ctx, fr->nframes, points_pitch))) return rc;
-    if (sparse_now && !ctx->sparse_stat.p) {
-        if ((rc = ensure(ctx, ctx->sparse_stat, 256))) return rc;
-        MRG_HIP_CHECK(hipMemset(ctx->sparse_stat.p, 0, 256));
-    }
-    begin_op(ctx, start_level);
-    auto& ps = ctx->pts[ctx->cur];
-    DetectOut out{(int32_t*)ps.cand_xy.p, points_pitch, (int32_t*)ps.cand_counts.p};
-    out.points = d_points;
-    out.levels = d_levels;
-    out.npoints = d_npoints;
-    out.points_pitch = points_pitch;
-    RefineIO io{d_points, d_levels, d_npoints, points_pitch, nullptr, (int32_t*)ps.leader.p,
-                (int32_t*)ps.need.p, (int32_t*)ps.nseeds.p, (uint32_t*)ps.seeds.p, (int32_t*)ps.sroot.p};
-    {
-        const size_t np = (size_t)fr->nframes * points_pitch;
-        order_after_previous(ctx, {{(const char*)d_points, np * 16}, {(const char*)d_levels, np},
-                                   {(const char*)d_npoints, (size_t)fr->nframes * 4}}, {});
-    }
-    LevelBatch lbs[kMaxLevel + 1];
-    hipEvent_t lev_ev[kMaxLevel + 1] = {};
-    auto note_pending = [&](int L) {
-        if (fr->nframes > ctx->pending_frames[ctx->cur][L]) ctx->pending_frames[ctx->cur][L] = fr->nframes;
-    };
-    if (sparse_now) {
-        // SPARSE REFINEMENT.  The dense schedule computes the response of levels start-1 .. 0 for whole frames and then
-        // looks at it around ~100 points.  Here: every level image in one pass over the frames (pyramid kernel; the
-        // variance windows need them around any peak), the dense response only at the START level (its detection needs
-        // every component), and below it, level by level on the component stream: queue_sparse_levels.
-        // what is timed in this mode (mrgingham_amd_chess_kernel_ms): the kernel that reads the frames, i.e. the launch
-        // that writes the level images (the dominant kernel of a sparse step; 1 B/px read + 0.328 B/px written)
-        hipEvent_t e0 = nullptr;
-        if (ctx->timing) {
-            e0 = timing_event(ctx);
-            hipEventRecord(e0, ctx->pix);
-        }
-        queue_level_images(ctx, fr, start_level, true, true);
-        if (e0) {
-            hipEvent_t em = timing_event(ctx);
-            hipEventRecord(em, ctx->pix);
-            ctx->events.emplace_back(e0, em);
-        }
-        lbs[start_level] = level_batch_of(ctx, fr, start_level);
-        launch_chess_any(ctx, lbs[start_level], tables_of(ctx, start_level), fr->nframes, true, true, ctx->pix, false);
-        hipEvent_t e1 = ctx->ev_pix[start_level];
-        hipEventRecord(e1, ctx->pix);
-        note_pending(start_level);
-        ctx->last_fused = 0;
-        ctx->last_merged = -1;  // (mrgingham_amd_chain_info: a sparse step)
-        MRG_HIP_CHECK(hipStreamWaitEvent(cur_cc(ctx), e1, 0));
-        launch_cc_detect(lbs[start_level], tables_of(ctx, start_level), start_level, out, 0, fr->nframes, cur_cc(ctx));
-        SparseRestore src{out.xy, out.capacity, start_level, nullptr, nullptr};
-        if ((rc = queue_sparse_levels(ctx, fr, start_level, io, src))) return rc;
-        end_op(ctx);
-        MRG_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    // pixel stream.  Frames of whole 16 x 8 blocks (every BASELINE size): level 0 first, its kernel also
-    // writes the level images 1..3 out of the rows it holds in LDS anyway, so the batch is read from HBM
-    // once instead of twice; the small levels follow.  Other shapes: every level image in one pass over
-    // the frames (pyramid kernel), then the responses top-down.
-    lbs[0] = level_batch_of(ctx, fr, 0);
-    const bool fused = ctx->fuse_pyramid && !ctx->use_v0 && start_level >= 1 && ctx->multi_level != 2 &&
-                       chess_pyramid_ok(lbs[0], fr->nframes);
-    queue_level_images(ctx, fr, start_level, !fused);
-    if (fused) {
-        hipEvent_t e0 = nullptr;
-        if (ctx->timing) {
-            e0 = timing_event(ctx);
-            hipEventRecord(e0, ctx->pix);
-        }
-#ifdef MRG_EXPERIMENT
-        if (!((ctx->chess_variant_hot & 32) && launch_chess16_pyramid(lbs[0], tables_of(ctx, 0), pyramid_out_of(ctx, start_level), fr->nframes, ctx->pix)))
-#endif
-            launch_chess_pyramid(lbs[0], tables_of(ctx, 0), pyramid_out_of(ctx, start_level), fr->nframes, ctx->pix, ctx->chess_seg);
-        if (e0) {
-            hipEvent_t e1 = timing_event(ctx);
-            hipEventRecord(e1, ctx->pix);
-            ctx->events.emplace_back(e0, e1);
-            lev_ev[0] = e1;
-        }  // else: the event behind level 1 stands in (the component chain reaches level 0 last anyway)
-        note_pending(0);
-    }
-    // levels 3 (or the top), 2, 1 -- or all of them, level 0 included -- in one launch when the shapes
-    // allow it.  Every hipEventRecord on the pixel stream is a packet of its own between two kernels
-    // (~4 us each in the kernel trace), so a boundary gets ONE: the levels of a merged launch share an
-    // event, and with kernel timing on the timing marks double as the hand-over events.
-    bool merged = false;
-    hipEvent_t before_l0 = nullptr;  // timing mode: an event recorded right before the level-0 launch, if there is one
-    const int top = start_level < 3 ? start_level : 3;
-    const int lowest = ctx->multi_level == 2 ? 0 : 1;  // lowest level inside the merged launch
-    if (top - lowest >= 1 && !ctx->use_v0 && ctx->multi_level) {
-        LevelBatch mlb[4];
-        CompTables mt[4];
-        int n = 0;
-        for (int L = lowest; L <= top; ++L, ++n) {  // largest level first
-            mlb[n] = level_batch_of(ctx, fr, L);
-            mt[n] = tables_of(ctx, L);
-        }
-        // decided BEFORE anything is queued: a level must not be appended to its hot list twice
-        if (chess_multi_ok(mlb, n, fr->nframes)) {
-            for (int L = start_level; L > top; --L) {
-                lbs[L] = queue_level_chess(ctx, fr, L);
-                lev_ev[L] = ctx->ev_pix[L];
-            }
-            hipEvent_t e0 = nullptr;
-            if (lowest == 0 && ctx->timing) {
-                e0 = timing_event(ctx);
-                hipEventRecord(e0, ctx->pix);
-            }
-            merged =
-#ifdef MRG_EXPERIMENT
-                ((ctx->chess_variant_hot & 16) && launch_chess16_multi(mlb, mt, n, fr->nframes, ctx->pix)) ||
-#endif
-                launch_chess_multi(mlb, mt, n, fr->nframes, ctx->pix, ctx->chess_seg);
-            if (merged) {
-                hipEvent_t em = (ctx->timing && !fused) ? timing_event(ctx) : ctx->ev_pix[top];
-                hipEventRecord(em, ctx->pix);
-                if (e0) ctx->events.emplace_back(e0, em);  // all levels in one launch: that launch is what is timed
-                else if (ctx->timing) before_l0 = em;
-                for (int L = top; L >= lowest; --L) {
-                    lbs[L] = mlb[L - lowest];
-                    lev_ev[L] = em;
-                    note_pending(L);
-                }
-            } else if (e0) {
-                ctx->event_pool.push_back(e0);
-            }
-        }
-    }
-    for (int L = merged ? lowest - 1 : start_level; L >= 1; --L) {
-        lbs[L] = queue_level_chess(ctx, fr, L);
-        lev_ev[L] = ctx->ev_pix[L];
-    }
-    if (fused) {
-        if (!lev_ev[0]) lev_ev[0] = lev_ev[1];
-    } else if (!(merged && lowest == 0)) {  // level 0 on its own
-        const CompTables t0 = tables_of(ctx, 0);
-        if (ctx->timing) {
-            hipEvent_t e0 = before_l0;
-            if (!e0) {
-                e0 = timing_event(ctx);
-                hipEventRecord(e0, ctx->pix);
-            }
-            launch_chess_any(ctx, lbs[0], t0, fr->nframes, true, true, ctx->pix, false);
-            hipEvent_t e1 = timing_event(ctx);
-            hipEventRecord(e1, ctx->pix);
-            ctx->events.emplace_back(e0, e1);
-            lev_ev[0] = e1;
-        } else {
-            launch_chess_any(ctx, lbs[0], t0, fr->nframes, true, true, ctx->pix, false);
-            hipEventRecord(ctx->ev_pix[0], ctx->pix);
-            lev_ev[0] = ctx->ev_pix[0];
-        }
-        note_pending(0);
-    }
-    ctx->last_fused = fused;
-    ctx->last_merged = merged ? top - lowest + 1 : 0;
-    // component stream: detect at the top (mrgingham.cc:50), candidates -> corners
-    // (find_grid.cc:353-354), then refine level by level (mrgingham.cc:87-99)
-    // which pixel-stream event a level's search waits for: level 0 runs LAST on the pixel stream in the
-    // classic order (cc_schedule 1 holds levels 1 and 0 back until then, 2 holds everything back) and
-    // FIRST in the fused order (then level 1 is the last)
-    auto gate_of = [&](int L) {
-        if (fused) return lev_ev[ctx->cc_schedule == 2 ? 1 : (L > 1 ? L : 1)];
-        return lev_ev[(ctx->cc_schedule == 1 && L <= 1) || ctx->cc_schedule == 2 ? 0 : L];
-    };
-    const bool no_cc = (ctx->cc_lds & 128) != 0;  // timing experiment only (tools/interference_ab.py): pixel kernels alone
-    MRG_HIP_CHECK(hipStreamWaitEvent(cur_cc(ctx), gate_of(start_level), 0));
-    if (!no_cc)
-        launch_cc_detect(lbs[start_level], tables_of(ctx, start_level), start_level, out, 0, fr->nframes, cur_cc(ctx));
-    for (int L = start_level - 1; L >= 0; --L) {
-        MRG_HIP_CHECK(hipStreamWaitEvent(cur_cc(ctx), gate_of(L), 0));
-        if (!no_cc) launch_cc_refine(lbs[L], tables_of(ctx, L), L, io, 0, fr->nframes, cur_cc(ctx));
-    }
-    end_op(ctx);
-    MRG_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int mrgingham_amd_cc_on_response_batch(mrgingham_amd_ctx* ctx, const int16_t* d_response,
-                                       const uint8_t* d_level_image, int nframes, int w, int h, int level,
-                                       int32_t* d_xy, int capacity_per_frame, int32_t* d_counts,
-                                       double* d_points, signed char* d_levels, const int32_t* d_npoints,
-                                       int points_pitch, int32_t* d_nrefined) {
-    if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
-    fb_drain(ctx);
-    const bool detect = d_xy != nullptr, refine = d_points != nullptr;
-    if (detect == refine) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "exactly one of d_xy (detect) and d_points (refine)");
-    if (nframes < 0 || w < 0 || h < 0 || w > 32767 || h > 32767 || level < 0 || level > kMaxLevel ||
-        (nframes > 0 && (!d_response || !d_level_image)))
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad response batch descriptor");
-    if (detect && (!d_counts || capacity_per_frame < 0)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "NULL outputs");
-    if (refine && (!d_levels || !d_npoints || points_pitch <= 0))
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "NULL point buffers");
-    if (nframes == 0) return 0;
-    MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    // the level-0 scratch of a w x h "frame": the response is the level image's as far as the
-    // component search is concerned; `level` only enters through the coordinate scale
-    int rc;
-    const int pitch = refine ? points_pitch : 0;
-    if ((rc = ensure_level(ctx, 0, nframes, w, h, pitch))) return rc;
-    if (refine && (rc = ensure_points(ctx, nframes, points_pitch))) return rc;
-    begin_op(ctx, 0);
-    const LevelScratch& L = cur_levels(ctx)[0];
-    LevelBatch lb;
-    lb.nframes = nframes;
-    lb.w = w;
-    lb.h = h;
-    lb.img = d_level_image;
-    lb.img_pitch = (long long)w * h;
-    lb.img_stride = w;
-    lb.resp = (int16_t*)L.resp.p;
-    lb.resp_pitch = (long long)w * h;
-    const CompTables t = tables_of(ctx, 0);
-    launch_hot_from_response(d_response, lb, t, 0, nframes, ctx->pix);
-    hipEventRecord(ctx->ev_pix[0], ctx->pix);
-    if (nframes > ctx->pending_frames[ctx->cur][0]) ctx->pending_frames[ctx->cur][0] = nframes;
-    if (detect) {
-        order_after_previous(ctx, {{(const char*)d_xy, (size_t)nframes * capacity_per_frame * 8},
-                                   {(const char*)d_counts, (size_t)nframes * 4}}, {});
-        MRG_HIP_CHECK(hipStreamWaitEvent(cur_cc(ctx), ctx->ev_pix[0], 0));
-        launch_cc_detect(lb, t, level, DetectOut{d_xy, capacity_per_frame, d_counts}, 0, nframes, cur_cc(ctx));
-    } else {
-        auto& ps = ctx->pts[ctx->cur];
-        RefineIO io{d_points, d_levels, d_npoints, points_pitch, d_nrefined, (int32_t*)ps.leader.p,
-                    (int32_t*)ps.need.p, (int32_t*)ps.nseeds.p, (uint32_t*)ps.seeds.p, (int32_t*)ps.sroot.p};
-        const size_t np = (size_t)nframes * points_pitch;
-        order_after_previous(ctx, {{(const char*)d_points, np * 16}, {(const char*)d_levels, np},
-                                   {(const char*)d_nrefined, d_nrefined ? (size_t)nframes * 4 : 0}},
-                             {{(const char*)d_npoints, (size_t)nframes * 4}});
-        MRG_HIP_CHECK(hipStreamWaitEvent(cur_cc(ctx), ctx->ev_pix[0], 0));
-        launch_cc_refine(lb, t, level, io, 0, nframes, cur_cc(ctx));
-    }
-    end_op(ctx);
-    MRG_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-}  // extern "C"

@@ -410,18 +410,13 @@ static int fb_host_end(mrgingham_amd_ctx* ctx, mrgingham_amd_ctx::BoardsJob& job
         char* const d_lv = d_pts + fb_align(pb);
         char* const d_np = d_lv + fb_align(lb);
         char* const d_pts0 = (char*)job.d_pts0.p;
-        const bool sparse = ctx->cc_lds && !ctx->use_v0 && top <= kRefineLevelsMax &&
-                            (ctx->sparse_refine == 2 ||
-                             (ctx->sparse_refine == 1 && (long long)fr->width * fr->height * B >= kSparsePaysPixels));
+        const bool sparse = sparse_applies(ctx, top, (long long)fr->width * fr->height * B);  // (top >= 1: nref > 0)
         hipEventRecord(job.ev_b0, cc);
         hipError_t e = hipMemcpyAsync(d_pts, pin.pts, fb_align(pb) + fb_align(lb) + (size_t)B * 4, hipMemcpyHostToDevice, cc);
         if (e == hipSuccess && sparse)  // (only the dense repeat of a sparse refinement goes back to them)
             e = hipMemcpyAsync(d_pts0, d_pts, fb_align(pb) + lb, hipMemcpyDeviceToDevice, cc);
         if (e == hipSuccess) {
-            auto& ps = ctx->pts[job.set];
-            RefineIO io{(double*)d_pts, (signed char*)d_lv, (const int32_t*)d_np, N, nullptr,
-                        (int32_t*)ps.leader.p, (int32_t*)ps.need.p, (int32_t*)ps.nseeds.p, (uint32_t*)ps.seeds.p,
-                        (int32_t*)ps.sroot.p};
+            const RefineIO io = refine_io_of(ctx, job.set, (double*)d_pts, (signed char*)d_lv, (const int32_t*)d_np, N, nullptr);
             const SparseRestore src{nullptr, 0, 0, (const double*)d_pts0, (const signed char*)(d_pts0 + fb_align(pb))};
             rc = queue_sparse_levels(ctx, fr, top, io, src, !sparse);
             job.top = top;
@@ -554,7 +549,7 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
     const int nlev = image_pyramid_level >= 0 ? 1 : 3;
     const int cap = 4 * N + 64;  // candidates kept per frame for the grid finder
     // the refinement takes the sparse schedule where it pays: such a context keeps three scratch sets (choose_sets)
-    if (ctx->sparse_refine && top >= 1 && ctx->cc_lds && !ctx->use_v0) ctx->sparse_seen = true;
+    if (sparse_possible(ctx, top)) ctx->sparse_seen = true;
     {   // a change of the rotation (another batch shape) synchronises and may free a set: no job may be in flight then
         const double per_set = 5.0 * (double)B * fr->width * fr->height;
         const double mx = per_set > ctx->max_set_bytes ? per_set : ctx->max_set_bytes;
@@ -638,27 +633,13 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
     // part A: level images of every level up to the top in one pass (the refinement's variance windows and cells read
     // them too), the responses of the levels searched, their candidates
     queue_level_images(ctx, fr, top, true);
-    LevelBatch lbs[3];
-    bool merged = false;
-    if (job.nlev >= 2 && !ctx->use_v0 && ctx->multi_level) {
-        LevelBatch mlb[3];
-        CompTables mt[3];
-        for (int k = 0; k < job.nlev; ++k) {  // largest level first
-            mlb[k] = level_batch_of(ctx, fr, job.levs[job.nlev - 1 - k]);
-            mt[k] = tables_of(ctx, job.levs[job.nlev - 1 - k]);
-        }
-        if (chess_multi_ok(mlb, job.nlev, B) && launch_chess_multi(mlb, mt, job.nlev, B, ctx->pix, ctx->chess_seg)) {
-            merged = true;
-            for (int k = 0; k < job.nlev; ++k) lbs[job.nlev - 1 - k] = mlb[k];
-            hipEventRecord(ctx->ev_pix[top], ctx->pix);
-            for (int li = 0; li < job.nlev; ++li)
-                if (B > ctx->pending_frames[ctx->cur][job.levs[li]]) ctx->pending_frames[ctx->cur][job.levs[li]] = B;
-        }
-    }
-    if (!merged)
-        for (int li = 0; li < job.nlev; ++li) lbs[li] = queue_level_chess(ctx, fr, job.levs[li]);
+    const int lowest = job.levs[job.nlev - 1];
+    LevelBatch by_level[kMaxLevel + 1], lbs[3];
+    hipEvent_t lev_ev[kMaxLevel + 1] = {};
+    queue_chess_levels(ctx, fr, top, lowest, false, by_level, lev_ev, nullptr);  // (no kernel timing around these)
+    for (int li = 0; li < job.nlev; ++li) lbs[li] = by_level[job.levs[li]];
     hipStream_t cc = cur_cc(ctx);
-    hipError_t e = hipStreamWaitEvent(cc, ctx->ev_pix[merged ? top : job.levs[job.nlev - 1]], 0);
+    hipError_t e = hipStreamWaitEvent(cc, lev_ev[lowest], 0);  // the last of them on the pixel stream
     {   // the candidates of every level searched in this pass: one grid per kernel, not one per level
         CompTables dts[3];
         DetectOut douts[3];

@@ -1,8 +1,9 @@
 // The context of libmrgingham_amd.so and the helpers that more than one of its host files calls.  Internal: not
 // installed, not part of include/.  The host side is cut by concern: api.hip (context lifetime, options, scratch sets,
-// status words, the _batch entry points), multi.hip (several devices), reference.hip (the reference's own C symbols
-// over one frame), boards.hip (find_boards: the level search, synchronous and pipelined), blobs_api.hip (the blob
-// detector and the circle-grid finder over a batch).
+// status words, the pixel-only _batch entry points), chain.hip (the detector's stream scheduling: detect / refine /
+// chain calls, kernel timing, the sparse schedule), multi.hip (several devices), reference.hip (the reference's own C
+// symbols over one frame), boards.hip (find_boards: the level search, synchronous and pipelined), blobs_api.hip (the
+// blob detector and the circle-grid finder over a batch).
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -150,7 +151,7 @@ struct mrgingham_amd_ctx {
     int multi_level = 1;
     int last_fused = 0, last_merged = 0;  // mrgingham_amd_chain_info
     // option "sparse_refine": chain_batch computes the response of the levels BELOW the start level only in the cells
-    // around the points it refines there (chain_batch_sparse)
+    // around the points it refines there (chain.hip: chain_pixels_sparse, queue_sparse_levels)
     int sparse_refine = 1;     // (default: where it pays)
     bool sparse_seen = false;  // a chain has taken the sparse schedule (choose_sets)
     mrg::DevBuf sparse_stat;   // [0]: frames the sparse schedule reported and the library repeated densely (mrgingham_amd_sparse_fallbacks)
@@ -169,7 +170,8 @@ struct mrgingham_amd_ctx {
     mrg::DevBuf aux_img, io_frame, io_out, io_counts;
     void* io_res_pin = nullptr;  // page-locked: count + first candidates of the single-frame detector
     // page-locked copies of the sets' status words ([level][counters_nf], what mrgingham_amd_sync inspects): they follow every
-    // op on its component stream (end_op), so that the sync behind it reads host memory instead of making a blocking copy
+    // op on its component stream (end_op), so that the sync behind it reads host memory instead of making a blocking copy;
+    // allocated with counters2 (ensure_level_set): status_pin_words is what counters_nf implies, or 0 where that failed
     int32_t* status_pin[kMaxSets] = {};
     size_t status_pin_words[kMaxSets] = {};
     bool status_copied[kMaxSets] = {};  // the LAST op on the set left its words in status_pin
@@ -251,7 +253,19 @@ struct mrgingham_amd_ctx {
 
 namespace mrg {
 
+// THE SPARSE SCHEDULE (option "sparse_refine"; chain_batch and the refinement of find_boards).  1 = where it pays: the
+// dense response of a small call is cheaper than the longer chain -- measured crossover at 80-100 Mpx per call, e.g.
+// 64 x 1280x960 or 8 x 4096x3072; 2 = always.
 constexpr long long kSparsePaysPixels = 96ll << 20;  // option "sparse_refine" 1: calls with at least this many frame pixels
+// this context can take it for points that start at level `top` (such a context keeps three scratch sets: choose_sets) ...
+static inline bool sparse_possible(const mrgingham_amd_ctx* ctx, int top) {
+    return ctx->sparse_refine && top >= 1 && ctx->cc_lds && !ctx->use_v0;
+}
+// ... and a call over `pixels` frame pixels in all does take it
+static inline bool sparse_applies(const mrgingham_amd_ctx* ctx, int top, long long pixels) {
+    return sparse_possible(ctx, top) && top <= kRefineLevelsMax && (ctx->sparse_refine == 2 || pixels >= kSparsePaysPixels);
+}
+constexpr int kCellsPerPoint = 9;  // sparse refinement: distinct cells the 3 x 3 seeds of one point can mark (2 x 2 each, one pixel apart)
 
 // api.hip: errors, buffers, level scratch
 int fail(mrgingham_amd_ctx* ctx, int code, const char* fmt, ...);
@@ -266,17 +280,22 @@ int ensure_level(mrgingham_amd_ctx* ctx, int level, int nframes, int W, int H, i
 int ensure_points(mrgingham_amd_ctx* ctx, int nframes, int pitch);
 int queue_preprocess16(mrgingham_amd_ctx* ctx, const uint16_t* d_frames, int64_t frame_pitch, int nframes, int width, int height,
                        int stride, int do_clahe, int blur_radius, uint8_t* d_out, hipStream_t s);
+int harvest_status(mrgingham_amd_ctx* ctx, int set, int level, int* rc, bool quiet = false);
+void launch_one_level_image(const mrgingham_amd_frames* fr, int level, uint8_t* out, int w, int h, hipStream_t s);
 
-// api.hip: the scratch-set rotation of a call, its status words, its pixel-stream and component-stream work
+// chain.hip: the scratch-set rotation of a call, its pixel-stream and component-stream work
 void begin_op(mrgingham_amd_ctx* ctx, int max_level);
 void order_after_previous(mrgingham_amd_ctx* ctx, std::initializer_list<mrgingham_amd_ctx::Span> w,
                           std::initializer_list<mrgingham_amd_ctx::Span> r);
 void end_op(mrgingham_amd_ctx* ctx);
-int harvest_status(mrgingham_amd_ctx* ctx, int set, int level, int* rc, bool quiet = false);
+void launch_chess_any(mrgingham_amd_ctx* ctx, const LevelBatch& lb, const CompTables& t, int n, bool clamp, bool hot,
+                      hipStream_t s, bool time_it);
 void queue_level_images(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int max_level, bool levels_1_to_3 = true,
                         bool gentle = false);
 LevelBatch level_batch_of(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level);
 LevelBatch queue_level_chess(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level);
+int queue_chess_levels(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int hi, int lo, bool merge_l0, LevelBatch* lbs,
+                       hipEvent_t* lev_ev, hipEvent_t* l0_mark);
 int queue_sparse_levels(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int top, RefineIO io,
                         const SparseRestore& restore, bool dense_only = false);
 
@@ -311,6 +330,19 @@ static inline int32_t* status_of(mrgingham_amd_ctx* ctx, int level) {
 }
 static inline int32_t* path_of(mrgingham_amd_ctx* ctx, int level) {
     return (int32_t*)ctx->counters2[ctx->cur].p + (size_t)(2 * (kMaxLevel + 1) + level) * ctx->counters_nf;
+}
+
+// this call leaves status words of `nframes` frames at `level`: the next sync looks at them
+static inline void note_pending(mrgingham_amd_ctx* ctx, int level, int nframes) {
+    int& n = ctx->pending_frames[ctx->cur][level];
+    if (nframes > n) n = nframes;
+}
+// a refinement of the caller's points over the point scratch of `set`
+static inline RefineIO refine_io_of(mrgingham_amd_ctx* ctx, int set, double* points, signed char* levels, const int32_t* npoints,
+                                    int pitch, int32_t* nrefined) {
+    auto& ps = ctx->pts[set];
+    return RefineIO{points, levels, npoints, pitch, nrefined, (int32_t*)ps.leader.p, (int32_t*)ps.need.p,
+                    (int32_t*)ps.nseeds.p, (uint32_t*)ps.seeds.p, (int32_t*)ps.sroot.p};
 }
 
 static inline CompTables tables_of(mrgingham_amd_ctx* ctx, int level) {

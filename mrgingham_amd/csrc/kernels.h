@@ -145,7 +145,7 @@ void launch_sparse_cells(const LevelBatch& lb, const CompTables& t, int level, c
                          int32_t* cell_cnt, int list_pitch, int frame0, int nframes, hipStream_t s, int32_t* cnt_all, int nframes_all);
 constexpr int kLdsPathSparse = 1024;  // CompTables::lds_path bit: the dense response only holds those cells
 // Sparse refinement, the frames it could not take (kStatusSparse in their level-0 status word): REPEATED DENSELY,
-// on the device, in three small launches (api.hip, queue_sparse_levels):
+// on the device, in three small launches (chain.hip, queue_sparse_levels):
 //   launch_sparse_flag_list          the frames as a list (list[0] = how many, list[1 ..] = which);
 //   launch_chess / launch_chess_multi with CompTables::only = that list: their dense responses + hot lists;
 //   launch_cc_refine_flagged_levels  per listed frame: its points back to what they were before the first sparse

@@ -116,7 +116,7 @@ def test_shipped_library_has_no_experiment_hooks():
     assert b"MRGINGHAM_AMD_DEVICE" in blob                  # the one variable it does read
     csrc = os.path.join(here, "mrgingham_amd", "csrc")
     srcs = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")))
-    assert {"api.hip", "boards.hip", "chess.hip", "cc.hip"} <= set(srcs)
+    assert {"api.hip", "chain.hip", "boards.hip", "chess.hip", "cc.hip"} <= set(srcs)
     for src in srcs:
         text = open(os.path.join(csrc, src)).read()
         lines = text.split("\n")

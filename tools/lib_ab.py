@@ -1,7 +1,8 @@
 """A/B of whole-library builds on the bench workload: python tools/lib_ab.py a.so b.so ... [--rounds N] [--gridn 10]
 One child process per library and round (MRGINGHAM_AMD_LIB), rounds interleaved; prints per library the median step
 time of the pipelined chain (64 x 4096x3072), the level-0 launch inside it, the level-0 kernel alone (plain response
-kernel, clamp, no hot list) and a checksum of the corner lists (must agree between builds)."""
+kernel, clamp, no hot list) and a checksum of the corner lists (must agree between builds); behind the two chain
+medians [min .. max] of the rounds."""
 import sys, os, subprocess, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "child":
@@ -70,5 +71,6 @@ for r in range(rounds):
 for a, rs in acc.items():
     if not rs: continue
     med = lambda k: sorted(r[k] for r in rs)[len(rs) // 2]
-    print(f"{a:44s} step {med('step_ms'):.4f} ms  L0 in chain {med('l0_us'):6.1f} us  plain alone {med('alone_us'):6.1f} us  "
-          f"chk {rs[0]['chk']:.6f} rchk {rs[0]['rchk']} npts {rs[0]['npts']}", flush=True)
+    rng = lambda k: f"[{min(r[k] for r in rs):.4f} .. {max(r[k] for r in rs):.4f}]"   # the spread of the rounds
+    print(f"{a:44s} step {med('step_ms'):.4f} ms {rng('step_ms')}  L0 in chain {med('l0_us'):6.1f} us {rng('l0_us')}  "
+          f"plain alone {med('alone_us'):6.1f} us  chk {rs[0]['chk']:.6f} rchk {rs[0]['rchk']} npts {rs[0]['npts']}", flush=True)
