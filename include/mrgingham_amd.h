@@ -38,7 +38,10 @@ extern "C" {
  *      the caller's current HIP device; _gather_rccl needs no RCCL header or library at build time and never loads a second RCCL.
  *      Later, additive: mrgingham_amd_preprocess16_batch (16-bit frames on the device; option "preprocess_fused" covers it).
  *      Later, additive: mrgingham_amd_blobs_batch, _find_circle_grids_batch, _blobs_stats (the blob path over a batch on the
- *      device); option "blob_chunk_frames". */
+ *      device); option "blob_chunk_frames".
+ *      Later, additive: mrgingham_amd_jpeg_coefficients, _jpeg_idct_batch, _read_jpegs_batch (baseline JPEG: entropy decode on
+ *      the host, inverse DCT on the device); option "jpeg_chunk_frames"; mrgingham_amd_read_image and the file entry points
+ *      read baseline JPEG. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -320,7 +323,7 @@ int mrgingham_amd_cc_on_response_batch(mrgingham_amd_ctx* ctx, const int16_t* d_
 
 /* C faces of find_chessboard_corners_from_image_file (find_chessboard_corners.hh:32-44, .cc:623-648)
  * and find_chessboard_from_image_file (mrgingham.hh:77-83, mrgingham.cc:145-170): the image file is
- * decoded (binary PGM or non-interlaced PNG; the reference uses cv::imread) and handed to the array
+ * decoded (binary PGM, non-interlaced PNG or baseline JPEG; the reference uses cv::imread) and handed to the array
  * functions above.  false when the file cannot be read or nothing is found. */
 bool find_chessboard_corners_from_image_file_C(const char* filename, int image_pyramid_level, bool debug,
                                                bool (*add_points)(int* xy, int N, double scale, void* cookie),
@@ -329,7 +332,8 @@ bool find_chessboard_from_image_file_C(const char* filename, const int gridn, in
                                        bool (*add_points)(double* xy, int N, void* cookie), void* cookie);
 
 /* The image decoder behind the two functions above and the command-line tool, on its own (host only, no
- * device needed): binary PGM (8 / 16 bit) and non-interlaced PNG.  `out` (may be NULL: sizes only)
+ * device needed): binary PGM (8 / 16 bit), non-interlaced PNG and baseline JPEG (see
+ * mrgingham_amd_jpeg_coefficients for what is accepted).  `out` (may be NULL: sizes only)
  * receives width*height grey bytes.  16-bit samples: cli_scaling = 0 keeps the high byte, what
  * cv::imread(IMREAD_GRAYSCALE) gives the file entry points; 1 rescales by 255/65535 with rounding, what
  * the CLI's convertTo does (mrgingham-from-image.cc:85-92).  Returns 0; -1 unreadable, unsupported or
@@ -337,6 +341,44 @@ bool find_chessboard_from_image_file_C(const char* filename, const int gridn, in
  * 32767 are rejected); -2 out_capacity too small (sizes are still reported). */
 int mrgingham_amd_read_image(const char* filename, int cli_scaling, uint8_t* out, size_t out_capacity, int* width,
                              int* height, int* depth);
+
+/* Baseline JPEG, first half (host only, no device needed): the marker parse and the Huffman decode of a file held in
+ * memory.  What cv::imread(IMREAD_GRAYSCALE) gives for a grey or YCbCr file is the luma plane after libjpeg's default
+ * integer inverse DCT, so only luma is kept: coef (may be NULL: sizes only) receives the quantised coefficients as int16
+ * [blocks_h][blocks_w][64] -- row-major inside a block, blocks in raster order --, quant (may be NULL) the 64 entries of
+ * the luma table in the same order.  blocks_w / blocks_h are the luma block counts padded to whole MCUs (4:2:0 at
+ * 31 x 33: 4 x 6).  Accepted: SOF0 / SOF1 (sequential Huffman, 8 bit), 1 component or 3 taken as YCbCr with luma first and
+ * at the frame's maximum sampling factors, one scan, 8- / 16-bit DQT, DHT / DRI anywhere before SOS, restart markers in
+ * sequence exactly at the interval, APPn / COM skipped, EXIF orientation ignored (IMREAD_IGNORE_ORIENTATION).
+ * Unreadable: progressive, arithmetic, lossless, 12 bit, 4 components, Adobe transform 0 (RGB), several scans, DNL /
+ * height 0, sides above 32767, and ANY malformed stream (truncated data is not padded).  Returns 0; -1 unreadable (never
+ * throws, never reads or writes out of bounds on a crafted file); -2 coef_capacity (in elements) too small (sizes and
+ * quant are still reported). */
+int mrgingham_amd_jpeg_coefficients(const uint8_t* data, size_t nbytes, int16_t* coef, size_t coef_capacity,
+                                    uint16_t* quant, int* width, int* height, int* blocks_w, int* blocks_h);
+
+/* Baseline JPEG, second half: dequantisation and the 8x8 inverse DCT of nframes frames on the device, bit for bit what
+ * mrgingham_amd_read_image computes on the host (libjpeg's default integer transform; sums and products modulo 2^32 on
+ * crafted input).  d_coef: frame f at d_coef + f*coef_pitch (ELEMENTS), laid out as above with the given blocks_w /
+ * blocks_h (blocks_w*8 >= width, blocks_h*8 >= height, coef_pitch >= blocks_w*blocks_h*64; d_coef 16-byte aligned and
+ * coef_pitch a multiple of 8).  d_quant: nframes x 64.  d_out: frame f row y at d_out + f*frame_pitch + y*stride; only
+ * the width x height pixels are written, the bytes between width and stride stay untouched.  Asynchronous on `stream`
+ * (NULL = default).  Arguments are checked like mrgingham_amd_preprocess_batch's (MRGINGHAM_AMD_ERR_ARG, nothing
+ * written). */
+int mrgingham_amd_jpeg_idct_batch(mrgingham_amd_ctx* ctx, const int16_t* d_coef, int64_t coef_pitch,
+                                  const uint16_t* d_quant, int nframes, int width, int height, int blocks_w,
+                                  int blocks_h, uint8_t* d_out, int64_t frame_pitch, int stride, void* stream);
+
+/* nfiles baseline JPEG files of ONE size straight into device frames (layout as d_out above): nthreads host threads
+ * (<= 0: all cores, at most 32) entropy-decode a chunk of files into page-locked staging while the chunk before it
+ * uploads and runs mrgingham_amd_jpeg_idct_batch; the decoded pixels never exist on the host.  h_status[f]: 0 decoded,
+ * -1 unreadable / unsupported / malformed, -2 a JPEG of another size; the frame of a failed file is zero-filled.
+ * SYNCHRONOUS: d_out is complete on return.  Returns MRGINGHAM_AMD_OK also when files failed.  Completes the
+ * find_boards jobs in flight first and restores the caller's HIP device.  The two device coefficient buffers stay within
+ * 1 GiB of context scratch (12 MP: ~20 frames each; option "jpeg_chunk_frames"). */
+int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width,
+                                   int height, uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads,
+                                   int32_t* h_status);
 
 /* The same preprocessing for one HOST image (out: dense width x height bytes, host): what the Python
  * recipe of find_board.docstring:8-10 does with cv2 before find_board.  Uses the calling thread's
@@ -523,6 +565,8 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         by the library, on the device, inside the same call (mrgingham_amd_sparse_fallbacks counts them).
  *   "blob_chunk_frames"   test hook: 0 (default) = mrgingham_amd_blobs_batch / _find_circle_grids_batch cut a batch into chunks
  *                         by their scratch budget; n > 0 = at most n frames per chunk.  Results never depend on it.
+ *   "jpeg_chunk_frames"   test hook: 0 (default) = mrgingham_amd_read_jpegs_batch cuts its files into chunks by its scratch
+ *                         budget; n > 0 = at most n files per chunk.  Results never depend on it.
  *   "find_boards_pipeline" 1 (default): mrgingham_amd_find_boards_batch / _submit / _collect as described there; 0: the
  *                         synchronous schedule (one level at a time for the whole batch, dense refinement) -- same results
  *   "chess_seg", "chess16_seg"  rows per workgroup of the ChESS kernels of THIS context (chess_v1* / chess_v16; 0 = cost model,

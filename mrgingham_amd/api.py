@@ -107,8 +107,35 @@ def refine_points(points, levels, image, image_pyramid_level):
     return pts, lv, n
 
 
+def jpeg_coefficients(data):
+    """Marker parse + Huffman decode of a baseline JPEG held in memory (host only): -> (coef int16 [bh, bw, 64], quant
+    uint16 [64], (height, width)) -- the quantised luma coefficients, row-major inside a block, blocks in raster order and
+    padded to whole MCUs, and the luma table in the same order (what Detector.jpeg_idct takes).  None when the data is
+    not a JPEG this library reads (mrgingham_amd_jpeg_coefficients: progressive, arithmetic, multi-scan, malformed, ...)."""
+    L = _lib.lib()
+    buf = bytes(data)
+    w, h, bw, bh = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    quant = np.zeros(64, dtype=np.uint16)
+    sizes = (ctypes.byref(w), ctypes.byref(h), ctypes.byref(bw), ctypes.byref(bh))
+    if L.mrgingham_amd_jpeg_coefficients(buf, len(buf), None, 0, quant.ctypes.data, *sizes) != 0:
+        return None
+    coef = np.empty((bh.value, bw.value, 64), dtype=np.int16)
+    if L.mrgingham_amd_jpeg_coefficients(buf, len(buf), coef.ctypes.data, coef.size, quant.ctypes.data, *sizes) != 0:
+        return None
+    return coef, quant, (h.value, w.value)
+
+
+def jpeg_coefficients_size(data):
+    """(height, width) of a baseline JPEG held in memory, from its header alone; None when it is not one this library reads."""
+    buf = bytes(data)
+    w, h = ctypes.c_int(), ctypes.c_int()
+    if _lib.lib().mrgingham_amd_jpeg_coefficients(buf, len(buf), None, 0, None, ctypes.byref(w), ctypes.byref(h), None, None) != 0:
+        return None
+    return h.value, w.value
+
+
 def read_image(filename, cli_scaling=False):
-    """Decode a binary PGM or non-interlaced PNG to uint8 [H, W] with the library's own decoder (host only).
+    """Decode a binary PGM, non-interlaced PNG or baseline JPEG to uint8 [H, W] with the library's own decoder (host only).
     16-bit files: the high byte (cv::imread(IMREAD_GRAYSCALE)) or, with cli_scaling, the CLI's
     convertTo(255/65535).  None when the file is unreadable, unsupported or malformed."""
     L = _lib.lib()
@@ -608,6 +635,57 @@ class Detector:
             if counts.max() <= cap:
                 return [xy[f, :counts[f]].copy() for f in range(B)]
             cap = self._blobs_cap = int(counts.max())   # (more keypoints than guessed: again, sized to the largest; remembered)
+
+    def jpeg_idct(self, coef, quant, height, width, out=None):
+        """Dequantisation + inverse DCT of entropy-decoded JPEG frames on the device (mrgingham_amd_jpeg_idct_batch), on
+        torch's current stream: coef int16 [B, bh, bw, 64] and quant uint16 [B, 64] device tensors as jpeg_coefficients
+        gives them per frame -> uint8 [B, height, width], the bytes read_image gives for the file.  `out`: a uint8
+        [B, height, >= width] device tensor (unit column stride) to write into; what lies beyond `width` is not touched."""
+        t = self.torch
+        if not (coef.is_cuda and coef.dtype == t.int16 and coef.dim() == 4 and coef.shape[3] == 64 and coef.is_contiguous()):
+            raise ValueError("jpeg_idct: coef is a contiguous int16 [B,bh,bw,64] tensor on the device")
+        B, bh, bw, _ = coef.shape
+        if not (quant.is_cuda and quant.dtype in (t.uint16, t.int16) and tuple(quant.shape) == (B, 64) and quant.is_contiguous()):
+            raise ValueError("jpeg_idct: quant is a contiguous uint16 [B,64] tensor on the device")
+        if out is None:
+            out = t.empty((B, height, width), dtype=t.uint8, device=coef.device)
+        if not (out.is_cuda and out.dtype == t.uint8 and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
+                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
+            raise ValueError("jpeg_idct: out is a uint8 [B,height,>=width] tensor on the device with unit column stride")
+        stream = t.cuda.current_stream(coef.device).cuda_stream
+        self._check(self.L.mrgingham_amd_jpeg_idct_batch(
+            self.ctx, coef.data_ptr(), bh * bw * 64, quant.data_ptr(), B, int(width), int(height), bw, bh, out.data_ptr(),
+            out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+        return out[:, :, :width]
+
+    def read_jpegs(self, paths, nthreads=0):
+        """Baseline JPEG files of one size straight into device frames (mrgingham_amd_read_jpegs_batch): `nthreads` host
+        threads (0: all cores, at most 32) entropy-decode, the device runs the inverse DCT; the decoded pixels never exist
+        on the host.  -> (frames uint8 [B,H,W] on the device, status int32 [B] numpy: 0 decoded, -1 unreadable /
+        unsupported / malformed, -2 a JPEG of another size; failed frames are zero).  The size is that of the first file
+        whose header parses (none does: frames are [B,0,0]).  Synchronous."""
+        t = self.torch
+        names = [os.fsencode(p) for p in paths]
+        B = len(names)
+        status = np.full((B,), -1, dtype=np.int32)
+        H = W = 0
+        for name in names:
+            try:
+                with open(name, "rb") as f:
+                    head = jpeg_coefficients_size(f.read())
+            except OSError:
+                head = None
+            if head is not None:
+                H, W = head
+                break
+        frames = t.zeros((B, H, W), dtype=t.uint8, device=self.device)
+        if B == 0 or H == 0:
+            return frames, status
+        arr = (ctypes.c_char_p * B)(*names)
+        t.cuda.current_stream(self.device).synchronize()
+        self._check(self.L.mrgingham_amd_read_jpegs_batch(self.ctx, arr, B, W, H, frames.data_ptr(), H * W, W, int(nthreads),
+                                                          status.ctypes.data))
+        return frames, status
 
     BLOBS_STATS = ("calls", "chunks", "nodes", "contours", "points", "device_ms", "host_ms", "frames")
 

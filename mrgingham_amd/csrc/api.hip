@@ -172,7 +172,7 @@ static std::vector<DevBuf*> all_buffers(mrgingham_amd_ctx* ctx) {
         for (DevBuf* b : {&j.d_cnt, &j.d_pts, &j.d_pts0}) v.push_back(b);
     for (DevBuf* b : {&ctx->io_counts, &ctx->aux_img, &ctx->io_frame, &ctx->io_out, &ctx->pre_scratch, &ctx->pre_tmp,
                       &ctx->pre_out, &ctx->pre16_scratch, &ctx->io_frame16, &ctx->dbg_img, &ctx->dbg_resp, &ctx->blob_scratch, &ctx->blob_nodes, &ctx->blob_out,
-                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2})
+                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->jpeg_dev[0], &ctx->jpeg_dev[1]})
         v.push_back(b);
     return v;
 }
@@ -472,6 +472,10 @@ void mrgingham_amd_destroy(mrgingham_amd_ctx* ctx) {
         if (ctx->status_pin[k]) hipHostFree(ctx->status_pin[k]);
     for (hipEvent_t e : ctx->io_ev)
         if (e) hipEventDestroy(e);
+    for (int k = 0; k < 2; ++k) {
+        if (ctx->jpeg_pin[k]) hipHostFree(ctx->jpeg_pin[k]);
+        if (ctx->jpeg_ev[k]) hipEventDestroy(ctx->jpeg_ev[k]);
+    }
     if (ctx->mg_done) hipEventDestroy(ctx->mg_done);
     if (ctx->mg_stream) hipStreamDestroy(ctx->mg_stream);
     for (auto& j : ctx->jobs) {
@@ -629,6 +633,11 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
     if (!strcmp(name, "blob_chunk_frames")) {
         if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "blob_chunk_frames: 0 (by the scratch budget) or a frame count");
         ctx->blob_chunk_frames = value;
+        return 0;
+    }
+    if (!strcmp(name, "jpeg_chunk_frames")) {
+        if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_chunk_frames: 0 (by the scratch budget) or a frame count");
+        ctx->jpeg_chunk_frames = value;
         return 0;
     }
     if (!strcmp(name, "sparse_refine")) {

@@ -186,6 +186,15 @@ struct mrgingham_amd_ctx {
     int blob_chunk_frames = 0;
     hipEvent_t blob_ev[2] = {};  // around a chunk's kernels while kernel timing is on
     double blob_stat[8] = {};    // mrgingham_amd_blobs_stats (+ [7]: frames)
+    // mrgingham_amd_read_jpegs_batch (jpeg_idct.hip): two chunks of files in flight, one being parsed into its page-locked
+    // staging (coefficients | tables) while the other uploads into its device image and runs the inverse DCT; option
+    // "jpeg_chunk_frames" (test hook): at most that many frames per chunk, 0 = by jpeg_coef_budget
+    mrg::DevBuf jpeg_dev[2];
+    void* jpeg_pin[2] = {};
+    size_t jpeg_pin_bytes[2] = {};
+    hipEvent_t jpeg_ev[2] = {};
+    size_t jpeg_coef_budget = (size_t)1 << 30;  // both device buffers together
+    int jpeg_chunk_frames = 0;
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
     // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
     // context of THIS context's device, created on first use -- not on the calling thread's default context, which

@@ -1,5 +1,6 @@
 // See image_io.h.
 #include "image_io.h"
+#include "jpeg.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,7 +15,7 @@ namespace mrg {
 // BEFORE anything is allocated or indexed from a header field of an untrusted file.
 constexpr int kMaxSide = 32767;
 
-static bool read_file(const char* path, std::vector<uint8_t>& buf) {
+bool read_file(const char* path, std::vector<uint8_t>& buf) {
     FILE* f = fopen(path, "rb");
     if (!f) return false;
     fseek(f, 0, SEEK_END);
@@ -159,6 +160,20 @@ static bool decode_png(const std::vector<uint8_t>& b, Image& im) {
     return true;
 }
 
+// Baseline JPEG (jpeg.h): the luma plane, as cv::imread(IMREAD_GRAYSCALE) takes it from libjpeg.
+static bool decode_jpeg(const std::vector<uint8_t>& b, Image& im) {
+    JpegInfo info;
+    if (jpeg_coefficients(b.data(), b.size(), nullptr, 0, 0, &info) != 0) return false;
+    std::vector<int16_t> coef((size_t)info.blocks_w * info.blocks_h * 64);
+    if (jpeg_coefficients(b.data(), b.size(), coef.data(), coef.size(), 0, &info) != 0) return false;
+    const size_t n = (size_t)info.width * info.height;
+    im.w = info.width; im.h = info.height; im.depth = 8;
+    about_to_hold(im, n, 0);
+    im.px8.resize(n);
+    jpeg_idct_host(coef.data(), 0, info, im.px8.data());
+    return true;
+}
+
 // 8-bit binary PGM, the format a calibration run usually feeds the tool: the pixels go from the file straight into
 // px8 -- no copy of the whole file in between (a 12 MB image: one pass over memory less per image).  Returns 1 = done,
 // 0 = not such a file (the general path decides), -1 = such a file, but broken.
@@ -208,6 +223,7 @@ bool read_image(const char* path, Image& im) {
         if (!read_file(path, b) || b.size() < 8) return false;
         if (b[0] == 'P' && b[1] == '5') return decode_pgm(b, im);
         if (b[0] == 0x89 && b[1] == 'P') return decode_png(b, im);
+        if (b[0] == 0xFF && b[1] == 0xD8) return decode_jpeg(b, im);
         return false;
     } catch (...) {  // std::bad_alloc / length_error on a file that claims more than can be held
         return false;

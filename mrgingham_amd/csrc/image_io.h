@@ -1,9 +1,11 @@
 // Image decoding for the file-based entry points and the command-line tool (the reference uses
-// cv::imread; OpenCV is not available to this build): binary PGM (P5, 8 or 16 bit) and
-// non-interlaced PNG (8 or 16 bit; grey, grey+alpha, RGB, RGBA, 8-bit palette) via zlib.  Colour is
-// reduced to grey with the fixed-point BT.601 weights (4899 R + 9617 G + 1868 B + 8192) >> 14;
-// byte-identity with cv::imread on colour files is not claimed (its conversion depends on the codec
-// build).
+// cv::imread; OpenCV is not available to this build): binary PGM (P5, 8 or 16 bit),
+// non-interlaced PNG (8 or 16 bit; grey, grey+alpha, RGB, RGBA, 8-bit palette) via zlib, and baseline
+// JPEG (jpeg.h: sequential Huffman, one scan; the luma plane, byte for byte what libjpeg's default
+// decoder gives cv::imread(IMREAD_GRAYSCALE); progressive, arithmetic and multi-scan files are
+// unreadable).  PNG colour is reduced to grey with the fixed-point BT.601 weights
+// (4899 R + 9617 G + 1868 B + 8192) >> 14; byte-identity with cv::imread on colour PNG files is not
+// claimed (its conversion depends on the codec build).
 #pragma once
 #include <stdint.h>
 
@@ -23,6 +25,8 @@ struct Image {
 };
 
 bool read_image(const char* path, Image& im);
+// the whole file into buf (false: missing, unreadable or empty)
+bool read_file(const char* path, std::vector<uint8_t>& buf);
 // 16 -> 8 bit the way the reference CLI does it: convertTo(CV_8U, 255./65535.) (mrgingham-from-image.cc:91)
 void to_8bit(const Image& im, std::vector<uint8_t>& out);
 // 16 -> 8 bit the way cv::imread(IMREAD_GRAYSCALE) without IMREAD_ANYDEPTH does it (the reference's file
