@@ -23,7 +23,7 @@ void launch_chess_v0(const LevelBatch& lb, const CompTables& t, int frame0, int 
 void launch_chess(const LevelBatch& lb, const CompTables& t, int frame0, int nframes, bool clamp, bool hot,
                   hipStream_t s, int seg_rows = 0);
 
-// sparse refinement: the response + hot list in a per-frame list of cells only (cells listed by launch_sparse_cells, cc.hip)
+// sparse refinement: the response + hot list in a per-frame list of cells only (cells listed by launch_sparse_cells, cc_lds.hip)
 void launch_chess_cells(const LevelBatch& lb, const CompTables& t, const uint32_t* cell_list, const int32_t* cell_cnt,
                         int list_pitch, int frame0, int nframes, hipStream_t s);
 
@@ -86,7 +86,7 @@ bool launch_preprocess16_batch(const uint16_t* frames, long long pitch, int nfra
                                int blur_radius, uint8_t* out, void* scratch, uint8_t* tmp, hipStream_t s,
                                unsigned long long* clk = nullptr);
 
-// cc.hip
+// cc.hip, cc_lds.hip
 struct DetectOut {
     int32_t* xy;      // [nframes*capacity*2]
     int capacity;
@@ -118,7 +118,7 @@ struct RefineIO {
     // NULL at level 0
     int32_t* next_cnt = nullptr;
     uint32_t* next_list = nullptr;
-    int subsets = 1;  // workgroups per frame of the sparse refinement kernel (cc.hip, "Several workgroups"): 1 .. 4
+    int subsets = 1;  // workgroups per frame of the sparse refinement kernel (cc_sparse.h, "Several workgroups"): 1 .. 4
     int next_w = 0, next_h = 0;
     long long next_max_items = 0;
 };

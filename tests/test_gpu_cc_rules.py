@@ -1,4 +1,4 @@
-"""The HIP component-search kernels (cc_label / cc_detect / cc_refine, csrc/cc.hip) driven with
+"""The HIP component-search kernels (cc_label / cc_detect / cc_refine, csrc/cc.hip and cc_lds.hip) driven with
 HAND-BUILT and random sparse responses through mrgingham_amd_cc_on_response_batch: every rule of
 find_chessboard_corners.cc:159-267 / :284-397 is met on purpose here, not only when a natural image
 happens to produce it.  Expectations: the hand-derived values of tests/cc_cases.py AND the oracle on

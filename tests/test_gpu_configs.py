@@ -119,7 +119,7 @@ def test_c3_cluttered_frames_match_the_oracle_on_both_search_paths(det):
         _check_against_oracle(host[f], pts[f], lv[f], int(npts[f]))
         assert int((lv[f, :int(npts[f])] == 0).sum()) >= 100, f
     # refinement at level 0 (~7e4 hot pixels per frame): out of LDS all the same, on the hot pixels in the cells
-    # around the points only (cc.hip, WinSel); level 3 (~1.6e3) fits as it is
+    # around the points only (cc_lds.h, WinSel); level 3 (~1.6e3) fits as it is
     assert paths[0] == [1] * B and paths[3] == [1] * B, paths
     hot0 = int((oracle.clamped_response(host[0], 0)[0] > 15).sum())
     assert 2e4 < hot0 < 2e5, hot0

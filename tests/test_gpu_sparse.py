@@ -59,7 +59,7 @@ def test_sparse_chain_is_the_dense_chain(W, H, B, gridn, start):
 @pytest.mark.parametrize("W,H,gridn,start", [(4096, 3072, 14, 3), (2048, 1536, 14, 3), (3000, 3000, 12, 2), (4096, 3072, 16, 3)])
 def test_several_workgroups_per_frame_give_the_same_chain(W, H, gridn, start):
     """A frame with at least 128 points to refine is cut into up to `sparse_subsets` subsets of points that are far enough
-    apart, one workgroup of the refinement kernel each (cc.hip, "Several workgroups"): 1, 2 and 4 give the dense chain's
+    apart, one workgroup of the refinement kernel each (cc_sparse.h, "Several workgroups"): 1, 2 and 4 give the dense chain's
     doubles, levels and order; frames mixed (a 10x10 board's frame in the same batch stays with one workgroup), calls
     pipelined without a sync, no frame repeated densely that one workgroup would have taken."""
     dense, sparse = _pair()

@@ -1,4 +1,4 @@
-"""Probe lengths of the LDS hash map of the component search (cc.hip, lds_hash / lds_find) on the hot lists of
+"""Probe lengths of the LDS hash map of the component search (cc_lds.h, lds_hash / lds_find) on the hot lists of
 synthetic boards: python tools/hash_probe.py   (CPU only; uses the oracle for the responses).
 Prints, per board / level: entries, mean/max probes per hit and per miss of the four-neighbour lookups, for the
 single-multiplier hash round 2 started with and for the per-coordinate one in use (both with one slot per probe),
