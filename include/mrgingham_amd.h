@@ -41,7 +41,9 @@ extern "C" {
  *      device); option "blob_chunk_frames".
  *      Later, additive: mrgingham_amd_jpeg_coefficients, _jpeg_idct_batch, _read_jpegs_batch (baseline JPEG: entropy decode on
  *      the host, inverse DCT on the device); option "jpeg_chunk_frames"; mrgingham_amd_read_image and the file entry points
- *      read baseline JPEG. */
+ *      read baseline JPEG.
+ *      Later, additive: mrgingham_amd_jpeg_entropy_batch, _jpeg_restart_intervals (restart intervals Huffman-decoded on the
+ *      device); options "jpeg_entropy", "jpeg_entropy_max_interval", "jpeg_entropy_memset". */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -369,13 +371,45 @@ int mrgingham_amd_jpeg_idct_batch(mrgingham_amd_ctx* ctx, const int16_t* d_coef,
                                   const uint16_t* d_quant, int nframes, int width, int height, int blocks_w,
                                   int blocks_h, uint8_t* d_out, int64_t frame_pitch, int stride, void* stream);
 
+/* The restart intervals of a baseline JPEG held in memory (host only, no device needed): what a decoder needs to
+ * take the file apart into independent streams.  *restart_interval: MCUs per interval from the DRI segment, 0 when the
+ * file has none (then *nintervals is 0).  offsets (may be NULL: counts only) receives *nintervals = ceil(MCUs /
+ * restart_interval) pairs [begin, end) of byte offsets into `data`: an interval ends at the first FF that is not
+ * followed by 00, or at the end of the file; then any number of FF and D0 + (i & 7) must follow, or the file is
+ * unreadable; what follows the last interval is not examined.  The marker parse is mrgingham_amd_jpeg_coefficients' and
+ * accepts what it accepts; the entropy-coded data is only searched for markers, so a file this call accepts may still
+ * fail to decode.  Returns 0; -1 unreadable; -2 capacity (in pairs) too small (the counts are still reported). */
+int mrgingham_amd_jpeg_restart_intervals(const uint8_t* data, size_t nbytes, int* restart_interval, int64_t* offsets,
+                                         size_t capacity, size_t* nintervals);
+
+/* The device twin of mrgingham_amd_jpeg_coefficients for files that carry restart markers: nfiles baseline JPEG files
+ * held in memory, of ONE size, are Huffman-decoded ON THE DEVICE, one lane per restart interval; the host only finds the
+ * markers and uploads the compressed bytes.  d_coef / d_quant receive what mrgingham_amd_jpeg_idct_batch takes: file f's
+ * luma coefficients at d_coef + f*coef_pitch (elements) as int16 [blocks_h][blocks_w][64] with the GIVEN blocks_w /
+ * blocks_h (a file's own block counts may be smaller: its blocks lie in the top left corner, the rest of its area is not
+ * touched), its luma table at d_quant + f*64.  Int16 for int16 what mrgingham_amd_jpeg_coefficients gives, and a file
+ * is accepted exactly when that function accepts it.  h_status[f]: 0 decoded; -1 unreadable; -2 another size (or block
+ * counts above the given ones); -3 readable, but not taken by the device: the file has no restart interval, or one of
+ * more than option "jpeg_entropy_max_interval" MCUs -- decode it with mrgingham_amd_jpeg_coefficients.  Every file whose
+ * status is not 0 has its blocks_w*blocks_h*64 coefficients and its table zeroed.  SYNCHRONOUS; runs on the context's
+ * pixel stream, completes the find_boards jobs in flight first and restores the caller's HIP device.  Arguments are
+ * checked like mrgingham_amd_jpeg_idct_batch's (MRGINGHAM_AMD_ERR_ARG, nothing written); width and height are at
+ * least 1.  A corrupt file costs a status, never a fault: every index the stream supplies is checked on the device. */
+int mrgingham_amd_jpeg_entropy_batch(mrgingham_amd_ctx* ctx, const uint8_t* const* data, const size_t* nbytes, int nfiles,
+                                     int width, int height, int16_t* d_coef, int64_t coef_pitch, int blocks_w,
+                                     int blocks_h, uint16_t* d_quant, int32_t* h_status);
+
 /* nfiles baseline JPEG files of ONE size straight into device frames (layout as d_out above): nthreads host threads
  * (<= 0: all cores, at most 32) entropy-decode a chunk of files into page-locked staging while the chunk before it
  * uploads and runs mrgingham_amd_jpeg_idct_batch; the decoded pixels never exist on the host.  h_status[f]: 0 decoded,
  * -1 unreadable / unsupported / malformed, -2 a JPEG of another size; the frame of a failed file is zero-filled.
  * SYNCHRONOUS: d_out is complete on return.  Returns MRGINGHAM_AMD_OK also when files failed.  Completes the
  * find_boards jobs in flight first and restores the caller's HIP device.  The two device coefficient buffers stay within
- * 1 GiB of context scratch (12 MP: ~20 frames each; option "jpeg_chunk_frames"). */
+ * 1 GiB of context scratch (12 MP: ~20 frames each; option "jpeg_chunk_frames").
+ * With option "jpeg_entropy" 1 the host threads read the files and find their restart markers; the files that have
+ * restart intervals (of at most "jpeg_entropy_max_interval" MCUs) are uploaded as compressed bytes and Huffman-decoded
+ * on the device (mrgingham_amd_jpeg_entropy_batch's kernel) in front of the inverse DCT, the others are decoded by the
+ * host threads as without the option.  Same frames, same statuses. */
 int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width,
                                    int height, uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads,
                                    int32_t* h_status);
@@ -567,6 +601,13 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         by their scratch budget; n > 0 = at most n frames per chunk.  Results never depend on it.
  *   "jpeg_chunk_frames"   test hook: 0 (default) = mrgingham_amd_read_jpegs_batch cuts its files into chunks by its scratch
  *                         budget; n > 0 = at most n files per chunk.  Results never depend on it.
+ *   "jpeg_entropy"        0 (default): mrgingham_amd_read_jpegs_batch entropy-decodes on its host threads; 1: files with
+ *                         restart intervals are Huffman-decoded on the device, one lane per interval.  Same frames and statuses.
+ *   "jpeg_entropy_max_interval"  MCUs per restart interval the device accepts (default 1024, at least 1; files above it go
+ *                         to the host threads / get status -3).  A condition, not a tuning result: it bounds the serial
+ *                         work of one lane, so a 12 MP file of a single interval is never handed to one lane.
+ *   "jpeg_entropy_memset" how the device decoder fills the blocks (same coefficients): 0 (default) = every lane writes its
+ *                         blocks in full, zeros included; 1 = the area is zeroed in front and lanes store non-zero values
  *   "find_boards_pipeline" 1 (default): mrgingham_amd_find_boards_batch / _submit / _collect as described there; 0: the
  *                         synchronous schedule (one level at a time for the whole batch, dense refinement) -- same results
  *   "chess_seg", "chess16_seg"  rows per workgroup of the ChESS kernels of THIS context (chess_v1* / chess_v16; 0 = cost model,
@@ -613,7 +654,9 @@ int mrgingham_amd_after_stream(mrgingham_amd_ctx* ctx, void* stream);
  * response kernel) over the launches issued since the last call, measured with
  * hipEvents on the streams the kernel ran on; the number of launches is stored
  * in *nlaunches.  Timing is off by default: enable with
- * mrgingham_amd_set_kernel_timing(ctx, 1); 2 = only the engine-clock probe below (no events on the streams), 0 = off. */
+ * mrgingham_amd_set_kernel_timing(ctx, 1); 2 = only the engine-clock probe below (no events on the streams), 0 = off.
+ * While timing is on, the Huffman launches of mrgingham_amd_jpeg_entropy_batch / of the loader under "jpeg_entropy" are
+ * bracketed and counted the same way (one pair per chunk; tools/jpeg_huff_bench.py). */
 void mrgingham_amd_set_kernel_timing(mrgingham_amd_ctx* ctx, int enable);
 double mrgingham_amd_chess_kernel_ms(mrgingham_amd_ctx* ctx, int* nlaunches);
 

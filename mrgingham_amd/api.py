@@ -134,6 +134,22 @@ def jpeg_coefficients_size(data):
     return h.value, w.value
 
 
+def jpeg_restart_intervals(data):
+    """The restart intervals of a baseline JPEG held in memory (host only; mrgingham_amd_jpeg_restart_intervals):
+    -> (restart_interval, offsets int64 [n, 2]) -- MCUs per interval and the [begin, end) byte offsets of the
+    n = ceil(MCUs / restart_interval) independent streams; (0, empty [0, 2]) for a file without a DRI segment; None when
+    the file is not one this library reads."""
+    L = _lib.lib()
+    buf = bytes(data)
+    ri, n = ctypes.c_int(), ctypes.c_size_t()
+    if L.mrgingham_amd_jpeg_restart_intervals(buf, len(buf), ctypes.byref(ri), None, 0, ctypes.byref(n)) != 0:
+        return None
+    offsets = np.zeros((n.value, 2), dtype=np.int64)
+    if L.mrgingham_amd_jpeg_restart_intervals(buf, len(buf), ctypes.byref(ri), offsets.ctypes.data, n.value, ctypes.byref(n)) != 0:
+        return None
+    return ri.value, offsets
+
+
 def read_image(filename, cli_scaling=False):
     """Decode a binary PGM, non-interlaced PNG or baseline JPEG to uint8 [H, W] with the library's own decoder (host only).
     16-bit files: the high byte (cv::imread(IMREAD_GRAYSCALE)) or, with cli_scaling, the CLI's
@@ -658,12 +674,43 @@ class Detector:
             out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
         return out[:, :, :width]
 
-    def read_jpegs(self, paths, nthreads=0):
+    def jpeg_entropy(self, datas, height, width):
+        """Huffman decode of baseline JPEG files held in memory ON THE DEVICE, one lane per restart interval
+        (mrgingham_amd_jpeg_entropy_batch): `datas` are the files' bytes, all height x width.  -> (coef int16
+        [B, bh, bw, 64], quant uint16 [B, 64]) device tensors as jpeg_idct takes them -- bh x bw the largest block counts
+        any sampling gives the size -- and status int32 [B] (numpy): 0 decoded (what jpeg_coefficients gives, in the top
+        left corner of the file's area), -1 unreadable, -2 another size, -3 readable but without restart intervals (or
+        longer ones than option "jpeg_entropy_max_interval"): decode those with jpeg_coefficients.  Files whose status is
+        not 0 have zero coefficients and tables.  Synchronous."""
+        t = self.torch
+        bufs = [bytes(d) for d in datas]
+        B = len(bufs)
+
+        def padded(side):
+            return max(-(-side // (8 * h)) * h for h in (1, 2, 3, 4))
+        bh, bw = padded(int(height)), padded(int(width))
+        coef = t.empty((B, bh, bw, 64), dtype=t.int16, device=self.device)
+        quant = t.empty((B, 64), dtype=t.uint16, device=self.device)
+        status = np.full((B,), -1, dtype=np.int32)
+        if B == 0:
+            return coef, quant, status
+        ptrs = (ctypes.c_char_p * B)(*bufs)
+        sizes = (ctypes.c_size_t * B)(*[len(b) for b in bufs])
+        t.cuda.current_stream(self.device).synchronize()
+        self._check(self.L.mrgingham_amd_jpeg_entropy_batch(self.ctx, ptrs, sizes, B, int(width), int(height), coef.data_ptr(),
+                                                            bh * bw * 64, bw, bh, quant.data_ptr(), status.ctypes.data))
+        return coef, quant, status
+
+    def read_jpegs(self, paths, nthreads=0, entropy="host"):
         """Baseline JPEG files of one size straight into device frames (mrgingham_amd_read_jpegs_batch): `nthreads` host
         threads (0: all cores, at most 32) entropy-decode, the device runs the inverse DCT; the decoded pixels never exist
         on the host.  -> (frames uint8 [B,H,W] on the device, status int32 [B] numpy: 0 decoded, -1 unreadable /
         unsupported / malformed, -2 a JPEG of another size; failed frames are zero).  The size is that of the first file
-        whose header parses (none does: frames are [B,0,0]).  Synchronous."""
+        whose header parses (none does: frames are [B,0,0]).  Synchronous.  entropy="device": option "jpeg_entropy" is 1
+        for this call (and what it was afterwards) -- files with restart intervals are Huffman-decoded on the device as
+        well, the host threads only find their markers; same frames, same statuses."""
+        if entropy not in ("host", "device"):
+            raise ValueError('read_jpegs: entropy is "host" or "device"')
         t = self.torch
         names = [os.fsencode(p) for p in paths]
         B = len(names)
@@ -683,8 +730,13 @@ class Detector:
             return frames, status
         arr = (ctypes.c_char_p * B)(*names)
         t.cuda.current_stream(self.device).synchronize()
-        self._check(self.L.mrgingham_amd_read_jpegs_batch(self.ctx, arr, B, W, H, frames.data_ptr(), H * W, W, int(nthreads),
-                                                          status.ctypes.data))
+        before = self._options.get("jpeg_entropy", 0)
+        self.set_option("jpeg_entropy", int(entropy == "device"))
+        try:
+            self._check(self.L.mrgingham_amd_read_jpegs_batch(self.ctx, arr, B, W, H, frames.data_ptr(), H * W, W, int(nthreads),
+                                                              status.ctypes.data))
+        finally:
+            self.set_option("jpeg_entropy", before)
         return frames, status
 
     BLOBS_STATS = ("calls", "chunks", "nodes", "contours", "points", "device_ms", "host_ms", "frames")

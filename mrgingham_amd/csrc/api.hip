@@ -172,7 +172,7 @@ static std::vector<DevBuf*> all_buffers(mrgingham_amd_ctx* ctx) {
         for (DevBuf* b : {&j.d_cnt, &j.d_pts, &j.d_pts0}) v.push_back(b);
     for (DevBuf* b : {&ctx->io_counts, &ctx->aux_img, &ctx->io_frame, &ctx->io_out, &ctx->pre_scratch, &ctx->pre_tmp,
                       &ctx->pre_out, &ctx->pre16_scratch, &ctx->io_frame16, &ctx->dbg_img, &ctx->dbg_resp, &ctx->blob_scratch, &ctx->blob_nodes, &ctx->blob_out,
-                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->jpeg_dev[0], &ctx->jpeg_dev[1]})
+                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->jpeg_dev[0], &ctx->jpeg_dev[1], &ctx->jpeg_huff_dev[0], &ctx->jpeg_huff_dev[1]})
         v.push_back(b);
     return v;
 }
@@ -474,6 +474,7 @@ void mrgingham_amd_destroy(mrgingham_amd_ctx* ctx) {
         if (e) hipEventDestroy(e);
     for (int k = 0; k < 2; ++k) {
         if (ctx->jpeg_pin[k]) hipHostFree(ctx->jpeg_pin[k]);
+        if (ctx->jpeg_huff_pin[k]) hipHostFree(ctx->jpeg_huff_pin[k]);
         if (ctx->jpeg_ev[k]) hipEventDestroy(ctx->jpeg_ev[k]);
     }
     if (ctx->mg_done) hipEventDestroy(ctx->mg_done);
@@ -640,6 +641,17 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
         ctx->jpeg_chunk_frames = value;
         return 0;
     }
+    if (!strcmp(name, "jpeg_entropy")) {
+        if (value != 0 && value != 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_entropy: 0 (host threads) or 1 (the device, for files with restart intervals)");
+        ctx->jpeg_entropy = value;
+        return 0;
+    }
+    if (!strcmp(name, "jpeg_entropy_max_interval")) {
+        if (value < 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_entropy_max_interval: at least 1 MCU");
+        ctx->jpeg_entropy_max_interval = value;
+        return 0;
+    }
+    if (!strcmp(name, "jpeg_entropy_memset")) { ctx->jpeg_entropy_memset = value != 0; return 0; }
     if (!strcmp(name, "sparse_refine")) {
         if (value < 0 || value > 2) return MRGINGHAM_AMD_ERR_ARG;
         ctx->sparse_refine = value;

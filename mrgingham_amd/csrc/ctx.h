@@ -195,6 +195,17 @@ struct mrgingham_amd_ctx {
     hipEvent_t jpeg_ev[2] = {};
     size_t jpeg_coef_budget = (size_t)1 << 30;  // both device buffers together
     int jpeg_chunk_frames = 0;
+    // the device entropy path of the loader and mrgingham_amd_jpeg_entropy_batch (jpeg_huff.hip): per chunk slot one
+    // staging image (frame records | tables | interval records | compressed bytes | one status byte per interval),
+    // page-locked on the host and mirrored on the device, both grown on demand.  Options "jpeg_entropy" (0: host threads
+    // decode, 1: the device where the file has restart intervals), "jpeg_entropy_max_interval" (MCUs one lane may be
+    // handed), "jpeg_entropy_memset" (0: lanes write whole blocks, 1: the area is zeroed in front and lanes store non-zeros)
+    mrg::DevBuf jpeg_huff_dev[2];
+    void* jpeg_huff_pin[2] = {};
+    size_t jpeg_huff_pin_bytes[2] = {};
+    int jpeg_entropy = 0;
+    int jpeg_entropy_max_interval = 1024;
+    int jpeg_entropy_memset = 0;
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
     // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
     // context of THIS context's device, created on first use -- not on the calling thread's default context, which
@@ -319,6 +330,15 @@ int refine_on_device(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, dou
 int blob_detect_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int nthreads, std::vector<std::vector<int32_t>>& xy,
                       std::vector<char>& bad);
 int host_threads(int nthreads);
+
+// jpeg_idct.hip
+void launch_jpeg_idct(const int16_t* d_coef, int64_t coef_pitch, const uint16_t* d_quant, int nframes, int width, int height,
+                      int blocks_w, uint8_t* d_out, int64_t frame_pitch, int stride, hipStream_t s);
+int ensure_pin(mrgingham_amd_ctx* ctx, int slot, size_t bytes);
+// jpeg_huff.hip: mrgingham_amd_read_jpegs_batch with option "jpeg_entropy" 1 (arguments checked, geometry chosen there)
+int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
+                              uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status, int bw, int bh,
+                              int chunk);
 
 // boards.hip
 struct GridScratch { std::vector<PointI> cand; std::vector<PointD> grid; };

@@ -1,5 +1,6 @@
 // See jpeg.h.
 #include "jpeg.h"
+#include "jpeg_huff_lane.h"
 #include "jpeg_idct8.h"
 
 #include <string.h>
@@ -9,25 +10,15 @@ namespace {
 
 constexpr int kMaxSide = 32767;  // as image_io.cpp: checked before anything is sized from a header field
 
-// position in the zigzag scan -> position in the block, row-major
-const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+const uint8_t kNatural[64] = {MRG_JPEG_NATURAL_ORDER};  // position in the zigzag scan -> position in the block
 
-constexpr int kLookBits = 9;
+constexpr int kLookBits = kJpegLookBits;
 
-struct Huff {
-    bool defined = false;
-    int nvals = 0;
-    uint16_t look[1 << kLookBits];  // the next 9 bits -> (code length << 8) | symbol; 0: a longer code, or none
-    int32_t maxcode[17];            // [l]: the largest code of l bits, -1 where there is none
-    int32_t valoff[17];             // symbol index of a code of l bits = code + valoff[l]
-    uint8_t vals[256];
-};
+using Huff = JpegHuffTable;  // (jpeg_huff_lane.h: the 9-bit look-up and the canonical walk, flat)
 
 // counts[16] + symbols, as a DHT segment holds them.  false: the lengths do not describe a prefix code.
 bool build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) {
-    memset(h.look, 0, sizeof(h.look));
+    memset(&h, 0, sizeof(h));
     memcpy(h.vals, vals, (size_t)nvals);
     h.nvals = nvals;
     int32_t code = 0;
@@ -50,7 +41,7 @@ bool build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) 
         }
         code <<= 1;
     }
-    h.defined = true;
+    h.defined = 1;
     return true;
 }
 
@@ -140,16 +131,19 @@ bool decode_block(Bits& b, const Huff& dc, const Huff& ac, int* pred, int16_t* d
 
 inline unsigned be16(const uint8_t* p) { return ((unsigned)p[0] << 8) | p[1]; }
 
-}  // namespace
-
-int jpeg_coefficients(const uint8_t* data, size_t nbytes, int16_t* coef, size_t coef_capacity, int row_pitch_blocks,
-                      JpegInfo* info) {
-    if (!data || !info || nbytes < 4 || data[0] != 0xFF || data[1] != 0xD8) return -1;
+// The marker parse up to and including SOS: everything of `sc` but the interval list.  *entropy: where the
+// entropy-coded data begins.  0, or -1 unreadable.
+int parse_header(const uint8_t* data, size_t nbytes, JpegScan* sc, size_t* entropy) {
+    JpegInfo* info = &sc->info;
+    if (!data || nbytes < 4 || data[0] != 0xFF || data[1] != 0xD8) return -1;
     uint16_t qt[4][64];
     bool qt_defined[4] = {false, false, false, false};
-    // (static-free, on the stack: 8 tables of ~1.5 KB; worker threads decode side by side)
-    Huff hd[4], ha[4];
-    int ncomp = 0, comp_id[3] = {0, 0, 0}, comp_h[3] = {0, 0, 0}, comp_v[3] = {0, 0, 0}, comp_tq[3] = {0, 0, 0};
+    Huff* hd = sc->dc;
+    Huff* ha = sc->ac;
+    for (int i = 0; i < 4; ++i) hd[i].defined = ha[i].defined = 0;
+    int ncomp = 0, comp_id[3] = {0, 0, 0}, comp_tq[3] = {0, 0, 0};
+    int* comp_h = sc->comp_h;
+    int* comp_v = sc->comp_v;
     bool have_sof = false, jfif = false, adobe = false;
     int adobe_transform = -1;
     unsigned restart_interval = 0;
@@ -225,7 +219,8 @@ int jpeg_coefficients(const uint8_t* data, size_t nbytes, int16_t* coef, size_t 
             if (!have_sof || dl < 1) return -1;
             const int ns = d[0];
             if (ns != ncomp || dl != (size_t)(4 + 2 * ns)) return -1;
-            int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+            int* td = sc->td;
+            int* ta = sc->ta;
             for (int c = 0; c < ns; ++c) {
                 if (d[1 + 2 * c] != comp_id[c]) return -1;
                 td[c] = d[2 + 2 * c] >> 4;
@@ -243,51 +238,101 @@ int jpeg_coefficients(const uint8_t* data, size_t nbytes, int16_t* coef, size_t 
             // a single-component scan is not interleaved: one block per MCU whatever its sampling factors say
             const int H0 = ncomp == 1 ? 1 : comp_h[0], V0 = ncomp == 1 ? 1 : comp_v[0];
             if (ncomp == 1) comp_h[0] = comp_v[0] = 1;
-            const int mcus_x = (info->width + 8 * H0 - 1) / (8 * H0), mcus_y = (info->height + 8 * V0 - 1) / (8 * V0);
-            info->blocks_w = mcus_x * H0;
-            info->blocks_h = mcus_y * V0;
-            int per_mcu = 0;
-            for (int c = 0; c < ncomp; ++c) per_mcu += comp_h[c] * comp_v[c];
-            if (per_mcu > 10) return -1;  // (the standard's limit)
-            if (!coef) return 0;
-            const int pitch = row_pitch_blocks > 0 ? row_pitch_blocks : info->blocks_w;
-            if (pitch < info->blocks_w || coef_capacity / 64 / (size_t)pitch < (size_t)info->blocks_h) return -2;
-            // a block takes at least two bits: a stream this short cannot hold the frame (and is not walked to find out)
-            const size_t nmcu = (size_t)mcus_x * mcus_y;
-            if (nmcu * per_mcu / 4 > nbytes - pos) return -1;
-
-            Bits bits;
-            bits.p = data + pos;
-            bits.end = data + nbytes;
-            int pred[3] = {0, 0, 0};
-            size_t done = 0;
-            unsigned next_rst = 0;
-            for (int my = 0; my < mcus_y; ++my)
-                for (int mx = 0; mx < mcus_x; ++mx, ++done) {
-                    if (restart_interval && done && done % restart_interval == 0) {
-                        // RSTn, in sequence, exactly here: nothing but the last byte's padding bits is left over
-                        if (bits.n - bits.pad >= 8) return -1;
-                        const uint8_t* p = bits.p;
-                        if (p >= bits.end || *p != 0xFF) return -1;
-                        while (p < bits.end && *p == 0xFF) ++p;
-                        if (p >= bits.end || *p != 0xD0 + next_rst) return -1;
-                        next_rst = (next_rst + 1) & 7;
-                        bits = Bits();
-                        bits.p = p + 1;
-                        bits.end = data + nbytes;
-                        pred[0] = pred[1] = pred[2] = 0;
-                    }
-                    for (int c = 0; c < ncomp; ++c)
-                        for (int v = 0; v < comp_v[c]; ++v)
-                            for (int h = 0; h < comp_h[c]; ++h) {
-                                int16_t* dst = c ? nullptr : coef + ((size_t)(my * V0 + v) * pitch + (size_t)(mx * H0 + h)) * 64;
-                                if (!decode_block(bits, hd[td[c]], ha[ta[c]], &pred[c], dst)) return -1;
-                            }
-                }
+            sc->ncomp = ncomp;
+            sc->mcus_x = (info->width + 8 * H0 - 1) / (8 * H0);
+            sc->mcus_y = (info->height + 8 * V0 - 1) / (8 * V0);
+            info->blocks_w = sc->mcus_x * H0;
+            info->blocks_h = sc->mcus_y * V0;
+            sc->blocks_per_mcu = 0;
+            for (int c = 0; c < ncomp; ++c) sc->blocks_per_mcu += comp_h[c] * comp_v[c];
+            if (sc->blocks_per_mcu > 10) return -1;  // (the standard's limit)
+            sc->restart_interval = restart_interval;
+            *entropy = pos;
             return 0;
         }
         // every other segment (APPn, COM, ...) is skipped
     }
+}
+
+// a block takes at least two bits: a stream this short cannot hold the frame (and is not walked to find out)
+bool too_short(const JpegScan& sc, size_t nbytes, size_t entropy) {
+    return (size_t)sc.mcus_x * sc.mcus_y * sc.blocks_per_mcu / 4 > nbytes - entropy;
+}
+
+}  // namespace
+
+int jpeg_scan(const uint8_t* data, size_t nbytes, JpegScan* sc) {
+    if (!sc) return -1;
+    sc->intervals.clear();
+    sc->entropy_begin = 0;
+    size_t pos = 0;
+    if (parse_header(data, nbytes, sc, &pos) || too_short(*sc, nbytes, pos)) return -1;
+    sc->entropy_begin = pos;
+    if (!sc->restart_interval) return 0;
+    const size_t nmcu = (size_t)sc->mcus_x * sc->mcus_y, count = (nmcu + sc->restart_interval - 1) / sc->restart_interval;
+    sc->intervals.reserve(2 * count);
+    for (size_t i = 0; i < count; ++i) {
+        // the interval: up to the first FF that no 00 follows, or the end of the file
+        size_t e = pos;
+        while (e < nbytes && !(data[e] == 0xFF && !(e + 1 < nbytes && data[e + 1] == 0))) e += data[e] == 0xFF ? 2 : 1;
+        sc->intervals.push_back(pos);
+        sc->intervals.push_back(e);
+        if (i + 1 == count) break;  // what follows the last interval is not examined
+        // RSTn, in sequence: FF, any number of FF, D0 + (i & 7)
+        while (e < nbytes && data[e] == 0xFF) ++e;
+        if (e >= nbytes || data[e] != 0xD0 + (i & 7)) { sc->intervals.clear(); return -1; }
+        pos = e + 1;
+    }
+    return 0;
+}
+
+int jpeg_coefficients(const uint8_t* data, size_t nbytes, int16_t* coef, size_t coef_capacity, int row_pitch_blocks,
+                      JpegInfo* info) {
+    if (!info) return -1;
+    // (static-free, on the stack: 8 tables of ~1.4 KB; worker threads decode side by side)
+    JpegScan sc;
+    size_t pos = 0;
+    const int head = parse_header(data, nbytes, &sc, &pos);
+    *info = sc.info;  // (unreadable: partly filled)
+    if (head) return -1;
+    if (!coef) return 0;
+    const int ncomp = sc.ncomp, mcus_x = sc.mcus_x, mcus_y = sc.mcus_y, H0 = sc.comp_h[0], V0 = sc.comp_v[0];
+    const int *comp_h = sc.comp_h, *comp_v = sc.comp_v, *td = sc.td, *ta = sc.ta;
+    const Huff *hd = sc.dc, *ha = sc.ac;
+    const unsigned restart_interval = sc.restart_interval;
+    const int pitch = row_pitch_blocks > 0 ? row_pitch_blocks : info->blocks_w;
+    if (pitch < info->blocks_w || coef_capacity / 64 / (size_t)pitch < (size_t)info->blocks_h) return -2;
+    if (too_short(sc, nbytes, pos)) return -1;
+
+    Bits bits;
+    bits.p = data + pos;
+    bits.end = data + nbytes;
+    int pred[3] = {0, 0, 0};
+    size_t done = 0;
+    unsigned next_rst = 0;
+    for (int my = 0; my < mcus_y; ++my)
+        for (int mx = 0; mx < mcus_x; ++mx, ++done) {
+            if (restart_interval && done && done % restart_interval == 0) {
+                // RSTn, in sequence, exactly here: nothing but the last byte's padding bits is left over
+                if (bits.n - bits.pad >= 8) return -1;
+                const uint8_t* p = bits.p;
+                if (p >= bits.end || *p != 0xFF) return -1;
+                while (p < bits.end && *p == 0xFF) ++p;
+                if (p >= bits.end || *p != 0xD0 + next_rst) return -1;
+                next_rst = (next_rst + 1) & 7;
+                bits = Bits();
+                bits.p = p + 1;
+                bits.end = data + nbytes;
+                pred[0] = pred[1] = pred[2] = 0;
+            }
+            for (int c = 0; c < ncomp; ++c)
+                for (int v = 0; v < comp_v[c]; ++v)
+                    for (int h = 0; h < comp_h[c]; ++h) {
+                        int16_t* dst = c ? nullptr : coef + ((size_t)(my * V0 + v) * pitch + (size_t)(mx * H0 + h)) * 64;
+                        if (!decode_block(bits, hd[td[c]], ha[ta[c]], &pred[c], dst)) return -1;
+                    }
+        }
+    return 0;
 }
 
 void jpeg_idct_host(const int16_t* coef, int row_pitch_blocks, const JpegInfo& info, uint8_t* out) {

@@ -12,6 +12,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
+#include "jpeg_huff_lane.h"
+
 namespace mrg {
 
 struct JpegInfo {
@@ -27,6 +31,29 @@ struct JpegInfo {
 // coef_capacity (elements) or row_pitch_blocks is too small for it (info is complete, nothing decoded).
 int jpeg_coefficients(const uint8_t* data, size_t nbytes, int16_t* coef, size_t coef_capacity, int row_pitch_blocks,
                       JpegInfo* info);
+
+// What the marker parse of jpeg_coefficients finds, for a caller that decodes the entropy-coded data itself (the device:
+// jpeg_huff.hip, one lane per restart interval through jpeg_huff_lane.h).
+struct JpegScan {
+    JpegInfo info;
+    int ncomp = 0;                                 // 1 or 3
+    int comp_h[3] = {}, comp_v[3] = {};            // blocks of component c in an MCU, across and down ([0]: 1, 1 when ncomp is 1)
+    int td[3] = {}, ta[3] = {};                    // the DC / AC table component c decodes with: dc[td[c]], ac[ta[c]]
+    int mcus_x = 0, mcus_y = 0, blocks_per_mcu = 0;
+    unsigned restart_interval = 0;                 // MCUs per restart interval, 0: the file has none
+    size_t entropy_begin = 0;                      // where the entropy-coded data begins
+    JpegHuffTable dc[4], ac[4];
+    // restart_interval != 0: [begin, end) byte offsets into the file of its ceil(mcus_x * mcus_y / restart_interval)
+    // intervals, two entries each.  An interval ends at the first FF that is not followed by 00, or at the end of the
+    // file; then any number of FF and D0 + (i & 7) must follow, or the file is unreadable; what follows the last
+    // interval is not examined.  (Exactly what jpeg_coefficients walks over.)
+    std::vector<uint64_t> intervals;
+};
+
+// The marker parse of jpeg_coefficients alone, and the restart intervals.  All acceptance rules above hold; the entropy-coded
+// data is only searched for markers.  0, or -1: jpeg_coefficients calls the file unreadable as well (the converse does
+// not hold: an interval may still fail to decode).
+int jpeg_scan(const uint8_t* data, size_t nbytes, JpegScan* scan);
 
 // The inverse DCT of every block into out (info.width x info.height bytes, dense); coef laid out as above.
 void jpeg_idct_host(const int16_t* coef, int row_pitch_blocks, const JpegInfo& info, uint8_t* out);

@@ -103,6 +103,10 @@ int check_idct_args(mrgingham_amd_ctx* ctx, const int16_t* d_coef, int64_t coef_
     return 0;
 }
 
+}  // namespace
+
+namespace mrg {
+
 void launch_jpeg_idct(const int16_t* d_coef, int64_t coef_pitch, const uint16_t* d_quant, int nframes, int width, int height,
                       int blocks_w, uint8_t* d_out, int64_t frame_pitch, int stride, hipStream_t s) {
     const int bw = (width + 7) / 8, bh = (height + 7) / 8;
@@ -128,7 +132,7 @@ int ensure_pin(mrgingham_amd_ctx* ctx, int slot, size_t bytes) {
     return 0;
 }
 
-}  // namespace
+}  // namespace mrg
 
 extern "C" {
 
@@ -188,6 +192,8 @@ int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
     int chunk = fit < 1 ? 1 : fit > (size_t)nfiles ? nfiles : (int)fit;
     if (chunk > nthreads) chunk -= chunk % nthreads;  // whole rounds of the host threads
     if (ctx->jpeg_chunk_frames > 0 && chunk > ctx->jpeg_chunk_frames) chunk = ctx->jpeg_chunk_frames;
+    if (ctx->jpeg_entropy)  // files with restart intervals are Huffman-decoded on the device (jpeg_huff.hip)
+        return read_jpegs_device_entropy(ctx, filenames, nfiles, width, height, d_out, frame_pitch, stride, nthreads, h_status, bw, bh, chunk);
     const size_t coef_bytes = (size_t)chunk * per_frame * sizeof(int16_t), slot_bytes = coef_bytes + (size_t)chunk * 64 * sizeof(uint16_t);
     const int nslots = nfiles > chunk ? 2 : 1;
     int rc;
