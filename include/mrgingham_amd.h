@@ -43,7 +43,10 @@ extern "C" {
  *      the host, inverse DCT on the device); option "jpeg_chunk_frames"; mrgingham_amd_read_image and the file entry points
  *      read baseline JPEG.
  *      Later, additive: mrgingham_amd_jpeg_entropy_batch, _jpeg_restart_intervals (restart intervals Huffman-decoded on the
- *      device); options "jpeg_entropy", "jpeg_entropy_max_interval", "jpeg_entropy_memset". */
+ *      device); options "jpeg_entropy", "jpeg_entropy_max_interval", "jpeg_entropy_memset".
+ *      Later, additive and backward compatible: mrgingham_amd_jpeg_sync_rounds; options "jpeg_sync", "jpeg_sync_subsequence",
+ *      "jpeg_sync_max_rounds" (files without restart markers Huffman-decoded on the device; off by default, and then every
+ *      call behaves as before). */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -382,6 +385,20 @@ int mrgingham_amd_jpeg_idct_batch(mrgingham_amd_ctx* ctx, const int16_t* d_coef,
 int mrgingham_amd_jpeg_restart_intervals(const uint8_t* data, size_t nbytes, int* restart_interval, int64_t* offsets,
                                          size_t capacity, size_t* nintervals);
 
+/* How the self-synchronising decoder that option "jpeg_sync" switches on fares on a baseline JPEG held in memory (host
+ * only, no device needed; the same decoder text and the same schedule as on the device, serially).  The entropy-coded
+ * segment of the file's one scan is cut into *nsubsequences pieces of subsequence_bytes raw bytes (a multiple of 4 in
+ * 8..1024); every piece is first decoded from its own first byte as if a block began there, then re-entered, round
+ * after round, from the state its left neighbour ended in, until a round changes nothing: then every piece holds what
+ * the serial decoder computes.  *rounds: the update rounds that changed at least one piece -- the device takes the file
+ * iff that is at most option "jpeg_sync_max_rounds".  Returns 0 for a readable file without restart intervals; -1
+ * unreadable (what mrgingham_amd_jpeg_coefficients calls unreadable, or a bad subsequence_bytes); -3 a readable file that
+ * has restart intervals; -4 a readable file without them whose entropy-coded segment has 2^29 bytes or more (the device
+ * leaves it to the host: status -3 of mrgingham_amd_jpeg_entropy_batch).  *rounds and *nsubsequences are 0 unless 0 is
+ * returned. */
+int mrgingham_amd_jpeg_sync_rounds(const uint8_t* data, size_t nbytes, int subsequence_bytes, int* rounds,
+                                   size_t* nsubsequences);
+
 /* The device twin of mrgingham_amd_jpeg_coefficients for files that carry restart markers: nfiles baseline JPEG files
  * held in memory, of ONE size, are Huffman-decoded ON THE DEVICE, one lane per restart interval; the host only finds the
  * markers and uploads the compressed bytes.  d_coef / d_quant receive what mrgingham_amd_jpeg_idct_batch takes: file f's
@@ -391,7 +408,11 @@ int mrgingham_amd_jpeg_restart_intervals(const uint8_t* data, size_t nbytes, int
  * is accepted exactly when that function accepts it.  h_status[f]: 0 decoded; -1 unreadable; -2 another size (or block
  * counts above the given ones); -3 readable, but not taken by the device: the file has no restart interval, or one of
  * more than option "jpeg_entropy_max_interval" MCUs -- decode it with mrgingham_amd_jpeg_coefficients.  Every file whose
- * status is not 0 has its blocks_w*blocks_h*64 coefficients and its table zeroed.  SYNCHRONOUS; runs on the context's
+ * status is not 0 has its blocks_w*blocks_h*64 coefficients and its table zeroed.
+ * With option "jpeg_sync" 1 the files WITHOUT restart intervals are decoded as well (see mrgingham_amd_jpeg_sync_rounds
+ * for the method; one lane per "jpeg_sync_subsequence" bytes): 0 decoded, with the same coefficients and table; -1
+ * unreadable; -3 not converged within "jpeg_sync_max_rounds" update rounds (or an entropy-coded segment of 2^29 bytes or
+ * more), zeroed like the others.  Files with restart intervals are treated as without the option.  SYNCHRONOUS; runs on the context's
  * pixel stream, completes the find_boards jobs in flight first and restores the caller's HIP device.  Arguments are
  * checked like mrgingham_amd_jpeg_idct_batch's (MRGINGHAM_AMD_ERR_ARG, nothing written); width and height are at
  * least 1.  A corrupt file costs a status, never a fault: every index the stream supplies is checked on the device. */
@@ -409,7 +430,11 @@ int mrgingham_amd_jpeg_entropy_batch(mrgingham_amd_ctx* ctx, const uint8_t* cons
  * With option "jpeg_entropy" 1 the host threads read the files and find their restart markers; the files that have
  * restart intervals (of at most "jpeg_entropy_max_interval" MCUs) are uploaded as compressed bytes and Huffman-decoded
  * on the device (mrgingham_amd_jpeg_entropy_batch's kernel) in front of the inverse DCT, the others are decoded by the
- * host threads as without the option.  Same frames, same statuses. */
+ * host threads as without the option.  Same frames, same statuses.
+ * With option "jpeg_sync" 1 on top of it the files without restart intervals are uploaded as compressed bytes too and
+ * decoded by the self-synchronising kernels in front of the inverse DCT.  Whether such a file converged within
+ * "jpeg_sync_max_rounds" is known only once its chunk has passed the stream: the ones that did not are then decoded by
+ * the host threads, uploaded, and the inverse DCT runs over their frames again.  Same frames, same statuses. */
 int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width,
                                    int height, uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads,
                                    int32_t* h_status);
@@ -608,6 +633,19 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         work of one lane, so a 12 MP file of a single interval is never handed to one lane.
  *   "jpeg_entropy_memset" how the device decoder fills the blocks (same coefficients): 0 (default) = every lane writes its
  *                         blocks in full, zeros included; 1 = the area is zeroed in front and lanes store non-zero values
+ *   "jpeg_sync"           0 (default): files without restart intervals keep the host decoder (status -3 from
+ *                         mrgingham_amd_jpeg_entropy_batch); 1: they are Huffman-decoded on the device by subsequences that
+ *                         synchronise themselves (mrgingham_amd_jpeg_sync_rounds).  The loader looks at it only under
+ *                         "jpeg_entropy" 1.  Same coefficients, frames and statuses.
+ *   "jpeg_sync_subsequence"  raw bytes of entropy-coded data per lane: a multiple of 4 in 8..1024 (default 128, the size with the best
+ *                         loader rate measured at 12 MP: DESIGN.md section 4.10).  Results never depend on it; the rounds a
+ *                         file needs do.
+ *   "jpeg_sync_max_rounds"  0..4096, the update rounds within which a file has to converge to be decoded on the device;
+ *                         0 (default) = 8192 / "jpeg_sync_subsequence".  A condition, not a tuning result: it bounds the
+ *                         launches queued per chunk (this many + 1) at 8 KB of synchronisation distance.
+ *   "jpeg_sync_time_phase"  internal hook of tools/jpeg_huff_bench.py, not part of the interface and free to change: what
+ *                         kernel timing brackets on that path: 0 (default) all its launches, 1 round 0, 2 the update
+ *                         rounds, 3 the scan, 4 the write pass.  Results never depend on it.
  *   "find_boards_pipeline" 1 (default): mrgingham_amd_find_boards_batch / _submit / _collect as described there; 0: the
  *                         synchronous schedule (one level at a time for the whole batch, dense refinement) -- same results
  *   "chess_seg", "chess16_seg"  rows per workgroup of the ChESS kernels of THIS context (chess_v1* / chess_v16; 0 = cost model,

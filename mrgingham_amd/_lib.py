@@ -41,7 +41,7 @@ EXPORTS = [
     "mrgingham_amd_stream_wait_multi", "mrgingham_amd_kernel_id", "mrgingham_amd_set_wait_policy",
     "mrgingham_amd_blobs_batch", "mrgingham_amd_find_circle_grids_batch", "mrgingham_amd_blobs_stats",
     "mrgingham_amd_jpeg_coefficients", "mrgingham_amd_jpeg_idct_batch", "mrgingham_amd_read_jpegs_batch",
-    "mrgingham_amd_jpeg_restart_intervals", "mrgingham_amd_jpeg_entropy_batch",
+    "mrgingham_amd_jpeg_restart_intervals", "mrgingham_amd_jpeg_entropy_batch", "mrgingham_amd_jpeg_sync_rounds",
 ]
 
 
@@ -128,6 +128,8 @@ def lib():
                                                            ctypes.POINTER(ctypes.c_size_t)]
         L.mrgingham_amd_jpeg_entropy_batch.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, ctypes.c_int64, c_int, c_int,
                                                        c_vp, c_vp]
+    if hasattr(L, "mrgingham_amd_jpeg_sync_rounds"):
+        L.mrgingham_amd_jpeg_sync_rounds.argtypes = [c_vp, ctypes.c_size_t, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_size_t)]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]
     L.mrgingham_amd_host_alloc.argtypes = [ctypes.c_size_t]

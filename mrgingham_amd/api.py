@@ -4,6 +4,7 @@ Single-image functions mirror the reference module (names, arguments, error
 behaviour: mrgingham_pywrap.c:40-112 ChESS_response_5, :128-212 find_points).
 `Detector` is the batch interface over device-resident torch tensors.
 """
+import contextlib
 import ctypes
 import os
 
@@ -148,6 +149,29 @@ def jpeg_restart_intervals(data):
     if L.mrgingham_amd_jpeg_restart_intervals(buf, len(buf), ctypes.byref(ri), offsets.ctypes.data, n.value, ctypes.byref(n)) != 0:
         return None
     return ri.value, offsets
+
+
+def jpeg_sync_rounds(data, subsequence=128):
+    """How the self-synchronising decoder of files without restart intervals fares on a baseline JPEG held in memory (host
+    only; mrgingham_amd_jpeg_sync_rounds): the entropy-coded segment cut into subsequences of `subsequence` bytes (a
+    multiple of 4 in 8..1024) -> (rounds, subsequences): the update rounds that change a record before the parallel decode
+    equals the serial one -- the device takes the file iff that is at most option "jpeg_sync_max_rounds" -- and how many
+    subsequences there are.  None when the file is not one this library reads; ValueError for a file that has restart
+    intervals (the device decodes those one lane per interval), for one whose entropy-coded segment has 2^29 bytes or more
+    (left to the host) and for a bad subsequence size."""
+    subsequence = int(subsequence)
+    if subsequence < 8 or subsequence > 1024 or subsequence % 4:
+        raise ValueError("jpeg_sync_rounds: subsequence is a multiple of 4 in 8..1024")
+    buf = bytes(data)
+    rounds, n = ctypes.c_int(), ctypes.c_size_t()
+    rc = _lib.lib().mrgingham_amd_jpeg_sync_rounds(buf, len(buf), subsequence, ctypes.byref(rounds), ctypes.byref(n))
+    if rc == -3:
+        raise ValueError("jpeg_sync_rounds: the file has restart intervals")
+    if rc == -4:
+        raise ValueError("jpeg_sync_rounds: an entropy-coded segment of 2^29 bytes or more is left to the host decoder")
+    if rc != 0:
+        return None
+    return rounds.value, n.value
 
 
 def read_image(filename, cli_scaling=False):
@@ -674,14 +698,33 @@ class Detector:
             out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
         return out[:, :, :width]
 
-    def jpeg_entropy(self, datas, height, width):
+    def _with_options(self, **values):
+        """Context manager: the options set for the duration of a call, and what they were afterwards."""
+        @contextlib.contextmanager
+        def scope():
+            defaults = {"jpeg_entropy": 0, "jpeg_sync": 0}
+            before = {k: self._options.get(k, defaults[k]) for k in values}
+            try:
+                for k, v in values.items():
+                    self.set_option(k, v)
+                yield
+            finally:
+                for k, v in before.items():
+                    self.set_option(k, v)
+        return scope()
+
+    def jpeg_entropy(self, datas, height, width, sync=False):
         """Huffman decode of baseline JPEG files held in memory ON THE DEVICE, one lane per restart interval
         (mrgingham_amd_jpeg_entropy_batch): `datas` are the files' bytes, all height x width.  -> (coef int16
         [B, bh, bw, 64], quant uint16 [B, 64]) device tensors as jpeg_idct takes them -- bh x bw the largest block counts
         any sampling gives the size -- and status int32 [B] (numpy): 0 decoded (what jpeg_coefficients gives, in the top
         left corner of the file's area), -1 unreadable, -2 another size, -3 readable but without restart intervals (or
         longer ones than option "jpeg_entropy_max_interval"): decode those with jpeg_coefficients.  Files whose status is
-        not 0 have zero coefficients and tables.  Synchronous."""
+        not 0 have zero coefficients and tables.  Synchronous.  sync=True: option "jpeg_sync" is 1 for this call (and what
+        it was afterwards) -- files without restart intervals are decoded as well, cut into subsequences of option
+        "jpeg_sync_subsequence" bytes that synchronise themselves; -3 then also means: not within "jpeg_sync_max_rounds"
+        update rounds (jpeg_sync_rounds tells how many a file needs).  sync=False sets the option to 0 for the call, whatever
+        set_option has made it (as read_jpegs treats `entropy`)."""
         t = self.torch
         bufs = [bytes(d) for d in datas]
         B = len(bufs)
@@ -697,20 +740,25 @@ class Detector:
         ptrs = (ctypes.c_char_p * B)(*bufs)
         sizes = (ctypes.c_size_t * B)(*[len(b) for b in bufs])
         t.cuda.current_stream(self.device).synchronize()
-        self._check(self.L.mrgingham_amd_jpeg_entropy_batch(self.ctx, ptrs, sizes, B, int(width), int(height), coef.data_ptr(),
-                                                            bh * bw * 64, bw, bh, quant.data_ptr(), status.ctypes.data))
+        with self._with_options(jpeg_sync=int(bool(sync))):
+            self._check(self.L.mrgingham_amd_jpeg_entropy_batch(self.ctx, ptrs, sizes, B, int(width), int(height), coef.data_ptr(),
+                                                                bh * bw * 64, bw, bh, quant.data_ptr(), status.ctypes.data))
         return coef, quant, status
 
-    def read_jpegs(self, paths, nthreads=0, entropy="host"):
+    def read_jpegs(self, paths, nthreads=0, entropy="host", sync=False):
         """Baseline JPEG files of one size straight into device frames (mrgingham_amd_read_jpegs_batch): `nthreads` host
         threads (0: all cores, at most 32) entropy-decode, the device runs the inverse DCT; the decoded pixels never exist
         on the host.  -> (frames uint8 [B,H,W] on the device, status int32 [B] numpy: 0 decoded, -1 unreadable /
         unsupported / malformed, -2 a JPEG of another size; failed frames are zero).  The size is that of the first file
         whose header parses (none does: frames are [B,0,0]).  Synchronous.  entropy="device": option "jpeg_entropy" is 1
         for this call (and what it was afterwards) -- files with restart intervals are Huffman-decoded on the device as
-        well, the host threads only find their markers; same frames, same statuses."""
+        well, the host threads only find their markers; same frames, same statuses.  sync=True (with entropy="device"):
+        option "jpeg_sync" is 1 for this call as well -- files without restart intervals are Huffman-decoded on the device
+        too (see jpeg_entropy); one that does not converge within the cap is decoded by the host threads afterwards."""
         if entropy not in ("host", "device"):
             raise ValueError('read_jpegs: entropy is "host" or "device"')
+        if sync and entropy != "device":
+            raise ValueError('read_jpegs: sync=True needs entropy="device"')
         t = self.torch
         names = [os.fsencode(p) for p in paths]
         B = len(names)
@@ -730,13 +778,9 @@ class Detector:
             return frames, status
         arr = (ctypes.c_char_p * B)(*names)
         t.cuda.current_stream(self.device).synchronize()
-        before = self._options.get("jpeg_entropy", 0)
-        self.set_option("jpeg_entropy", int(entropy == "device"))
-        try:
+        with self._with_options(jpeg_entropy=int(entropy == "device"), jpeg_sync=int(bool(sync))):
             self._check(self.L.mrgingham_amd_read_jpegs_batch(self.ctx, arr, B, W, H, frames.data_ptr(), H * W, W, int(nthreads),
                                                               status.ctypes.data))
-        finally:
-            self.set_option("jpeg_entropy", before)
         return frames, status
 
     BLOBS_STATS = ("calls", "chunks", "nodes", "contours", "points", "device_ms", "host_ms", "frames")

@@ -172,7 +172,8 @@ static std::vector<DevBuf*> all_buffers(mrgingham_amd_ctx* ctx) {
         for (DevBuf* b : {&j.d_cnt, &j.d_pts, &j.d_pts0}) v.push_back(b);
     for (DevBuf* b : {&ctx->io_counts, &ctx->aux_img, &ctx->io_frame, &ctx->io_out, &ctx->pre_scratch, &ctx->pre_tmp,
                       &ctx->pre_out, &ctx->pre16_scratch, &ctx->io_frame16, &ctx->dbg_img, &ctx->dbg_resp, &ctx->blob_scratch, &ctx->blob_nodes, &ctx->blob_out,
-                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->jpeg_dev[0], &ctx->jpeg_dev[1], &ctx->jpeg_huff_dev[0], &ctx->jpeg_huff_dev[1]})
+                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->jpeg_dev[0], &ctx->jpeg_dev[1], &ctx->jpeg_huff_dev[0], &ctx->jpeg_huff_dev[1],
+                      &ctx->jpeg_sync_dev[0], &ctx->jpeg_sync_dev[1], &ctx->jpeg_sync_rec[0], &ctx->jpeg_sync_rec[1]})
         v.push_back(b);
     return v;
 }
@@ -475,6 +476,7 @@ void mrgingham_amd_destroy(mrgingham_amd_ctx* ctx) {
     for (int k = 0; k < 2; ++k) {
         if (ctx->jpeg_pin[k]) hipHostFree(ctx->jpeg_pin[k]);
         if (ctx->jpeg_huff_pin[k]) hipHostFree(ctx->jpeg_huff_pin[k]);
+        if (ctx->jpeg_sync_pin[k]) hipHostFree(ctx->jpeg_sync_pin[k]);
         if (ctx->jpeg_ev[k]) hipEventDestroy(ctx->jpeg_ev[k]);
     }
     if (ctx->mg_done) hipEventDestroy(ctx->mg_done);
@@ -649,6 +651,26 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
     if (!strcmp(name, "jpeg_entropy_max_interval")) {
         if (value < 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_entropy_max_interval: at least 1 MCU");
         ctx->jpeg_entropy_max_interval = value;
+        return 0;
+    }
+    if (!strcmp(name, "jpeg_sync")) {
+        if (value != 0 && value != 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_sync: 0 (files without restart intervals keep the host decoder) or 1 (the device decodes them)");
+        ctx->jpeg_sync = value;
+        return 0;
+    }
+    if (!strcmp(name, "jpeg_sync_subsequence")) {
+        if (value < 8 || value > 1024 || (value & 3)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_sync_subsequence: bytes, a multiple of 4 in 8..1024");
+        ctx->jpeg_sync_subsequence = value;
+        return 0;
+    }
+    if (!strcmp(name, "jpeg_sync_max_rounds")) {
+        if (value < 0 || value > 4096) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_sync_max_rounds: 0 (8192 / jpeg_sync_subsequence) or 1..4096");
+        ctx->jpeg_sync_max_rounds = value;
+        return 0;
+    }
+    if (!strcmp(name, "jpeg_sync_time_phase")) {
+        if (value < 0 || value > 4) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_sync_time_phase: 0 (all launches) or 1..4 (round 0, update rounds, scan, write pass)");
+        ctx->jpeg_sync_time_phase = value;
         return 0;
     }
     if (!strcmp(name, "jpeg_entropy_memset")) { ctx->jpeg_entropy_memset = value != 0; return 0; }

@@ -206,6 +206,17 @@ struct mrgingham_amd_ctx {
     int jpeg_entropy = 0;
     int jpeg_entropy_max_interval = 1024;
     int jpeg_entropy_memset = 0;
+    // files without restart intervals on the device (jpeg_huff_sync.hip): per chunk slot a staging image of their own
+    // (frame records | tables | compressed bytes || the per-file words that come back) and the device-only records of the
+    // subsequences.  Options "jpeg_sync" (0: such files keep the host decoder), "jpeg_sync_subsequence" (bytes per lane),
+    // "jpeg_sync_max_rounds" (0: 8192 / jpeg_sync_subsequence), "jpeg_sync_time_phase" (tools: what kernel timing brackets)
+    mrg::DevBuf jpeg_sync_dev[2], jpeg_sync_rec[2];
+    void* jpeg_sync_pin[2] = {};
+    size_t jpeg_sync_pin_bytes[2] = {};
+    int jpeg_sync = 0;
+    int jpeg_sync_subsequence = 128;  // (measured: DESIGN.md section 4.10)
+    int jpeg_sync_max_rounds = 0;
+    int jpeg_sync_time_phase = 0;
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
     // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
     // context of THIS context's device, created on first use -- not on the calling thread's default context, which
@@ -339,6 +350,37 @@ int ensure_pin(mrgingham_amd_ctx* ctx, int slot, size_t bytes);
 int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
                               uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status, int bw, int bh,
                               int chunk);
+
+// jpeg_huff_sync.hip: files without restart intervals (option "jpeg_sync"), for the two callers in jpeg_huff.hip
+struct JpegScan;
+struct JpegSyncFile {
+    const uint8_t* data = nullptr;  // the file
+    const JpegScan* scan = nullptr;
+    uint32_t len = 0;  // of its entropy-coded segment (jpeg_sync_plan)
+    int frame = 0;     // which coefficient area of the chunk it decodes into
+    // laid out by jpeg_sync_lay_out
+    int ntables = 0;
+    uint32_t nsub = 0;
+    size_t table_off = 0, rec_first = 0, stream_off = 0;
+};
+struct JpegSyncChunk {
+    std::vector<JpegSyncFile> files;
+    size_t tables = 0, streams = 0, words = 0, total = 0, nrecords = 0, d_spec = 0;
+    uint32_t most = 0;  // subsequences of the longest file
+};
+// does the sync path take this scanned file (option on, no restart intervals, a stream a 32-bit bit offset spans)?
+bool jpeg_sync_plan(const mrgingham_amd_ctx* ctx, const uint8_t* data, size_t nbytes, const JpegScan& sc, uint32_t* len);
+int jpeg_sync_max_rounds(const mrgingham_amd_ctx* ctx);
+// ch->files (data, scan, len, frame) -> where everything lies; grows slot k's buffers
+int jpeg_sync_lay_out(mrgingham_amd_ctx* ctx, int k, JpegSyncChunk* ch);
+// writes file i of the chunk into slot k's staging image (any thread, one per file)
+void jpeg_sync_fill(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int i, int blocks_h, int pitch_blocks);
+// queues the upload, the zeroing of the files' coefficient areas, round 0, the update rounds, the scan, the write pass and
+// the download of the per-file words
+int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int16_t* d_coef, int64_t coef_pitch, size_t area_elems,
+                     hipStream_t s);
+// after the stream has passed the download: 0 decoded, -1 unreadable, -3 not converged within the cap
+int32_t jpeg_sync_status(const mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int i, int* rounds);
 
 // boards.hip
 struct GridScratch { std::vector<PointI> cand; std::vector<PointD> grid; };

@@ -335,6 +335,123 @@ int jpeg_coefficients(const uint8_t* data, size_t nbytes, int16_t* coef, size_t 
     return 0;
 }
 
+void jpeg_lane_setup(const JpegScan& sc, const JpegHuffTable** tables, int* ntables, JpegLaneGeom* g, int blocks_h, int pitch_blocks) {
+    memset(g, 0, sizeof(*g));
+    *ntables = 0;
+    for (int c = 0; c < sc.ncomp; ++c)
+        for (int ac = 0; ac < 2; ++ac) {
+            const JpegHuffTable* t = ac ? &sc.ac[sc.ta[c]] : &sc.dc[sc.td[c]];
+            int s = 0;
+            while (s < *ntables && tables[s] != t) ++s;
+            if (s == *ntables) tables[(*ntables)++] = t;  // (at most 2 * 3)
+            g->slots |= (uint32_t)s << (4 * (ac ? 4 + c : c));
+        }
+    g->ncomp = sc.ncomp;
+    g->H0 = sc.comp_h[0];
+    g->V0 = sc.comp_v[0];
+    g->mcus_x = sc.mcus_x;
+    for (int c = 0; c < sc.ncomp; ++c) g->nblk |= (uint32_t)(sc.comp_h[c] * sc.comp_v[c]) << (8 * c);
+    g->blocks_h = blocks_h;
+    g->pitch_blocks = pitch_blocks;
+}
+
+size_t jpeg_segment_end(const uint8_t* data, size_t nbytes, size_t begin) {
+    size_t e = begin;
+    while (e < nbytes && !(data[e] == 0xFF && !(e + 1 < nbytes && data[e + 1] == 0))) e += data[e] == 0xFF ? 2 : 1;
+    return e;
+}
+
+int jpeg_sync_begin(const uint8_t* data, size_t nbytes, int subsequence, JpegSyncState* st) {
+    if (!st || subsequence < 8 || subsequence > 1024 || (subsequence & 3)) return -1;
+    if (jpeg_scan(data, nbytes, &st->scan)) return -1;
+    const JpegScan& sc = st->scan;
+    if (sc.restart_interval) return -3;
+    const size_t end = jpeg_segment_end(data, nbytes, sc.entropy_begin);
+    if (end - sc.entropy_begin >= kJpegSyncMaxStream) return -4;
+    st->stream = data + sc.entropy_begin;
+    st->len = (uint32_t)(end - sc.entropy_begin);
+    st->subsequence = (uint32_t)subsequence;
+    st->nsub = (st->len + st->subsequence - 1) / st->subsequence;
+    st->total_blocks = (uint32_t)(sc.mcus_x * sc.mcus_y * sc.blocks_per_mcu);
+    if (st->nsub == 0) return -1;  // (no data at all: the first symbol overruns)
+    const JpegHuffTable* named[kJpegLaneTables] = {};
+    jpeg_lane_setup(sc, named, &st->ntables, &st->geom, sc.info.blocks_h, sc.info.blocks_w);
+    for (int s = 0; s < st->ntables; ++s) st->tables[s] = *named[s];
+    st->spec.resize(st->nsub);
+    for (uint32_t i = 0; i < st->nsub; ++i) {
+        const uint32_t begin = i * st->subsequence, stop = begin + st->subsequence < st->len ? begin + st->subsequence : st->len;
+        const uint64_t entry = i ? jpeg_sync_spec_entry(st->stream, st->len, begin) : jpeg_sync_pack(0, 0, 0);
+        jpeg_sync_speculate(st->stream, st->len, stop, entry, st->tables, kNatural, st->geom, &st->spec[i]);
+    }
+    st->cur = st->spec;
+    return 0;
+}
+
+bool jpeg_sync_round(JpegSyncState* st) {
+    std::vector<JpegSyncRecord> next(st->nsub);  // (a round reads only what the round before it wrote)
+    bool changed = false;
+    next[0] = st->cur[0];
+    for (uint32_t i = 1; i < st->nsub; ++i) {
+        const uint32_t begin = i * st->subsequence, stop = begin + st->subsequence < st->len ? begin + st->subsequence : st->len;
+        changed |= jpeg_sync_update(st->stream, st->len, stop, st->cur[i - 1], st->cur[i], st->spec[i], st->tables, kNatural, st->geom, &next[i]);
+    }
+    st->cur.swap(next);
+    return changed;
+}
+
+int jpeg_sync_finish(const JpegSyncState& st, int16_t* coef, size_t coef_capacity, int row_pitch_blocks) {
+    const JpegInfo& info = st.scan.info;
+    const int pitch = row_pitch_blocks > 0 ? row_pitch_blocks : info.blocks_w;
+    if (!coef || pitch < info.blocks_w || coef_capacity / 64 / (size_t)pitch < (size_t)info.blocks_h) return -2;
+    JpegLaneGeom g = st.geom;
+    g.pitch_blocks = pitch;
+    // the scan: every subsequence's first block and predictors; nothing behind the first failed one is looked at
+    std::vector<JpegSyncStart> start(st.nsub);
+    uint64_t cum = 0;
+    int64_t pred[3] = {0, 0, 0};
+    bool dead = false, reached = false;
+    for (uint32_t i = 0; i < st.nsub; ++i) {
+        const JpegSyncRecord& r = st.cur[i];
+        start[i].first_block = dead || cum > st.total_blocks ? st.total_blocks : (uint32_t)cum;
+        for (int c = 0; c < 3; ++c) start[i].pred[c] = (int32_t)(pred[c] < -(1 << 30) ? -(1 << 30) : pred[c] > (1 << 30) ? (1 << 30) : pred[c]);
+        if (dead) continue;
+        const bool fallback = (r.blocks & kJpegSyncFallback) != 0;
+        const uint32_t count = fallback ? (r.blocks >> 16) & 0x7FFFu : r.blocks & 0xFFFFu;
+        if (cum < st.total_blocks && cum + count >= st.total_blocks) reached = true;
+        cum += count;
+        for (int c = 0; c < 3; ++c) pred[c] += r.dc[c];
+        dead = fallback;
+    }
+    if (!reached) return -1;
+    for (int by = 0; by < info.blocks_h; ++by) memset(coef + (size_t)by * pitch * 64, 0, (size_t)info.blocks_w * 64 * sizeof(int16_t));
+    int flags = 0;
+    for (uint32_t i = st.nsub; i-- > 0;) {  // (in reverse: the lanes are independent)
+        if (start[i].first_block >= st.total_blocks) continue;
+        const uint32_t begin = i * st.subsequence, stop = begin + st.subsequence < st.len ? begin + st.subsequence : st.len;
+        const uint64_t entry = i ? st.cur[i - 1].exit : jpeg_sync_pack(0, 0, 0);
+        if (entry & kJpegSyncFailed) { flags |= 2; continue; }
+        JpegSyncRecord unused;
+        flags |= jpeg_sync_lane<true>(st.stream, st.len, stop, entry, st.tables, kNatural, g, start[i], st.total_blocks, coef, &unused);
+    }
+    return (flags & 2) || !(flags & 1) ? -1 : 0;
+}
+
+int jpeg_sync_decode(const uint8_t* data, size_t nbytes, int subsequence, int max_rounds, int16_t* coef, size_t coef_capacity,
+                     int row_pitch_blocks, JpegInfo* info, int* rounds, size_t* nsubsequences) {
+    JpegSyncState st;
+    if (rounds) *rounds = -1;
+    if (nsubsequences) *nsubsequences = 0;
+    const int rc = jpeg_sync_begin(data, nbytes, subsequence, &st);
+    if (info) *info = st.scan.info;
+    if (rc) return rc;
+    if (nsubsequences) *nsubsequences = st.nsub;
+    int t = 0;  // update rounds that changed a record
+    while (jpeg_sync_round(&st))
+        if (++t > max_rounds) return -3;
+    if (rounds) *rounds = t;
+    return jpeg_sync_finish(st, coef, coef_capacity, row_pitch_blocks);
+}
+
 void jpeg_idct_host(const int16_t* coef, int row_pitch_blocks, const JpegInfo& info, uint8_t* out) {
     const int pitch = row_pitch_blocks > 0 ? row_pitch_blocks : info.blocks_w;
     const int bw = (info.width + 7) / 8, bh = (info.height + 7) / 8;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "jpeg_huff_lane.h"
+#include "jpeg_huff_sync.h"
 
 namespace mrg {
 
@@ -54,6 +55,37 @@ struct JpegScan {
 // data is only searched for markers.  0, or -1: jpeg_coefficients calls the file unreadable as well (the converse does
 // not hold: an interval may still fail to decode).
 int jpeg_scan(const uint8_t* data, size_t nbytes, JpegScan* scan);
+
+// A file without restart intervals, decoded as the device decodes it (jpeg_huff_sync.hip): the schedule of
+// jpeg_huff_sync.h -- round 0, update rounds until one changes nothing, the scan, the write pass -- restated serially.
+struct JpegSyncState {
+    JpegScan scan;
+    const uint8_t* stream = nullptr;  // the entropy-coded segment, up to its first marker (inside the caller's data)
+    uint32_t len = 0, subsequence = 0, nsub = 0, total_blocks = 0;
+    int ntables = 0;
+    JpegHuffTable tables[kJpegLaneTables];
+    JpegLaneGeom geom;
+    std::vector<JpegSyncRecord> spec, cur;  // round 0; the last round's records
+};
+
+// What a lane needs of a scanned file: the tables its scan names (each once, at most kJpegLaneTables: tables[s] points
+// into `sc`) and the geometry, for a coefficient area of blocks_h x pitch_blocks blocks.
+void jpeg_lane_setup(const JpegScan& sc, const JpegHuffTable** tables, int* ntables, JpegLaneGeom* g, int blocks_h, int pitch_blocks);
+// Where the entropy-coded segment that begins at sc.entropy_begin ends: the first FF that no 00 follows, or the end of the file.
+size_t jpeg_segment_end(const uint8_t* data, size_t nbytes, size_t begin);
+
+// Marker parse, the cut into subsequences of `subsequence` bytes (a multiple of 4 in 8..1024) and round 0.  0; -1 the
+// file is unreadable; -3 it has restart intervals; -4 its stream is too long for a 32-bit bit offset.
+int jpeg_sync_begin(const uint8_t* data, size_t nbytes, int subsequence, JpegSyncState* st);
+// One update round over all records.  Returns whether any record changed.
+bool jpeg_sync_round(JpegSyncState* st);
+// The scan and the write pass over the records as they stand (only meaningful after a round that changed nothing): coef
+// as for jpeg_coefficients, every block of the file written.  0, -1 unreadable, -2 coef_capacity / row_pitch_blocks too small.
+int jpeg_sync_finish(const JpegSyncState& st, int16_t* coef, size_t coef_capacity, int row_pitch_blocks);
+// The whole schedule with at most max_rounds changing rounds.  0 (coef and *info as jpeg_coefficients gives them), -1
+// unreadable, -2 as above, -3 restart intervals / not converged within max_rounds, -4 too long (*rounds: -1 then).
+int jpeg_sync_decode(const uint8_t* data, size_t nbytes, int subsequence, int max_rounds, int16_t* coef, size_t coef_capacity,
+                     int row_pitch_blocks, JpegInfo* info, int* rounds, size_t* nsubsequences);
 
 // The inverse DCT of every block into out (info.width x info.height bytes, dense); coef laid out as above.
 void jpeg_idct_host(const int16_t* coef, int row_pitch_blocks, const JpegInfo& info, uint8_t* out);

@@ -1,7 +1,8 @@
 // Baseline JPEG on the device, the entropy half: the restart intervals of a file are independent streams (byte aligned,
 // DC predictors reset), so one lane Huffman-decodes one interval -- jpeg_huff_lane.h, the text the host runs under the
 // sanitizers -- and the coefficients are born in HBM, where jpeg_idct_kernel expects them.  The host only finds the
-// markers (jpeg_scan) and uploads the compressed bytes.  Files without restart intervals keep the host decoder.  See
+// markers (jpeg_scan) and uploads the compressed bytes.  Files without restart intervals keep the host decoder, or,
+// under option "jpeg_sync", go through the self-synchronising decoder of jpeg_huff_sync.hip.  See
 // include/mrgingham_amd.h for the contract of mrgingham_amd_jpeg_entropy_batch and of option "jpeg_entropy", and
 // DESIGN.md section 4.10 for the layout and the measured figures.
 #include <string.h>
@@ -76,16 +77,23 @@ struct FileJob {
     size_t stream_bytes = 0;  // padded
     // where it lies in the staging image
     size_t stream_off = 0, table_off = 0, interval_first = 0;
+    // status -3 and no restart intervals, option "jpeg_sync" on: jpeg_huff_sync.hip takes it, as file `sync` of the chunk's
+    // JpegSyncChunk (-1: not)
+    int sync = -1;
+    uint32_t sync_len = 0;
 };
 
 // 0 the device takes it, -1 unreadable, -2 another size, -3 readable but the host has to decode it
-void plan_file(FileJob& j, int width, int height, int blocks_w, int blocks_h, int max_interval) {
+void plan_file(const mrgingham_amd_ctx* ctx, FileJob& j, int width, int height, int blocks_w, int blocks_h) {
+    const int max_interval = ctx->jpeg_entropy_max_interval;
     j.status = -1;
     j.ntables = 0;
+    j.sync = -1;
     if (!j.data || jpeg_scan(j.data, j.nbytes, &j.scan)) return;
     const JpegScan& sc = j.scan;
     if (sc.info.width != width || sc.info.height != height || sc.info.blocks_w > blocks_w || sc.info.blocks_h > blocks_h) { j.status = -2; return; }
     j.status = -3;
+    if (jpeg_sync_plan(ctx, j.data, j.nbytes, sc, &j.sync_len)) j.sync = 0;  // (numbered by sync_files)
     if (!sc.restart_interval || sc.restart_interval > (unsigned)max_interval || j.nbytes >= 0xFFFFFFF0u) return;
     j.slots = 0;
     for (int c = 0; c < sc.ncomp; ++c)
@@ -171,6 +179,23 @@ void fill_image(char* image, const Layout& l, const FileJob& j, int i, int block
     memcpy(image + j.stream_off, j.data + sc.entropy_begin, len);
     memset(image + j.stream_off + len, 0, j.stream_bytes - len);
     memset(image + l.status + j.interval_first, 0, (size_t)fr.nintervals);
+}
+
+// the files of a chunk that the sync path takes, numbered in order, and where they lie in slot k's buffers of that path
+int sync_files(mrgingham_amd_ctx* ctx, int k, FileJob* jobs, int n, JpegSyncChunk* ch) {
+    ch->files.clear();
+    for (int i = 0; i < n; ++i) {
+        FileJob& j = jobs[i];
+        if (j.sync < 0) continue;
+        j.sync = (int)ch->files.size();
+        JpegSyncFile f;
+        f.data = j.data;
+        f.scan = &j.scan;
+        f.len = j.sync_len;
+        f.frame = i;
+        ch->files.push_back(f);
+    }
+    return ch->files.empty() ? 0 : jpeg_sync_lay_out(ctx, k, ch);
 }
 
 int ensure_image(mrgingham_amd_ctx* ctx, int slot, size_t bytes) {
@@ -261,18 +286,58 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
     std::vector<FileJob> jobs[2];
     std::vector<std::vector<uint8_t>> files[2];
     Layout lay[2];
+    JpegSyncChunk sync[2];
     int first[2] = {0, 0}, count[2] = {0, 0};
     bool busy[2] = {false, false};
     // the chunk in slot k has passed the stream: its status bytes are on the host.  A file with a failed interval is
     // unreadable, and its frame is zeroed behind the transform that has run over it.
+    // A file of the sync path whose write pass failed is unreadable as well; one that did not converge within the cap is
+    // known only now: the pool threads decode those, their coefficient slices are uploaded and the transform runs over
+    // their frames again (the table is in the image already).
     auto finish = [&](int k) -> int {
         MRG_HIP_CHECK(hipEventSynchronize(ctx->jpeg_ev[k]));
         busy[k] = false;
-        for (int i = 0; i < count[k]; ++i)
-            if (jobs[k][i].status == 0 && !all_decoded((const char*)ctx->jpeg_huff_pin[k], lay[k], jobs[k][i])) {
+        std::vector<int> late;
+        for (int i = 0; i < count[k]; ++i) {
+            const FileJob& j = jobs[k][i];
+            int32_t st = 0;
+            if (j.status == 0) st = all_decoded((const char*)ctx->jpeg_huff_pin[k], lay[k], j) ? 0 : -1;
+            else if (j.sync >= 0) st = jpeg_sync_status(ctx, k, sync[k], j.sync, nullptr);
+            if (st == -3) late.push_back(i);
+            if (st == -1) {
                 h_status[first[k] + i] = -1;
                 MRG_HIP_CHECK(hipMemset2DAsync(d_out + (size_t)(first[k] + i) * frame_pitch, (size_t)stride, 0, (size_t)width, (size_t)height, s));
             }
+        }
+        if (late.empty()) return 0;
+        int rc;
+        if ((rc = ensure_pin(ctx, k, slot_bytes))) return rc;
+        int16_t* h_coef = (int16_t*)ctx->jpeg_pin[k];
+        std::atomic<int> next{0};
+        const int nlate = (int)late.size();
+        auto decode = [&]() {
+            for (int q; (q = next.fetch_add(1)) < nlate;) {
+                const int i = late[(size_t)q];
+                const FileJob& j = jobs[k][i];
+                JpegInfo info;
+                h_status[first[k] + i] = jpeg_coefficients(j.data, j.nbytes, h_coef + (size_t)i * per_frame, per_frame, bw, &info) == 0 ? 0 : -1;
+            }
+        };
+        ctx->pool.run(nthreads < nlate ? nthreads : nlate, decode);
+        char* dev = (char*)ctx->jpeg_dev[k].p;
+        const uint16_t* d_quant = (const uint16_t*)((char*)ctx->jpeg_huff_dev[k].p + lay[k].quant);
+        for (int i : late) {
+            uint8_t* frame = d_out + (size_t)(first[k] + i) * frame_pitch;
+            if (h_status[first[k] + i] != 0) {
+                MRG_HIP_CHECK(hipMemset2DAsync(frame, (size_t)stride, 0, (size_t)width, (size_t)height, s));
+                continue;
+            }
+            int16_t* d_slice = (int16_t*)dev + (size_t)i * per_frame;
+            MRG_HIP_CHECK(hipMemcpyAsync(d_slice, h_coef + (size_t)i * per_frame, per_frame * sizeof(int16_t), hipMemcpyHostToDevice, s));
+            launch_jpeg_idct(d_slice, (int64_t)per_frame, d_quant + (size_t)i * 64, 1, width, height, bw, frame, frame_pitch, stride, s);
+        }
+        MRG_HIP_CHECK(hipGetLastError());
+        MRG_HIP_CHECK(hipStreamSynchronize(s));  // (the slot's staging is filled again next)
         return 0;
     };
     for (int f0 = 0, k = 0; f0 < nfiles; f0 += chunk, k ^= nslots - 1) {
@@ -293,7 +358,7 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
                         j.data = files[k][i].data();
                         j.nbytes = files[k][i].size();
                     }
-                    plan_file(j, width, height, bw, bh, ctx->jpeg_entropy_max_interval);
+                    plan_file(ctx, j, width, height, bw, bh);
                 } catch (...) {  // std::bad_alloc on a file too large to hold
                     j.status = -1;
                 }
@@ -302,8 +367,9 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
         ctx->pool.run(nthreads < n ? nthreads : n, scan);
         lay[k] = lay_out(jobs[k].data(), n);
         if ((rc = ensure_image(ctx, k, lay[k].total))) return rc;
+        if ((rc = sync_files(ctx, k, jobs[k].data(), n, &sync[k]))) return rc;
         int nhost = 0;
-        for (int i = 0; i < n; ++i) nhost += jobs[k][i].status == -3;
+        for (int i = 0; i < n; ++i) nhost += jobs[k][i].status == -3 && jobs[k][i].sync < 0;
         if (nhost && (rc = ensure_pin(ctx, k, slot_bytes))) return rc;
         // 2. the files the device takes go into the image; 3. the others are decoded by the same threads as without the
         // option, into the coefficient staging
@@ -314,7 +380,10 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
             for (int i; (i = next.fetch_add(1)) < n;) {
                 FileJob& j = jobs[k][i];
                 int32_t st = j.status;
-                if (st == -3) {
+                if (j.sync >= 0) {  // (decoded unless finish() finds otherwise)
+                    jpeg_sync_fill(ctx, k, sync[k], j.sync, bh, bw);
+                    st = 0;
+                } else if (st == -3) {
                     JpegInfo info;
                     st = jpeg_coefficients(j.data, j.nbytes, h_coef + (size_t)i * per_frame, per_frame, bw, &info) == 0 ? 0 : -1;
                 }
@@ -326,10 +395,11 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
         ctx->pool.run(nthreads < n ? nthreads : n, fill);
         char* dev = (char*)ctx->jpeg_dev[k].p;
         for (int i = 0; i < n; ++i)  // only the slices the host has decoded are uploaded as coefficients
-            if (jobs[k][i].status == -3 && h_status[f0 + i] == 0)
+            if (jobs[k][i].status == -3 && jobs[k][i].sync < 0 && h_status[f0 + i] == 0)
                 MRG_HIP_CHECK(hipMemcpyAsync(dev + (size_t)i * per_frame * sizeof(int16_t), h_coef + (size_t)i * per_frame,
                                              per_frame * sizeof(int16_t), hipMemcpyHostToDevice, s));
         if ((rc = queue_huff(ctx, k, lay[k], jobs[k].data(), n, (int16_t*)dev, (int64_t)per_frame, per_frame, false, s))) return rc;
+        if ((rc = jpeg_sync_launch(ctx, k, sync[k], (int16_t*)dev, (int64_t)per_frame, per_frame, s))) return rc;
         launch_jpeg_idct((const int16_t*)dev, (int64_t)per_frame, (const uint16_t*)((char*)ctx->jpeg_huff_dev[k].p + lay[k].quant), n, width,
                          height, bw, d_out + (size_t)f0 * frame_pitch, frame_pitch, stride, s);
         MRG_HIP_CHECK(hipGetLastError());
@@ -401,7 +471,7 @@ int mrgingham_amd_jpeg_entropy_batch(mrgingham_amd_ctx* ctx, const uint8_t* cons
                 jobs[i].data = data[f0 + i];
                 jobs[i].nbytes = nbytes[f0 + i];
                 try {
-                    plan_file(jobs[i], width, height, blocks_w, blocks_h, ctx->jpeg_entropy_max_interval);
+                    plan_file(ctx, jobs[i], width, height, blocks_w, blocks_h);
                 } catch (...) {
                     jobs[i].status = -1;
                 }
@@ -411,21 +481,32 @@ int mrgingham_amd_jpeg_entropy_batch(mrgingham_amd_ctx* ctx, const uint8_t* cons
         const Layout l = lay_out(jobs.data(), n);
         int rc;
         if ((rc = ensure_image(ctx, 0, l.total))) return rc;
+        JpegSyncChunk sync;
+        if ((rc = sync_files(ctx, 0, jobs.data(), n, &sync))) return rc;
         char* image = (char*)ctx->jpeg_huff_pin[0];
         next = 0;
         auto fill = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) fill_image(image, l, jobs[i], i, blocks_h, blocks_w);
+            for (int i; (i = next.fetch_add(1)) < n;) {
+                fill_image(image, l, jobs[i], i, blocks_h, blocks_w);
+                if (jobs[i].sync < 0) continue;  // (its table goes up with the others; taken back below if it fails)
+                jpeg_sync_fill(ctx, 0, sync, jobs[i].sync, blocks_h, blocks_w);
+                memcpy((uint16_t*)(image + l.quant) + (size_t)i * 64, jobs[i].scan.info.quant, 64 * sizeof(uint16_t));
+            }
         };
         ctx->pool.run(nthreads < n ? nthreads : n, fill);
         int16_t* coef = d_coef + (size_t)f0 * (size_t)coef_pitch;
         if ((rc = queue_huff(ctx, 0, l, jobs.data(), n, coef, coef_pitch, area, true, s))) return rc;
+        if ((rc = jpeg_sync_launch(ctx, 0, sync, coef, coef_pitch, area, s))) return rc;
         MRG_HIP_CHECK(hipMemcpyAsync(d_quant + (size_t)f0 * 64, image + l.quant, (size_t)n * 64 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         MRG_HIP_CHECK(hipStreamSynchronize(s));
         bool again = false;
         for (int i = 0; i < n; ++i) {
             int32_t st = jobs[i].status;
-            if (st == 0 && !all_decoded(image, l, jobs[i])) {  // unreadable after all: no half-decoded coefficients, no table
-                st = -1;
+            const int32_t synced = jobs[i].sync >= 0 ? jpeg_sync_status(ctx, 0, sync, jobs[i].sync, nullptr) : 0;
+            if (jobs[i].sync >= 0 && synced == 0) st = 0;
+            if ((st == 0 && jobs[i].sync < 0 && !all_decoded(image, l, jobs[i])) || synced != 0) {
+                // unreadable after all (or not converged within the cap: -3 stays): no half-decoded coefficients, no table
+                st = synced ? synced : -1;
                 MRG_HIP_CHECK(hipMemsetAsync(coef + (size_t)i * (size_t)coef_pitch, 0, area * sizeof(int16_t), s));
                 MRG_HIP_CHECK(hipMemsetAsync(d_quant + (size_t)(f0 + i) * 64, 0, 64 * sizeof(uint16_t), s));
                 again = true;

@@ -17,6 +17,20 @@ times, in one process on one box:
            per second, best and median of three calls after a warm-up one of each;
   upload   bytes per frame that cross the link on either path (host: 2 B per coefficient of the padded block area + the
            table; device: the staging image -- records, tables, interval offsets, compressed bytes).
+One JSON document.
+
+    python tools/jpeg_huff_bench.py --sync --file nodri.jpg --file nodri420.jpg [--frames 64] [--launches 30]
+                                    [--out profiles/jpeg_sync_bench.json]
+
+The files WITHOUT restart intervals through the self-synchronising decoder (option "jpeg_sync"; --make writes the board
+in grey, nodri.jpg, and in 4:2:0, nodri420.jpg).  Per file and per subsequence size S in 32, 64, 128:
+  rounds   what mrgingham_amd.jpeg_sync_rounds counts, and the subsequences;
+  kernels  hipEvents around round 0, the update rounds (cap + 1 launches), the scan and the write pass, each alone
+           (option "jpeg_sync_time_phase") and around all of them, of one Detector.jpeg_entropy(sync=True) call over the
+           batch: median of --launches calls after three warm-up ones;
+  loader   Detector.read_jpegs at 1 / 4 / 16 host threads with entropy="host" and entropy="device", sync=True,
+           alternating in one process: frames per second, best and median of three calls after a warm-up one of each;
+  upload   bytes per frame that cross the link on either path.
 One JSON document."""
 import json
 import os
@@ -40,7 +54,8 @@ def make(out_dir):
     img.save(os.path.join(out_dir, "rows.jpg"), "JPEG", quality=90, restart_marker_rows=1)
     img.save(os.path.join(out_dir, "dri8.jpg"), "JPEG", quality=90, restart_marker_blocks=8)
     img.save(os.path.join(out_dir, "nodri.jpg"), "JPEG", quality=90)
-    for n in ("rows.jpg", "dri8.jpg", "nodri.jpg"):
+    img.convert("RGB").save(os.path.join(out_dir, "nodri420.jpg"), "JPEG", quality=90, subsampling=2)
+    for n in ("rows.jpg", "dri8.jpg", "nodri.jpg", "nodri420.jpg"):
         print(n, os.path.getsize(os.path.join(out_dir, n)))
 
 
@@ -63,10 +78,92 @@ def symbols_of(coef):
     return total
 
 
+def loader_legs(det, paths, B, ways):
+    """ways: {name: read_jpegs keywords}, alternating -> {"threads_N": {name: {best, median}, ...}}"""
+    out = {}
+    for n in (1, 4, 16):
+        legs = {w: [] for w in ways}
+        for w, kw in ways.items():
+            det.read_jpegs(paths, nthreads=n, **kw)          # warm-up
+        for _ in range(1 if n == 1 else 3):
+            for w, kw in ways.items():
+                t0 = time.perf_counter()
+                det.read_jpegs(paths, nthreads=n, **kw)
+                legs[w].append(time.perf_counter() - t0)
+        out[f"threads_{n}"] = {w: {"frames_per_s_best": round(B / min(v), 1), "frames_per_s_median": round(B / statistics.median(v), 1)}
+                               for w, v in legs.items()}
+    return out
+
+
+def sync_main(args):
+    import torch
+    import mrgingham_amd
+    files = opts(args, "--file")
+    B = int((opts(args, "--frames") or ["64"])[0])
+    launches = int((opts(args, "--launches") or ["30"])[0])
+    out_path = (opts(args, "--out") or [os.path.join(ROOT, "profiles", "jpeg_sync_bench.json")])[0]
+    det = mrgingham_amd.Detector(0)
+    doc = {"frames": B, "device": torch.cuda.get_device_name(0), "files": {}}
+    phases = ("all", "round0", "rounds", "scan", "write")
+    for path in files:
+        data = open(path, "rb").read()
+        coef, quant, (H, W) = mrgingham_amd.jpeg_coefficients(data)
+        want = mrgingham_amd.read_image(path)
+        padded = lambda side: max(-(-side // (8 * h)) * h for h in (1, 2, 3, 4))      # noqa: E731
+        sos = data.index(b"\xff\xda")
+        stream = len(data) - 2 - (sos + 2 + int.from_bytes(data[sos + 2:sos + 4], "big"))
+        ntables = 2 if b"\xff\xc0\x00\x0b" in data else 4                       # (SOF0 of one component: grey)
+        host_upload = padded(H) * padded(W) * 64 * 2 + 128
+        # the sync path's own image: record (80) + Huffman tables + the padded stream; the other image: record (64) + table (128)
+        dev_upload = 80 + ntables * 1424 + ((stream + 3) & ~3) + 4 + 64 + 128
+        entry = {"file_bytes": len(data), "width": W, "height": H, "entropy_bytes": stream,
+                 "upload_bytes_per_frame": {"host": host_upload, "device": dev_upload, "host_over_device": round(host_upload / dev_upload, 2)},
+                 "subsequence": {}}
+        for S in (32, 64, 128):
+            rounds, nsub = mrgingham_amd.jpeg_sync_rounds(data, S)
+            leg = {"rounds": rounds, "subsequences": nsub, "cap": 8192 // S}
+            det.set_option("jpeg_sync_subsequence", S)
+            det.set_kernel_timing(1)
+            det.chess_kernel_ms()
+            for phase, name in enumerate(phases):
+                det.set_option("jpeg_sync_time_phase", phase)
+                us = []
+                for k in range(3 + launches):
+                    d_coef, d_quant, status = det.jpeg_entropy([data] * B, H, W, sync=True)
+                    ms, n = det.chess_kernel_ms()
+                    assert n == 1 and (status == 0).all(), (n, status)
+                    if k >= 3:
+                        us.append(ms * 1e3)
+                leg[f"us_per_batch_{name}"] = {"median": round(statistics.median(us), 1), "min": round(min(us), 1), "max": round(max(us), 1)}
+            det.set_option("jpeg_sync_time_phase", 0)
+            det.set_kernel_timing(0)
+            leg["equals_host_decoder"] = bool((d_coef[B - 1, :coef.shape[0], :coef.shape[1]].cpu().numpy() == coef).all())
+            leg["compressed_bytes_per_s"] = round(stream * B / (leg["us_per_batch_all"]["median"] * 1e-6))
+            del d_coef, d_quant
+            paths = [path] * B
+            leg["loader"] = loader_legs(det, paths, B, {"host": dict(entropy="host"), "sync": dict(entropy="device", sync=True)})
+            for e in leg["loader"].values():
+                e["sync_over_host_median"] = round(e["sync"]["frames_per_s_median"] / e["host"]["frames_per_s_median"], 3)
+            frames, status = det.read_jpegs(paths, nthreads=16, entropy="device", sync=True)
+            leg["loader"]["equals_host_decoder"] = bool((status == 0).all() and (frames[B // 2].cpu().numpy() == want).all()
+                                                        and (frames[B - 1].cpu().numpy() == want).all())
+            entry["subsequence"][str(S)] = leg
+            print(os.path.basename(path), S, json.dumps(leg), flush=True)
+        det.set_option("jpeg_sync_subsequence", 32)
+        doc["files"][os.path.basename(path)] = entry
+    det.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(json.dumps(doc, indent=1) + "\n")
+    print("wrote", out_path)
+
+
 def main():
     args = sys.argv[1:]
     if "--make" in args:
         return make(opts(args, "--make")[0])
+    if "--sync" in args:
+        return sync_main(args)
     import numpy as np
     import torch
     import mrgingham_amd
