@@ -170,6 +170,20 @@ __device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
                                                                   __builtin_bit_cast(i16x2, b)));
 }
 
+// (a | b | c | d) & m in two full-rate v_bitop3_b32 (gfx950; v_or3_b32 and v_and_or_b32 issue at half rate).
+// The truth-table byte of an expression is the expression over a = 0xf0, b = 0xcc, c = 0xaa.
+__device__ __forceinline__ uint32_t or3_and(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t m) {
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    const uint32_t abc = __builtin_amdgcn_bitop3_b32(a, b, c, 0xf0 | 0xcc | 0xaa);
+    return __builtin_amdgcn_bitop3_b32(abc, d, m, (0xf0 | 0xcc) & 0xaa);
+#else
+    uint32_t abc, r;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xfe" : "=v"(abc) : "v"(a), "v"(b), "v"(c));
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xa8" : "=v"(r) : "v"(abc), "v"(d), "v"(m));
+    return r;
+#endif
+}
+
 struct StageRegs {
     uint4 g;        // 16 pixels
     uint32_t next;  // byte 0 = the pixel after them
@@ -415,11 +429,25 @@ __device__ __forceinline__ void emit_pyramid_rows(const char* lds, int y, int st
 // The responses of pixel pair k (0..3) of a lane's aligned 8-pixel group out of its window registers: rows -5, +5,
 // -4, +4 of plane P0 (pairs that start at an even pixel), rows -2, +2 and the centre row of plane P1 (pairs that
 // start at an odd pixel), 12 registers each = pixels x0 - 8 .. x0 + 15, and the centre row's own pairs z0.
-// Returns response + 8192 in each half.
+// Returns response + 2 * (a half of `ybias`) in each half: response + 8192 with the default kYBias.
+//
+// Ranges, per 16-bit half: the sum response is <= 4 * 510 and the difference response <= 8 * 255, so
+// 2 * (Y - X) = SR - DR lies in [-2040, 2040] and Y - X >= -1020; |M - LM| <= 4080 (M <= 16 * 255, LM <= 4080); the
+// response lies in [-6120, 2040].  The bias on Y has to keep Yb - X positive (any bias above 1020 does) and the biased
+// result positive (a bias above 3060 does), so no borrow ever crosses from one half into the other.
+//
+// The row mask of the CLAMP kernels rides on that bias: a row of the zeroed 7-pixel frame takes kYBiasFrameRow
+// (3072 per half) where a row inside it takes kYBias (4096).  The biased result of a frame row is then
+// response + 6144, in [24, 8184] -- still positive, no borrow -- and the saturating subtraction that strips the bias
+// from a CLAMP result takes off at least 8192 (the column mask: 0x2000 inside the frame columns, 0xffff outside):
+// every pixel of a frame row saturates to exactly 0, which is what masking the row gave.  Rows inside the frame are
+// computed as before, bit for bit.
+constexpr uint32_t kYBias = 0x10001000u, kYBiasFrameRow = 0x0C000C00u;
 __device__ __forceinline__ uint32_t response_pair_biased(const uint32_t (&m5)[12], const uint32_t (&p5)[12],
                                                          const uint32_t (&m4)[12], const uint32_t (&p4)[12],
                                                          const uint32_t (&m2)[12], const uint32_t (&p2)[12],
-                                                         const uint32_t (&z1)[12], const uint32_t (&z0)[4], int k) {
+                                                         const uint32_t (&z1)[12], const uint32_t (&z0)[4], int k,
+                                                         uint32_t ybias = kYBias) {
     const int c = 4 + k;
     // quadruples (a,b,c,d) = (s[i], s[i+4], s[i+8], s[i+12]); ring offsets from ChESS.c:68-83
     const uint32_t a0 = m5[c + 1], c0 = p5[c - 1], b0 = m2[c - 3], d0 = p2[c + 2];
@@ -432,9 +460,9 @@ __device__ __forceinline__ uint32_t response_pair_biased(const uint32_t (&m5)[12
     const uint32_t t10 = a0 + c0, t20 = b0 + d0, t11 = a1 + c1, t21 = b1 + d1;
     const uint32_t t12 = a2 + c2, t22 = b2 + d2, t13 = a3 + c3, t23 = b3 + d3;
     const uint32_t M = ((t10 + t20) + (t11 + t21)) + ((t12 + t22) + (t13 + t23));
-    // Y carries a +4096 bias per half so that Y - X (>= -2040) stays positive
+    // Y carries a bias per half (+4096, or +3072 in a frame row: see above) so that Y - X (>= -1020) stays positive
     const uint32_t Yb = ((pk_max_u16(t10, t20) + pk_max_u16(t11, t21)) +
-                         (pk_max_u16(t12, t22) + pk_max_u16(t13, t23))) + 0x10001000u;
+                         (pk_max_u16(t12, t22) + pk_max_u16(t13, t23))) + ybias;
     const uint32_t X = ((pk_max_u16(a0, c0) + pk_max_u16(b0, d0)) + (pk_max_u16(a1, c1) + pk_max_u16(b1, d1))) +
                        ((pk_max_u16(a2, c2) + pk_max_u16(b2, d2)) + (pk_max_u16(a3, c3) + pk_max_u16(b3, d3)));
     // local_mean = (I[x-1]+I[x]+I[x+1])*16/3, truncating (ChESS.c:86): floor(16n/3) = (n*349536)>>16, n <= 765
@@ -444,10 +472,14 @@ __device__ __forceinline__ uint32_t response_pair_biased(const uint32_t (&m5)[12
     const uint32_t LM = __builtin_amdgcn_perm(lm_hi, lm_lo, 0x07060302u);
     const uint32_t dev = pk_max_u16(M, LM) - pk_min_u16(M, LM);  // |M - LM| per half
     const uint32_t d1x = Yb - X;
-    return (d1x + d1x) - dev;  // halves = response + 8192, in [2072, 10232]  (ChESS.c:104)
+    return (d1x + d1x) - dev;  // halves = response + 8192, in [2072, 10232]; in a frame row + 6144, in [24, 8184]  (ChESS.c:104)
 }
 
-template <bool CLAMP, bool HOT, int STAGE, bool PYR = false, bool FILTER = false>
+// WHOLE: the frame is whole 8-pixel groups wide and whole 8-row granules tall (w % 8 == 0, h % V1_RB == 0).  Then
+// segment_rows hands out whole granules, every row of every iteration is a row of the segment (`yy < ye` always
+// holds), and a lane's group of 8 pixels is either wholly inside the frame or wholly outside: the per-iteration
+// row tests and the scalar tail of the response store are compiled out.
+template <bool CLAMP, bool HOT, int STAGE, bool PYR = false, bool FILTER = false, bool WHOLE = false>
 __device__ __forceinline__ void chess_v1_body(const LevelBatch& lb, const CompTables& t, int frame0, int nsegs, unsigned bid,
                                               unsigned nwg_level, char* lds, const PyramidOut* po = nullptr) {
     // XCD-aware work order: workgroup b is dispatched to XCD b % 8 (observed, used
@@ -556,8 +588,12 @@ __device__ __forceinline__ void chess_v1_body(const LevelBatch& lb, const CompTa
     // half-waves get separately wrapped uniform slots, selected with a mask.
     const uint32_t lane_off = 16u + 16u * lx;                      // D[-4] of the lane within a row
     const uint32_t lane_off_h = lane_off + (half ? V1_ROWB : 0u);  // + the half-wave's row
-    const uint32_t halfmask = half ? 0xffffffffu : 0u;
+    uint32_t halfmask = half ? 0xffffffffu : 0u;
+    // opaque: `a + (halfmask & d)` with uniform a, d then stays one v_and_b32 on this register (hipcc otherwise sees
+    // the select behind the mask and spends a v_mov_b32 + v_cndmask_b32 per use and iteration)
+    asm("" : "+v"(halfmask));
     const bool seg_interior = ys >= kMargin && ye <= h - kMargin;  // workgroup-uniform
+    const uint32_t rows_inside = (uint32_t)max(h - 2 * kMargin, 0);  // rows kMargin .. h - kMargin - 1
     // response rows as a buffer resource: the lane's byte offset within the wave's two rows is a constant, the
     // rows' offset is wave-uniform (SGPR offset of the store)
     const i32x4 resp_rsrc = raw_rsrc(resp, (uint32_t)min((long long)w * h * 2, 0xffffffffLL));
@@ -605,14 +641,26 @@ __device__ __forceinline__ void chess_v1_body(const LevelBatch& lb, const CompTa
         const u32x4 z0v = lds_read_b128(r0 + 16);
         const uint32_t z0[4] = {z0v.x, z0v.y, z0v.z, z0v.w};
 
+        // CLAMP: a row of the 7-pixel frame takes the smaller bias and saturates to 0 with the frame columns
+        // (response_pair_biased).  The two half-waves hold different rows: each row's bias is wave-uniform (SALU),
+        // the lane picks its own with one v_and_b32.  Deliberately no branch on seg_interior: it would end the basic
+        // block between the window reads and the math, and the scheduler then no longer overlaps the two
+        // (measured: the launches of the small levels +3.5 %).
+        uint32_t ybias = kYBias;
+        if (CLAMP) {
+            const uint32_t y0 = (uint32_t)(s0 - 64 - kMargin);  // row of half 0 counted from the first row inside the frame
+            const bool in0 = y0 < rows_inside, in1 = y0 + 1u < rows_inside;
+            const uint32_t b0 = in0 ? kYBias : kYBiasFrameRow, b1 = in1 ? kYBias : kYBiasFrameRow;
+            ybias = b0 + (halfmask & (b1 - b0));
+        }
         uint32_t out[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const uint32_t P = response_pair_biased(m5, p5, m4, p4, m2, p2, z1, z0, k);
-            if (CLAMP) out[k] = pk_sub_sat_u16(P, xmask[k]);  // max(r, 0), 0 in the frame columns
+            const uint32_t P = response_pair_biased(m5, p5, m4, p4, m2, p2, z1, z0, k, ybias);
+            if (CLAMP) out[k] = pk_sub_sat_u16(P, xmask[k]);  // max(r, 0), 0 in the frame columns and rows
             else out[k] = pk_sub_i16(P, 0x20002000u) & xmask[k];
         }
-        if (!seg_interior) {
+        if (!CLAMP && !seg_interior) {
             const uint32_t rm = (yy >= kMargin && yy < h - kMargin) ? 0xffffffffu : 0u;
 #pragma unroll
             for (int k = 0; k < 4; ++k) out[k] &= rm;
@@ -620,8 +668,8 @@ __device__ __forceinline__ void chess_v1_body(const LevelBatch& lb, const CompTa
 
         if (HOT) {
             // responses are clamped here, so "> 15" is "any bit above bit 3"
-            const bool live = yy < ye;
-            const uint32_t any = (out[0] | out[1] | out[2] | out[3]) & 0xfff0fff0u;
+            const bool live = WHOLE || yy < ye;
+            const uint32_t any = or3_and(out[0], out[1], out[2], out[3], 0xfff0fff0u);
             if (__ballot(any != 0 && live) != 0ull) {
                 // bit i = pixel i of the lane is hot: per register, both halves to 0 / 1 (v_pk_min_u16), then the
                 // two flags go to their bit positions and into the mask in one v_dot2_u32_u16 (lo * 2^2k + hi * 2^(2k+1))
@@ -650,8 +698,8 @@ __device__ __forceinline__ void chess_v1_body(const LevelBatch& lb, const CompTa
             stage_store(lds, (pr + 64) & (V1_NR - 1), st_ch, pre);
             __builtin_amdgcn_s_setprio(0);
         }
-        if (yy < ye && x0 < w) {
-            if (x0 + 8 <= w) {
+        if ((WHOLE || yy < ye) && x0 < w) {
+            if (WHOLE || x0 + 8 <= w) {
                 // streamed out: the dense response is only ever re-read around the few hot pixels
                 const u32x4 v = {out[0], out[1], out[2], out[3]};
                 raw_buffer_store_b128(v, resp_rsrc, st_resp_voff, (int)((uint32_t)(s0 - 64) * (uint32_t)w * 2u), kAuxNT);
@@ -677,16 +725,17 @@ __device__ __forceinline__ void chess_v1_body(const LevelBatch& lb, const CompTa
     clock_probe_end(probe, clkp, lb.clk);
 }
 
-template <bool CLAMP, bool HOT, int STAGE, bool FILTER = false>
+template <bool CLAMP, bool HOT, int STAGE, bool FILTER = false, bool WHOLE = false>
 __global__ __launch_bounds__(256) void chess_v1_kernel(LevelBatch lb, CompTables t, int frame0, int nsegs) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    chess_v1_body<CLAMP, HOT, STAGE, false, FILTER>(lb, t, frame0, nsegs, blockIdx.x, gridDim.x, lds);
+    chess_v1_body<CLAMP, HOT, STAGE, false, FILTER, WHOLE>(lb, t, frame0, nsegs, blockIdx.x, gridDim.x, lds);
 }
 
 // Level 0 of the chain: response + clamp + hot list + the level images 1..3 (see emit_pyramid_rows).
 __global__ __launch_bounds__(256, 4) void chess_v1_pyr_kernel(LevelBatch lb, CompTables t, int nsegs, PyramidOut po) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    chess_v1_body<true, true, STAGE_PERM16, true>(lb, t, 0, nsegs, blockIdx.x, gridDim.x, lds, &po);
+    // (chess_pyramid_ok: w % 16 == 0 and h % 8 == 0, so WHOLE)
+    chess_v1_body<true, true, STAGE_PERM16, true, false, true>(lb, t, 0, nsegs, blockIdx.x, gridDim.x, lds, &po);
 }
 
 // ---------------------------------------------------------------------------
@@ -803,7 +852,8 @@ struct ChessMulti {
     int nsegs[kMultiMax];     // balanced row segments per frame (common.h, segment_rows)
     int n;
 };
-template <bool FILTER>  // FILTER: only the frames a sparse chain reported (CompTables::only, see chess_v1_body)
+// WHOLE: every level's height is a multiple of 8 (chess_v1_body; the widths are multiples of 16 anyway)
+template <bool FILTER, bool WHOLE = false>  // FILTER: only the frames a sparse chain reported (CompTables::only, see chess_v1_body)
 __global__ __launch_bounds__(256, 4) void chess_v1_multi_kernel(ChessMulti a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int b = blockIdx.x;
@@ -813,7 +863,7 @@ __global__ __launch_bounds__(256, 4) void chess_v1_multi_kernel(ChessMulti a) {
         if (j < a.n && b >= a.first_wg[j]) k = j;
     const int rel = b - a.first_wg[k];
     if (rel >= a.nwg[k]) return;  // padding between slots
-    chess_v1_body<true, true, STAGE_PERM16, false, FILTER>(a.lb[k], a.t[k], 0, a.nsegs[k], (unsigned)rel, (unsigned)a.nwg[k], lds);
+    chess_v1_body<true, true, STAGE_PERM16, false, FILTER, WHOLE>(a.lb[k], a.t[k], 0, a.nsegs[k], (unsigned)rel, (unsigned)a.nwg[k], lds);
 }
 
 
@@ -871,10 +921,16 @@ void launch_chess(const LevelBatch& lb, const CompTables& t, int frame0, int nfr
 #else
 #define MRG_CASE_TYPED2(C, H)
 #endif
+    // frames of whole 8-row granules (the width is a multiple of 16 on this staging path): chess_v1_body's WHOLE
+    const bool whole = lb.h % V1_RB == 0;
 #define MRG_LAUNCH(C, H, A) hipLaunchKernelGGL((chess_v1_kernel<C, H, A>), grid, dim3(256), lds, s, lb, t, frame0, nsegs)
+#define MRG_LAUNCH_WHOLE(C, H) hipLaunchKernelGGL((chess_v1_kernel<C, H, STAGE_PERM16, false, true>), grid, dim3(256), lds, s, lb, t, frame0, nsegs)
 #define MRG_LAUNCH_ST(C, H)                                             \
     switch (stage) {                                                    \
-        case STAGE_PERM16: MRG_LAUNCH(C, H, STAGE_PERM16); break;       \
+        case STAGE_PERM16:                                              \
+            if (whole) MRG_LAUNCH_WHOLE(C, H);                          \
+            else MRG_LAUNCH(C, H, STAGE_PERM16);                        \
+            break;                                                      \
         MRG_CASE_TYPED2(C, H)                                           \
         case STAGE_TYPED1: MRG_LAUNCH(C, H, STAGE_TYPED1); break;       \
         default: MRG_LAUNCH(C, H, STAGE_GENERIC); break;                \
@@ -890,6 +946,7 @@ void launch_chess(const LevelBatch& lb, const CompTables& t, int frame0, int nfr
     else if (clamp) { MRG_LAUNCH_ST(true, false) }
     else { MRG_LAUNCH_ST(false, false) }
 #undef MRG_LAUNCH_ST
+#undef MRG_LAUNCH_WHOLE
 #undef MRG_LAUNCH
 #undef MRG_CASE_TYPED2
 }
@@ -946,7 +1003,10 @@ bool launch_chess_multi(const LevelBatch* lbs, const CompTables* ts, int n, int 
         total += (a.nwg[k] + 7) / 8 * 8;
     }
     const size_t lds = 2 * V1_PLANE + (V1_HOTBUF + 12) * sizeof(int);
+    bool whole = true;  // every level in whole 8-row granules: the instantiation without the per-row tests
+    for (int k = 0; k < n; ++k) whole = whole && lbs[k].h % V1_RB == 0;
     if (ts[0].only) hipLaunchKernelGGL(chess_v1_multi_kernel<true>, dim3(total), dim3(256), lds, s, a);
+    else if (whole) hipLaunchKernelGGL((chess_v1_multi_kernel<false, true>), dim3(total), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(chess_v1_multi_kernel<false>, dim3(total), dim3(256), lds, s, a);
     return true;
 }
