@@ -46,7 +46,10 @@ extern "C" {
  *      device); options "jpeg_entropy", "jpeg_entropy_max_interval", "jpeg_entropy_memset".
  *      Later, additive and backward compatible: mrgingham_amd_jpeg_sync_rounds; options "jpeg_sync", "jpeg_sync_subsequence",
  *      "jpeg_sync_max_rounds" (files without restart markers Huffman-decoded on the device; off by default, and then every
- *      call behaves as before). */
+ *      call behaves as before).
+ *      Later, additive: mrgingham_amd_find_boards_submit_ex (no refinement, the corners' refinement levels),
+ *      mrgingham_amd_probe_image, _files_plan, _find_boards_files (a list of image files to boards, loader and detector
+ *      pipelined on two contexts). */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -508,6 +511,78 @@ int mrgingham_amd_find_boards_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd
                                      int image_pyramid_level, double* h_boards, signed char* h_found_level,
                                      int nthreads);
 int mrgingham_amd_find_boards_collect(mrgingham_amd_ctx* ctx, int ticket);
+/* mrgingham_amd_find_boards_submit with the two things the one-image wrappers have on top of it (_submit is
+ * _submit_ex(.., do_refine 1, .., h_levels NULL, ..)); _collect is the same.  do_refine 0: the boards stay as the grid
+ * finder made them (mrgingham-from-image --no-refine).  h_levels (HOST, may be NULL): nframes x gridn*gridn signed chars,
+ * the pyramid level every corner of a found board ended at -- what the reference's refinement_level array holds
+ * (mrgingham.cc:81-99); with do_refine 0 every entry is the found level; the block of a frame without a board is left
+ * untouched.  It must stay valid until the job's _collect returns, like h_boards. */
+int mrgingham_amd_find_boards_submit_ex(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* frames, int gridn,
+                                        int image_pyramid_level, int do_refine, double* h_boards, signed char* h_levels,
+                                        signed char* h_found_level, int nthreads);
+
+/* ---- a list of image files to boards ---------------------------------------------------------------------------
+ * What mrgingham_amd_read_image would produce for a file, from its header alone (host only, no device needed, nothing
+ * is decoded): *width, *height, *bits (8 or 16), *kind (1 binary PGM, 2 PNG, 3 baseline JPEG: the header parse of
+ * mrgingham_amd_jpeg_coefficients, up to and including SOS).  Any output pointer may be NULL.  Returns 0; -1 for what
+ * read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut short or
+ * breaks a rule (sides above 32767, interlaced PNG, progressive JPEG, ...), a PGM shorter than its header promises.  A
+ * file that passes may still fail to decode.  Never sizes anything from an unchecked field. */
+int mrgingham_amd_probe_image(const char* filename, int* width, int* height, int* bits, int* kind);
+
+/* How mrgingham_amd_find_boards_files cuts a list into chunks, as a function (host only): key[i] >= 0 -- files of equal
+ * key can share a chunk; key[i] < 0 -- the file is not batched (chunk_of_file[i] = slot_in_chunk[i] = -1).  Chunks are
+ * created in this order: the next chunk belongs to the key of the lowest-index file not yet placed and takes that key's
+ * next batch_frames files in list order.  So files keep their order inside a key, and every chunk holds the first batched
+ * file the chunks before it left out: with chunks completed in order, the files known to be final form a prefix of the
+ * list that grows with every chunk and never shrinks.  Returns 0, or MRGINGHAM_AMD_ERR_ARG (nfiles < 0, batch_frames < 1,
+ * a NULL pointer) with nothing written. */
+int mrgingham_amd_files_plan(const int32_t* key, int nfiles, int batch_frames, int32_t* chunk_of_file,
+                             int32_t* slot_in_chunk, int32_t* nchunks);
+
+/* A list of image files to boards: per file exactly what mrgingham_amd_read_image's decoder followed by
+ * mrgingham_amd_process_image_ex(.., the same options, do_blobs 0, debug 0) gives -- status, found level, the boards
+ * double for double, the corners' levels -- whatever batch_frames, nthreads, jpeg_entropy or the file's place in the list.
+ * SYNCHRONOUS.  The call creates two contexts on ONE device and destroys them: a loader thread fills a ring of three
+ * chunks of device frames on the first, the calling thread runs mrgingham_amd_preprocess_batch (not when do_clahe and
+ * blur_radius are 0) and mrgingham_amd_find_boards_submit_ex per chunk on the second, keeps as many chunks in flight as
+ * that context has scratch sets and collects them in chunk order.  The two are ordered by events and by what has been
+ * collected; nothing synchronises the device in the steady state.  Restores the caller's current HIP device.
+ * Routing by mrgingham_amd_probe_image: 8-bit files of one size share chunks (mrgingham_amd_files_plan, key = size) --
+ * JPEG files through mrgingham_amd_read_jpegs_batch straight into the chunk's frames, PGM / PNG files decoded by the
+ * loader's host threads into page-locked staging and uploaded; 16-bit files, and sizes the batch entry points refuse
+ * while the one-image path takes them (CLAHE below 8 x 8 pixels), go one at a time through the one-image path on the
+ * CALLING THREAD's context (mrgingham_amd_thread_device), when the prefix of final files reaches them.  A file the
+ * probe rejects, or accepts and the decoder then rejects, has status -1.
+ * Memory: the ring is 3 x (raw + preprocessed) device buffers of batch_frames frames of the largest batched size;
+ * batch_frames is lowered until one buffer stays within 1 GiB (12 MP: 85 frames), so the ring stays within 6 GiB; the
+ * page-locked staging (lists with PGM / PNG files only) within 3 GiB.
+ * Outputs (HOST, nfiles entries each, all required): h_status 0 processed / -1 unreadable; h_found_level the level, or
+ * -1; h_boards (gridn*gridn*2 doubles per file) and h_levels (gridn*gridn signed chars per file) are written only where
+ * a board was found.  progress (may be NULL) is called from the calling thread with non-decreasing values: files
+ * [0, nfinal) are final and will not be written again; the last call passes nfiles.  stats (may be NULL): up to nstats
+ * of the MRGINGHAM_AMD_FILES_STATS doubles below.  Returns MRGINGHAM_AMD_OK (also when files were unreadable; nfiles 0 is
+ * fine), MRGINGHAM_AMD_ERR_ARG with nothing written (NULL pointers, gridn outside 2..1024, level above 10, blur radius outside
+ * 0..64, no such device), or the device error that stopped the pipeline (every wait in it ends when the other side
+ * fails); the outputs of files beyond the last progress value are then undefined. */
+typedef struct mrgingham_amd_files_options {
+    int do_clahe, blur_radius, gridn, image_pyramid_level, do_refine;
+    int batch_frames; /* frames per chunk; <= 0: 64 */
+    int nthreads;     /* host threads of the loader and of the grid finder, each (<= 0: all cores, at most 32) */
+    int jpeg_entropy; /* 0: the loader's host threads Huffman-decode; 1: options "jpeg_entropy" 1 and "jpeg_sync" 1 on the loader context */
+    int device;       /* -1: the device of the calling thread's context (mrgingham_amd_thread_device) */
+} mrgingham_amd_files_options;
+#define MRGINGHAM_AMD_FILES_CHUNKS 0           /* chunks that went through the ring */
+#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) */
+#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (PGM / PNG) */
+#define MRGINGHAM_AMD_FILES_ONE_IMAGE 3        /* files through the one-image path */
+#define MRGINGHAM_AMD_FILES_UNREADABLE 4       /* files with status -1 ([1] + [2] + [3] + [4] = nfiles) */
+#define MRGINGHAM_AMD_FILES_DETECTOR_WAIT_MS 5 /* wall ms the calling thread waited for a loaded chunk: the loader bounds the run */
+#define MRGINGHAM_AMD_FILES_LOADER_WAIT_MS 6   /* wall ms the loader thread waited for a free ring slot: the detector bounds it */
+#define MRGINGHAM_AMD_FILES_STATS 7
+int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
+                                    double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
+                                    void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats);
 
 /* Where the find_boards calls of this context spent their HOST time since the last reset, and what their grid-finder
  * threads did (the reference's find_grid_from_points, mrgingham.cc:51, is the host part of the product call; on a busy

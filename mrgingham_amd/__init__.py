@@ -12,8 +12,9 @@ memory and streams.
     board = mrgingham.find_board(image, gridn=10)               # float64[100, 2] or None
 """
 from .api import (ChESS_response_5, find_points, find_chessboard_corners, refine_points, find_board, find_chessboard,
-                  find_grid_from_points, preprocess, read_image, jpeg_coefficients, jpeg_restart_intervals, jpeg_sync_rounds, Detector, level_dims)
+                  find_grid_from_points, preprocess, read_image, jpeg_coefficients, jpeg_restart_intervals, jpeg_sync_rounds, Detector, level_dims,
+                  find_boards_files, probe_image, files_plan)
 
 __all__ = ["ChESS_response_5", "find_points", "find_chessboard_corners", "refine_points", "find_board",
            "find_chessboard", "find_grid_from_points", "preprocess", "read_image", "jpeg_coefficients", "jpeg_restart_intervals", "jpeg_sync_rounds", "Detector",
-           "level_dims"]
+           "level_dims", "find_boards_files", "probe_image", "files_plan"]

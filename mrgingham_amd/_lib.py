@@ -16,6 +16,15 @@ ADD_POINTS_INT = ctypes.CFUNCTYPE(ctypes.c_bool, ctypes.POINTER(ctypes.c_int), c
                                   ctypes.c_void_p)
 
 
+PROGRESS_F = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)
+
+
+class FilesOptions(ctypes.Structure):
+    """mrgingham_amd_files_options"""
+    _fields_ = [(n, ctypes.c_int) for n in ("do_clahe", "blur_radius", "gridn", "image_pyramid_level", "do_refine",
+                                            "batch_frames", "nthreads", "jpeg_entropy", "device")]
+
+
 class Frames(ctypes.Structure):
     """mrgingham_amd_frames"""
     _fields_ = [("frames", ctypes.c_void_p), ("frame_pitch", ctypes.c_int64), ("nframes", ctypes.c_int),
@@ -42,6 +51,8 @@ EXPORTS = [
     "mrgingham_amd_blobs_batch", "mrgingham_amd_find_circle_grids_batch", "mrgingham_amd_blobs_stats",
     "mrgingham_amd_jpeg_coefficients", "mrgingham_amd_jpeg_idct_batch", "mrgingham_amd_read_jpegs_batch",
     "mrgingham_amd_jpeg_restart_intervals", "mrgingham_amd_jpeg_entropy_batch", "mrgingham_amd_jpeg_sync_rounds",
+    "mrgingham_amd_find_boards_submit_ex", "mrgingham_amd_probe_image", "mrgingham_amd_files_plan",
+    "mrgingham_amd_find_boards_files",
 ]
 
 
@@ -130,6 +141,12 @@ def lib():
                                                        c_vp, c_vp]
     if hasattr(L, "mrgingham_amd_jpeg_sync_rounds"):
         L.mrgingham_amd_jpeg_sync_rounds.argtypes = [c_vp, ctypes.c_size_t, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_size_t)]
+    if hasattr(L, "mrgingham_amd_find_boards_files"):
+        L.mrgingham_amd_find_boards_submit_ex.argtypes = [c_vp, FP, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int]
+        L.mrgingham_amd_probe_image.argtypes = [ctypes.c_char_p] + [ctypes.POINTER(c_int)] * 4
+        L.mrgingham_amd_files_plan.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, ctypes.POINTER(ctypes.c_int32)]
+        L.mrgingham_amd_find_boards_files.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp, c_vp,
+                                                      c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]
     L.mrgingham_amd_host_alloc.argtypes = [ctypes.c_size_t]

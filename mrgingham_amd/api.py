@@ -191,6 +191,82 @@ def read_image(filename, cli_scaling=False):
     return out
 
 
+def probe_image(filename):
+    """What read_image would produce for the file, from its header alone (mrgingham_amd_probe_image; host only, nothing is
+    decoded): (height, width, bits, kind) with kind 1 binary PGM, 2 PNG, 3 baseline JPEG; None for a file that is
+    unreadable at header level."""
+    w, h, b, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if _lib.lib().mrgingham_amd_probe_image(os.fsencode(filename), ctypes.byref(w), ctypes.byref(h), ctypes.byref(b),
+                                            ctypes.byref(k)) != 0:
+        return None
+    return h.value, w.value, b.value, k.value
+
+
+def files_plan(keys, batch):
+    """How find_boards_files cuts a list into chunks (mrgingham_amd_files_plan; host only): keys int32 [n], files of equal
+    key >= 0 can share a chunk, key < 0 is not batched -> (chunk_of_file int32 [n], slot_in_chunk int32 [n], nchunks);
+    -1 / -1 for the files that are not batched."""
+    keys = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+    chunk = np.empty(keys.shape, dtype=np.int32)
+    slot = np.empty(keys.shape, dtype=np.int32)
+    n = ctypes.c_int32()
+    if _lib.lib().mrgingham_amd_files_plan(keys.ctypes.data, len(keys), int(batch), chunk.ctypes.data, slot.ctypes.data,
+                                           ctypes.byref(n)) != 0:
+        raise ValueError("files_plan: batch must be at least 1")
+    return chunk, slot, n.value
+
+
+FILES_STATS = ("chunks", "files_device_loader", "files_host_decoded", "files_one_image", "files_unreadable",
+               "ms_detector_waited_for_chunk", "ms_loader_waited_for_slot")
+
+
+def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_radius=1, refine=True, batch=64, nthreads=0,
+                      entropy="host", device=None, progress=None):
+    """A list of image files (binary PGM, PNG, baseline JPEG; any sizes) to boards (mrgingham_amd_find_boards_files): a
+    loader thread fills chunks of `batch` equally-sized frames on the device -- JPEG through the batch loader,
+    entropy="device": Huffman-decoded on the device as well -- while the calling thread preprocesses and searches the
+    chunks before them.  Per file the same numbers as read_image + the one-image path with the same options.
+    -> (boards float64 [n, gridn*gridn, 2], NaN where no board was found; levels int8 [n, gridn*gridn], the pyramid
+    level every corner ended at; found int8 [n], the level the board was found at or -1; status int32 [n], 0 processed,
+    -1 unreadable; stats dict, FILES_STATS).  progress(nfinal, boards, levels, found, status) is called from this thread
+    with non-decreasing values of nfinal and the arrays the call is going to return: their entries [0, nfinal) are final,
+    the last call passes n.  device None: the calling thread's device."""
+    if entropy not in ("host", "device"):
+        raise ValueError('find_boards_files: entropy is "host" or "device"')
+    _require_device()
+    L = _lib.lib()
+    names = [os.fsencode(p) for p in paths]
+    n, N = len(names), int(gridn) * int(gridn)
+    boards = np.full((n, N, 2), np.nan, dtype=np.float64)
+    levels = np.zeros((n, N), dtype=np.int8)
+    found = np.full((n,), -1, dtype=np.int8)
+    status = np.full((n,), -1, dtype=np.int32)
+    stats = np.zeros(len(FILES_STATS), dtype=np.float64)
+    o = _lib.FilesOptions(int(bool(clahe)), int(blur_radius), int(gridn), int(image_pyramid_level), int(bool(refine)), int(batch),
+                          int(nthreads), int(entropy == "device"), -1 if device is None else int(device))
+    raised = []
+
+    def on_progress(nfinal, cookie):
+        if progress is not None and not raised:
+            try:
+                progress(nfinal, boards, levels, found, status)
+            except BaseException as e:   # (an exception cannot cross the C frames: it is raised after the call)
+                raised.append(e)
+    cb = _lib.PROGRESS_F(on_progress)
+    arr = (ctypes.c_char_p * max(n, 1))(*names)
+    rc = L.mrgingham_amd_find_boards_files(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
+                                           status.ctypes.data, cb, None, stats.ctypes.data, len(stats))
+    if raised:
+        raise raised[0]
+    if rc == -1:
+        raise ValueError("find_boards_files: bad argument (gridn >= 2, image_pyramid_level <= 10, blur_radius 0..64, an existing device)")
+    if rc != 0:
+        e = RuntimeError(f"mrgingham_amd_find_boards_files failed: {rc}")
+        e.code = rc
+        raise e
+    return boards, levels, found, status, dict(zip(FILES_STATS, stats.tolist()))
+
+
 def set_wait_policy(policy):
     """How this process's threads wait for the device: 0 runtime default, 1 spin, 2 yield, 3 block
     (mrgingham_amd_set_wait_policy; before the first context -- inside a PyTorch process the runtime is usually
@@ -793,14 +869,20 @@ class Detector:
             self._check(n)
         return dict(zip(self.BLOBS_STATS, out.tolist()))
 
-    def find_boards(self, frames, gridn=10, image_pyramid_level=-1, nthreads=0, blobs=False):
+    def find_boards(self, frames, gridn=10, image_pyramid_level=-1, nthreads=0, blobs=False, refine=True, levels=False):
         """Full detector over a batch: -> (boards float64 [B, gridn*gridn, 2] (numpy, host),
         found_level int8 [B], -1 where no board was found).  Synchronous.  blobs=True (level 0 only): a grid of dark
         circles instead of a chessboard -- the blob detector, then the grid finder, no refinement
-        (find_circle_grid_from_image_array, bridge.cc:104-113); found is 0 or -1."""
+        (find_circle_grid_from_image_array, bridge.cc:104-113); found is 0 or -1.  refine=False: the boards stay as the
+        grid finder made them; levels=True: a third array, int8 [B, gridn*gridn], the pyramid level every corner of a
+        found board ended at (mrgingham_amd_find_boards_submit_ex)."""
         t = self.torch
         if blobs and image_pyramid_level != 0:
             raise RuntimeError("blob detector requires that image_pyramid_level == 0")
+        if blobs and (levels or not refine):
+            raise ValueError("find_boards: blobs=True has neither refinement nor levels")
+        if levels or not refine:
+            return self.find_boards_collect(self.find_boards_submit(frames, gridn, image_pyramid_level, nthreads, refine, levels))
         fr, B, H, W = self._frames(frames)
         boards = np.full((B, gridn * gridn, 2), np.nan, dtype=np.float64)
         found = np.full((B,), -1, dtype=np.int8)
@@ -814,36 +896,44 @@ class Detector:
                                                            found.ctypes.data, int(nthreads)))
         return boards, found
 
-    def find_boards_submit(self, frames, gridn=10, image_pyramid_level=-1, nthreads=0):
+    def find_boards_submit(self, frames, gridn=10, image_pyramid_level=-1, nthreads=0, refine=True, levels=False):
         """First half of find_boards: queues the device passes of the batch and returns a job to hand to
         find_boards_collect.  Submit the next batch(es) before collecting this one and the device passes, the host's
-        grid finder and the refinement of consecutive batches overlap (include/mrgingham_amd.h)."""
+        grid finder and the refinement of consecutive batches overlap (include/mrgingham_amd.h).  refine / levels: as
+        find_boards; with levels=True find_boards_collect returns the third array."""
         t = self.torch
         fr, B, H, W = self._frames(frames)
         boards = np.full((B, gridn * gridn, 2), np.nan, dtype=np.float64)
         found = np.full((B,), -1, dtype=np.int8)
+        lv = np.zeros((B, gridn * gridn), dtype=np.int8) if levels else None
         t.cuda.current_stream(frames.device).synchronize()
-        ticket = self.L.mrgingham_amd_find_boards_submit(self.ctx, ctypes.byref(fr), int(gridn), int(image_pyramid_level),
-                                                         boards.ctypes.data, found.ctypes.data, int(nthreads))
+        if levels or not refine:
+            ticket = self.L.mrgingham_amd_find_boards_submit_ex(self.ctx, ctypes.byref(fr), int(gridn), int(image_pyramid_level),
+                                                                int(bool(refine)), boards.ctypes.data,
+                                                                lv.ctypes.data if levels else None, found.ctypes.data, int(nthreads))
+        else:
+            ticket = self.L.mrgingham_amd_find_boards_submit(self.ctx, ctypes.byref(fr), int(gridn), int(image_pyramid_level),
+                                                             boards.ctypes.data, found.ctypes.data, int(nthreads))
         if ticket < 0:
             self._check(ticket)
         # The library writes into `boards` / `found` (and reads `frames`) until the job is complete -- from inside ANY later
         # call on this context.  The Detector holds them until then, so a caller that drops the job tuple without
         # collecting it cannot make the library write into freed memory.
-        self._fb_live[ticket] = (boards, found, frames)
+        self._fb_live[ticket] = (boards, found, frames, lv)
         if len(self._fb_live) > 64:            # jobs nobody collected: complete what is in flight, then let the old ones go
             self.find_boards_stats(reset=False)   # (completes every batch in flight: their outputs are final)
             for tk in sorted(self._fb_live)[:-8]:
                 del self._fb_live[tk]
-        return (ticket, boards, found, frames)
+        return (ticket, boards, found, frames, lv) if levels else (ticket, boards, found, frames)
 
     def find_boards_collect(self, job):
-        """Second half: waits for the job -> (boards float64 [B, gridn*gridn, 2], found_level int8 [B])."""
+        """Second half: waits for the job -> (boards float64 [B, gridn*gridn, 2], found_level int8 [B]), and the
+        corners' levels int8 [B, gridn*gridn] when the job was submitted with levels=True."""
         try:
             self._check(self.L.mrgingham_amd_find_boards_collect(self.ctx, job[0]))
         finally:
             self._fb_live.pop(job[0], None)
-        return job[1], job[2]
+        return (job[1], job[2], job[4]) if len(job) > 4 else (job[1], job[2])
 
     FB_STATS = ("batches", "host_threads", "ms_submit_checks", "ms_submit_prev_host_begin", "ms_submit_device_queued",
                 "ms_grid_finder_joined", "ms_refinement_queued", "ms_collect_wait_refinement", "ms_collect_boards_copied",

@@ -3,10 +3,13 @@
 // corner, "filename - - -" when no board is found), same worker model (--jobs N threads, image i
 // goes to worker i % N, mrgingham-from-image.cc:50), same failure behaviour (an unreadable image is
 // reported and ends that worker, :58-68).  Row (f)-3 of the scope table: I/O around the hot path.
+// --batch N leaves that worker model: the whole list goes through mrgingham_amd_find_boards_files (a loader thread and
+// the detector pipelined over chunks of N equally-sized frames, JPEG decoded on the device), records come out in list
+// order, and an unreadable image is reported without ending anything.
 //
 // Image decoding: the reference uses cv::imread; OpenCV is not available to this build, so this
-// file reads binary PGM (P5, 8 or 16 bit) and non-interlaced PNG (8 or 16 bit; grey, grey+alpha,
-// RGB, RGBA, 8-bit palette) with zlib.  Colour is reduced to grey with the fixed-point BT.601
+// file reads binary PGM (P5, 8 or 16 bit), non-interlaced PNG (8 or 16 bit; grey, grey+alpha,
+// RGB, RGBA, 8-bit palette) with zlib, and baseline JPEG (the luma plane).  Colour is reduced to grey with the fixed-point BT.601
 // weights (4899 R + 9617 G + 1868 B + 8192) >> 14 -- OpenCV's own conversion depends on its
 // codec build, so byte-identity with cv::imread on colour files is not claimed.
 //
@@ -40,13 +43,16 @@ struct Options {
     int gpus = 0;  // --gpus: 0 = not given (the library's default: worker k on device k % devices, or MRGINGHAM_AMD_DEVICE)
     bool doclahe = true, do_refine = true, debug = false, doblobs = false;
     int debug_sequence_x = -1, debug_sequence_y = -1;
+    int batch = 0;                // --batch N: frames per chunk of mrgingham_amd_find_boards_files; 0 = not given
+    bool entropy_device = false;  // --jpeg-entropy device
 } opt;
 
 const char* kUsage =
     "Usage: %s [--gridn N] [--noclahe] [--blur radius] [--level l] [--no-refine] [--jobs N]\n"
-    "          [--gpus N|all] [--debug] [--debug-sequence x,y] imageglobs...\n"
+    "          [--gpus N|all] [--batch N [--jpeg-entropy host|device]] [--debug] [--debug-sequence x,y]\n"
+    "          imageglobs...\n"
     "\n"
-    "Finds the chessboard in every image (binary PGM or PNG) and writes a vnlog table\n"
+    "Finds the chessboard in every image (binary PGM, PNG or baseline JPEG) and writes a vnlog table\n"
     "\n"
     "  # filename x y level\n"
     "\n"
@@ -63,6 +69,12 @@ const char* kUsage =
     "  --gpus N|all    GPUs to use: worker k works on device k mod N (default: every GPU of the node,\n"
     "                  or the one named by MRGINGHAM_AMD_DEVICE); --jobs several times the GPU count keeps\n"
     "                  each GPU busy while other workers read and decode\n"
+    "  --batch N       the whole list through the batch pipeline, N >= 1 frames per chunk: files of one size are\n"
+    "                  loaded in chunks (JPEG decoded on the GPU) while the chunks before them are searched, on one\n"
+    "                  GPU; --jobs is the number of host threads.  Records are written in list order.  An unreadable\n"
+    "                  image is reported like without --batch, and processing goes on: in this mode no worker stops.\n"
+    "                  Not with --debug, --blobs or --gpus above 1\n"
+    "  --jpeg-entropy host|device   with --batch: where JPEG files are Huffman-decoded (default host: --jobs threads)\n"
     "  --blobs         find a grid of dark circles instead of a chessboard (no --level, no refinement)\n"
     "  --debug         one image only: write the preprocessed image, the level images, the ChESS\n"
     "                  responses and the corner vnlogs to /tmp like the reference does\n"
@@ -209,6 +221,68 @@ void* worker(void* arg) {
     return nullptr;
 }
 
+// --batch: records of the files [printed, nfinal), in list order, as the prefix of final files grows
+struct BatchOut {
+    std::vector<double> xy;
+    std::vector<signed char> lv, found;
+    std::vector<int32_t> status;
+    int printed = 0;
+};
+void batch_progress(int nfinal, void* cookie) {
+    BatchOut& B = *(BatchOut*)cookie;
+    const int N = opt.gridn * opt.gridn;
+    flockfile(stdout);
+    for (; B.printed < nfinal; ++B.printed) {
+        const int i = B.printed;
+        const char* filename = opt.globbed.gl_pathv[i];
+        if (B.status[(size_t)i] != 0) {  // mrgingham-from-image.cc:58-68
+            fprintf(stderr, "Couldn't open image '%s'\n", filename);
+            printf("## Couldn't open image '%s'\n", filename);
+            printf("%s - - -\n", filename);
+            continue;
+        }
+        const int level = B.found[(size_t)i];
+        if (level >= 0)
+            for (int k = 0; k < N; ++k)
+                printf("%s %f %f %d\n", filename, B.xy[((size_t)i * N + k) * 2], B.xy[((size_t)i * N + k) * 2 + 1],
+                       opt.do_refine ? (int)B.lv[(size_t)i * N + k] : level);
+        else
+            printf("%s - - -\n", filename);
+    }
+    funlockfile(stdout);
+}
+int run_batch() {
+    const size_t n = opt.globbed.gl_pathc, N = (size_t)opt.gridn * opt.gridn;
+    BatchOut B;
+    B.xy.resize(n * N * 2);
+    B.lv.resize(n * N);
+    B.found.resize(n);
+    B.status.resize(n);
+    mrgingham_amd_files_options o{};
+    o.do_clahe = opt.doclahe;
+    o.blur_radius = opt.blur_radius;
+    o.gridn = opt.gridn;
+    o.image_pyramid_level = opt.level;
+    o.do_refine = opt.do_refine;
+    o.batch_frames = opt.batch;
+    o.nthreads = opt.jobs;
+    o.jpeg_entropy = opt.entropy_device;
+    o.device = -1;
+    double stats[MRGINGHAM_AMD_FILES_STATS] = {};
+    const int rc = mrgingham_amd_find_boards_files(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
+                                                   B.status.data(), batch_progress, &B, stats, MRGINGHAM_AMD_FILES_STATS);
+    fflush(stdout);
+    if (getenv("MRGINGHAM_AMD_CLI_TIMING"))
+        fprintf(stderr, "batch: %.0f chunks; files: %.0f device loader, %.0f host-decoded, %.0f one at a time, %.0f unreadable; "
+                        "detector waited %.1f ms for chunks, loader waited %.1f ms for ring slots\n",
+                stats[0], stats[1], stats[2], stats[3], stats[4], stats[5], stats[6]);
+    if (rc != 0) {
+        fprintf(stderr, "mrgingham-amd-from-image: the batch pipeline failed (%d)\n", rc);
+        return 2;
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -218,9 +292,10 @@ int main(int argc, char* argv[]) {
         {"no-refine", no_argument, nullptr, 'R'},      {"jobs", required_argument, nullptr, 'j'},
         {"gridn", required_argument, nullptr, 'N'},    {"debug", no_argument, nullptr, 'd'},
         {"debug-sequence", required_argument, nullptr, 'D'}, {"help", no_argument, nullptr, 'h'},
-        {"gpus", required_argument, nullptr, 'G'},
+        {"gpus", required_argument, nullptr, 'G'},     {"batch", required_argument, nullptr, 'T'},
+        {"jpeg-entropy", required_argument, nullptr, 'E'},
         {nullptr, 0, nullptr, 0}};
-    bool doblobs = false;
+    bool doblobs = false, entropy_given = false;
     int c;
     while ((c = getopt_long(argc, argv, "hj:b:l:", longopts, nullptr)) != -1) {
         switch (c) {
@@ -245,11 +320,39 @@ int main(int argc, char* argv[]) {
             case 'l': opt.level = atoi(optarg); break;
             case 'j': opt.jobs = atoi(optarg); break;
             case 'G': opt.gpus = !strcmp(optarg, "all") ? -1 : atoi(optarg); if (opt.gpus == 0) opt.gpus = -2; break;
+            case 'T': {
+                char* end = nullptr;
+                const long v = strtol(optarg, &end, 10);
+                if (end == optarg || *end || v < 1 || v > 1 << 20) {
+                    fprintf(stderr, "--batch takes a positive frame count, got '%s'\n", optarg);
+                    fprintf(stderr, kUsage, argv[0]);
+                    return 1;
+                }
+                opt.batch = (int)v;
+                break;
+            }
+            case 'E':
+                if (strcmp(optarg, "host") && strcmp(optarg, "device")) {
+                    fprintf(stderr, "--jpeg-entropy takes 'host' or 'device', got '%s'\n", optarg);
+                    fprintf(stderr, kUsage, argv[0]);
+                    return 1;
+                }
+                entropy_given = true;
+                opt.entropy_device = !strcmp(optarg, "device");
+                break;
             default:
                 fprintf(stderr, "Unknown option\n");
                 fprintf(stderr, kUsage, argv[0]);
                 return 1;
         }
+    }
+    if (entropy_given && !opt.batch) {
+        fprintf(stderr, "--jpeg-entropy is only accepted with --batch\n");
+        return 1;
+    }
+    if (opt.batch && (opt.debug || doblobs || opt.gpus > 1 || opt.gpus == -1)) {
+        fprintf(stderr, "--batch works on one GPU (no --gpus above 1, no --gpus all) and has neither --debug nor --blobs\n");
+        return 1;
     }
     if (optind > argc - 1) {
         fprintf(stderr, "Not enough arguments: need image globs\n");
@@ -304,6 +407,11 @@ int main(int argc, char* argv[]) {
     for (int i = 0; i < argc; ++i) printf(" %s", argv[i]);
     printf("\n# filename x y level\n");
     fflush(stdout);
+    if (opt.batch) {
+        const int rc = run_batch();
+        globfree(&opt.globbed);
+        return rc;
+    }
     const bool pinned_by_env = getenv("MRGINGHAM_AMD_DEVICE") != nullptr && opt.gpus <= 0;
     const int ng = opt.gpus > 0 ? opt.gpus : (pinned_by_env ? 1 : ndev);
     device_queues = std::vector<DeviceQueue>((size_t)ng);

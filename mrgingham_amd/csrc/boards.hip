@@ -726,6 +726,12 @@ int mrgingham_amd_find_boards_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd
     return fb_submit(ctx, fr, gridn, image_pyramid_level, h_boards, h_found_level, nthreads, true, nullptr);
 }
 
+int mrgingham_amd_find_boards_submit_ex(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int gridn,
+                                        int image_pyramid_level, int do_refine, double* h_boards, signed char* h_levels,
+                                        signed char* h_found_level, int nthreads) {
+    return fb_submit(ctx, fr, gridn, image_pyramid_level, h_boards, h_found_level, nthreads, do_refine != 0, h_levels);
+}
+
 int mrgingham_amd_find_boards_collect(mrgingham_amd_ctx* ctx, int ticket) {
     if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
     MRG_HIP_CHECK(hipSetDevice(ctx->device));

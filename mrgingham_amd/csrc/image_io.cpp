@@ -230,6 +230,90 @@ bool read_image(const char* path, Image& im) {
     }
 }
 
+// The header checks of decode_pgm / read_pgm8_direct, decode_png and decode_jpeg without the decoding.  PGM and PNG keep
+// what they need in front: only the first kProbeBytes of such a file are read (a PGM whose comments push the header
+// beyond them is read whole); a JPEG is read whole, its tables may lie anywhere before SOS.
+bool probe_image(const char* path, int* width, int* height, int* bits, int* kind) {
+    constexpr size_t kProbeBytes = 4096;
+    if (!path) return false;
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    struct Close { FILE* f; ~Close() { fclose(f); } } close_it{f};
+    try {
+        fseek(f, 0, SEEK_END);
+        const long size = ftell(f);
+        fseek(f, 0, SEEK_SET);
+        if (size < 8) return false;
+        std::vector<uint8_t> b((size_t)size < kProbeBytes ? (size_t)size : kProbeBytes);
+        bool ok = fread(b.data(), 1, b.size(), f) == b.size();
+        auto rest = [&]() {  // the whole file
+            const size_t have = b.size();
+            b.resize((size_t)size);
+            return fread(b.data() + have, 1, b.size() - have, f) == b.size() - have;
+        };
+        int w = 0, h = 0, d = 0, k = 0;
+        if (ok && b[0] == 'P' && b[1] == '5') {
+            k = 1;
+            for (int pass = 0; pass < 2 && ok; ++pass) {
+                size_t p = 2;
+                int v[3] = {0, 0, 0};
+                bool parsed = true;
+                for (int i = 0; i < 3 && parsed; ++i) {
+                    for (;;) {
+                        while (p < b.size() && (b[p] == ' ' || b[p] == '\t' || b[p] == '\n' || b[p] == '\r')) ++p;
+                        if (p < b.size() && b[p] == '#') { while (p < b.size() && b[p] != '\n') ++p; continue; }
+                        break;
+                    }
+                    if (p >= b.size() || b[p] < '0' || b[p] > '9') { parsed = false; break; }
+                    long x = 0;
+                    while (p < b.size() && b[p] >= '0' && b[p] <= '9') { x = x * 10 + (b[p] - '0'); if (x > 1 << 30) { parsed = false; break; } ++p; }
+                    v[i] = (int)x;
+                }
+                if ((!parsed || p >= b.size()) && pass == 0 && b.size() < (size_t)size) {  // the header may go on
+                    ok = rest();
+                    continue;
+                }
+                ok = parsed && p < b.size();
+                if (!ok) break;
+                ++p;  // the single whitespace after maxval
+                if (v[0] <= 0 || v[1] <= 0 || v[0] > kMaxSide || v[1] > kMaxSide || v[2] <= 0 || v[2] > 65535) { ok = false; break; }
+                w = v[0]; h = v[1]; d = v[2] < 256 ? 8 : 16;
+                ok = (size_t)size - p >= (size_t)w * h * (d / 8);
+                break;
+            }
+        } else if (ok && b[0] == 0x89 && b[1] == 'P') {
+            k = 2;
+            static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+            // decode_png: the signature, then IHDR first, 13 bytes long and whole
+            ok = (size_t)size >= 8 + 25 && b.size() >= 8 + 25 && !memcmp(b.data(), sig, 8) && be32(&b[8]) == 13 && !memcmp(&b[12], "IHDR", 4);
+            if (ok) {
+                const uint8_t* dd = &b[16];
+                const uint32_t uw = be32(dd), uh = be32(dd + 4);
+                const int pbits = dd[8], ctype = dd[9], interlace = dd[12];
+                ok = uw != 0 && uh != 0 && uw <= (uint32_t)kMaxSide && uh <= (uint32_t)kMaxSide && interlace == 0 &&
+                     (pbits == 8 || pbits == 16) && (ctype == 0 || ctype == 2 || ctype == 4 || ctype == 6 || (ctype == 3 && pbits == 8));
+                w = (int)uw; h = (int)uh; d = pbits;
+            }
+        } else if (ok && b[0] == 0xFF && b[1] == 0xD8) {
+            k = 3;
+            ok = b.size() == (size_t)size || rest();
+            JpegInfo info;
+            ok = ok && jpeg_coefficients(b.data(), b.size(), nullptr, 0, 0, &info) == 0;
+            w = info.width; h = info.height; d = 8;
+        } else {
+            ok = false;
+        }
+        if (!ok) return false;
+        if (width) *width = w;
+        if (height) *height = h;
+        if (bits) *bits = d;
+        if (kind) *kind = k;
+        return true;
+    } catch (...) {  // std::bad_alloc on a file too large to hold
+        return false;
+    }
+}
+
 bool write_png_gray8(const char* path, const uint8_t* px, int w, int h) {
     if (!path || !px || w <= 0 || h <= 0) return false;
     try {

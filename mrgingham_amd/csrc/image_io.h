@@ -25,6 +25,12 @@ struct Image {
 };
 
 bool read_image(const char* path, Image& im);
+// What read_image would produce, from the file's header alone (nothing is decoded): width, height, bits (8 or 16) and
+// kind -- 1 binary PGM, 2 PNG, 3 baseline JPEG (jpeg_coefficients' header parse, up to and including SOS).  false for
+// whatever read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut
+// short or breaks a rule (sides above 32767 included), a PGM shorter than its header promises.  A file that passes may
+// still fail to decode.  Never throws, never sizes anything from an unchecked field.
+bool probe_image(const char* path, int* width, int* height, int* bits, int* kind);
 // the whole file into buf (false: missing, unreadable or empty)
 bool read_file(const char* path, std::vector<uint8_t>& buf);
 // 16 -> 8 bit the way the reference CLI does it: convertTo(CV_8U, 255./65535.) (mrgingham-from-image.cc:91)
