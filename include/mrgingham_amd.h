@@ -49,7 +49,9 @@ extern "C" {
  *      call behaves as before).
  *      Later, additive: mrgingham_amd_find_boards_submit_ex (no refinement, the corners' refinement levels),
  *      mrgingham_amd_probe_image, _files_plan, _find_boards_files (a list of image files to boards, loader and detector
- *      pipelined on two contexts). */
+ *      pipelined on two contexts).
+ *      Later, additive: mrgingham_amd_debug_pixel_stage, _debug_pixel_products (test hooks: the pixel stage of a call alone
+ *      and what it hands to the component search). */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -647,6 +649,38 @@ int mrgingham_amd_debug_paths(mrgingham_amd_ctx* ctx, int level, int nframes, in
  * groups formed, LIFO demand known + neighbour table built, fills done (all of the first band), end;
  * [8..11] = hot pixels, points, bands, level.  Synchronises.  (tools/cc_phases.py) */
 int mrgingham_amd_debug_refine_clock(mrgingham_amd_ctx* ctx, long long* h_ticks12);
+
+/* TEST HOOK: the PIXEL STAGE of a call alone.  Queues on the pixel stream exactly what the named entry point queues
+ * there under the context's current options -- level images, clamped responses, hot lists and pixel -> index maps --
+ * launches NO kernel of the component search, ends the call and synchronises (returns what mrgingham_amd_sync would).
+ * The products stay in the context's scratch for mrgingham_amd_debug_pixel_products until the next call that computes.
+ *   MRGINGHAM_AMD_PIXELS_CHAIN     mrgingham_amd_chain_batch(frames, level = start level, points_pitch);
+ *                                  mrgingham_amd_chain_info reports the launch as after that call.  Products: levels
+ *                                  0 .. level -- with the sparse schedule the level images of all of them, and the
+ *                                  response, list and map of the start level only (the levels below it are computed on
+ *                                  the component stream);
+ *   MRGINGHAM_AMD_PIXELS_LEVEL     mrgingham_amd_detect_batch(frames, level).  Products: that level;
+ *   MRGINGHAM_AMD_PIXELS_RESPONSE  mrgingham_amd_cc_on_response_batch: d_response = dense int16 responses, frames->nframes
+ *                                  of frames->width x frames->height (no other field of `frames` is read).  Products:
+ *                                  "level" 0 without a level image.
+ * d_response is NULL in the other two modes; points_pitch only sizes scratch (as in the calls themselves; >= 1 for a chain). */
+#define MRGINGHAM_AMD_PIXELS_CHAIN 0
+#define MRGINGHAM_AMD_PIXELS_LEVEL 1
+#define MRGINGHAM_AMD_PIXELS_RESPONSE 2
+int mrgingham_amd_debug_pixel_stage(mrgingham_amd_ctx* ctx, int mode, const mrgingham_amd_frames* frames, int level,
+                                    int points_pitch, const int16_t* d_response);
+
+/* TEST HOOK: what mrgingham_amd_debug_pixel_stage left for frame `frame` at `level` (w x h = mrgingham_amd_level_dims of
+ * the frames; gw = (w + 7) / 8), copied to the host; a NULL pointer skips that product:
+ *   h_image     w * h bytes, the level image (levels >= 1)            h_response  w * h int16, the clamped response
+ *   h_hot_cnt   1: hot-list entries MADE (may exceed the capacity)    h_cap       1: the list's capacity per frame
+ *   h_hot_xy    min(*h_hot_cnt, *h_cap) entries (y << 16) | x         h_gidx      gw * h pairs (first index, 8-bit mask);
+ *                                                                                 pairs of groups without a hot pixel are
+ *                                                                                 never written and hold anything
+ * MRGINGHAM_AMD_ERR_ARG when there is no pixel stage to read (another call has computed since) or the product asked for
+ * is not one of that stage's. */
+int mrgingham_amd_debug_pixel_products(mrgingham_amd_ctx* ctx, int level, int frame, uint8_t* h_image, int16_t* h_response,
+                                       int32_t* h_hot_cnt, int32_t* h_cap, uint32_t* h_hot_xy, uint32_t* h_gidx);
 
 /* Device memory the context currently holds (level scratch of both sets, point scratch, staging). */
 long long mrgingham_amd_scratch_bytes(const mrgingham_amd_ctx* ctx);

@@ -52,7 +52,7 @@ EXPORTS = [
     "mrgingham_amd_jpeg_coefficients", "mrgingham_amd_jpeg_idct_batch", "mrgingham_amd_read_jpegs_batch",
     "mrgingham_amd_jpeg_restart_intervals", "mrgingham_amd_jpeg_entropy_batch", "mrgingham_amd_jpeg_sync_rounds",
     "mrgingham_amd_find_boards_submit_ex", "mrgingham_amd_probe_image", "mrgingham_amd_files_plan",
-    "mrgingham_amd_find_boards_files",
+    "mrgingham_amd_find_boards_files", "mrgingham_amd_debug_pixel_stage", "mrgingham_amd_debug_pixel_products",
 ]
 
 
@@ -165,6 +165,8 @@ def lib():
     L.mrgingham_amd_read_image.argtypes = [ctypes.c_char_p, c_int, c_vp, ctypes.c_size_t, ctypes.POINTER(c_int),
                                            ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     L.mrgingham_amd_debug_paths.argtypes = [c_vp, c_int, c_int, c_vp]
+    L.mrgingham_amd_debug_pixel_stage.argtypes = [c_vp, c_int, FP, c_int, c_int, c_vp]
+    L.mrgingham_amd_debug_pixel_products.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.mrgingham_amd_chain_info.argtypes = [c_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.mrgingham_amd_debug_refine_clock.argtypes = [c_vp, c_vp]
     L.mrgingham_amd_scratch_bytes.argtypes = [c_vp]

@@ -963,6 +963,53 @@ class Detector:
         self._check(self.L.mrgingham_amd_debug_paths(self.ctx, int(level), int(nframes), out.ctypes.data))
         return out
 
+    PIXELS_CHAIN, PIXELS_LEVEL, PIXELS_RESPONSE = 0, 1, 2
+
+    def pixel_products(self, frames, level=3, mode="chain", max_points=1024):
+        """Test hook (mrgingham_amd_debug_pixel_stage / _debug_pixel_products): runs the PIXEL STAGE alone of
+        chain(frames, level) (mode "chain"), of detect(frames, level) ("level"), or of cc_detect_on_response(frames, ..)
+        ("response": `frames` is the int16 response [B,h,w]) -- no component search -- and returns what that stage hands
+        over, as numpy arrays: {level: {"w", "h", "cap", and where they are products of the stage "image" u8 [B,h,w],
+        "response" i16 [B,h,w], "hot_cnt" i32 [B] (entries made: may exceed cap), "hot_xy" a list of B u32 arrays of
+        min(hot_cnt, cap) entries (y << 16) | x, "gidx" u32 [B,h,gw,2] (first index, mask: only the pairs of groups with
+        a hot pixel are ever written)}}."""
+        t = self.torch
+        mode = {"chain": self.PIXELS_CHAIN, "level": self.PIXELS_LEVEL, "response": self.PIXELS_RESPONSE}[mode]
+        if mode == self.PIXELS_RESPONSE:
+            assert frames.dtype == t.int16 and frames.is_cuda and frames.is_contiguous() and frames.dim() == 3
+            B, H, W = frames.shape
+            fr, resp, level = _lib.Frames(None, 0, B, W, H, W), frames.data_ptr(), 0
+        else:
+            (fr, B, H, W), resp = self._frames(frames), None
+        t.cuda.current_stream(frames.device).synchronize()
+        self._check(self.L.mrgingham_amd_debug_pixel_stage(self.ctx, mode, ctypes.byref(fr), int(level), int(max_points), resp))
+        out = {}
+        for L in (range(level + 1) if mode == self.PIXELS_CHAIN else (level,)):
+            w, h = level_dims(W, H, L)
+            gw = (w + 7) // 8
+            p = {"w": w, "h": h}
+            cnt, cap = ctypes.c_int32(), ctypes.c_int32()
+            img = np.empty((B, h, w), np.uint8)
+            lists = self.L.mrgingham_amd_debug_pixel_products(self.ctx, L, 0, None, None, None, ctypes.byref(cap), None, None) == 0
+            if self.L.mrgingham_amd_debug_pixel_products(self.ctx, L, 0, img.ctypes.data, None, None, None, None, None) == 0:
+                p["image"] = img
+            if lists:
+                p.update(cap=cap.value, response=np.empty((B, h, w), np.int16), hot_cnt=np.empty(B, np.int32), hot_xy=[],
+                         gidx=np.empty((B, h, gw, 2), np.uint32))
+            for f in range(B):
+                if "image" in p:
+                    self._check(self.L.mrgingham_amd_debug_pixel_products(self.ctx, L, f, img[f].ctypes.data, None, None, None, None, None))
+                if lists:
+                    self._check(self.L.mrgingham_amd_debug_pixel_products(self.ctx, L, f, None, None, ctypes.byref(cnt), None, None, None))
+                    xy = np.empty(max(0, min(cnt.value, cap.value)), np.uint32)
+                    self._check(self.L.mrgingham_amd_debug_pixel_products(
+                        self.ctx, L, f, None, p["response"][f].ctypes.data, ctypes.byref(cnt), ctypes.byref(cap), xy.ctypes.data,
+                        p["gidx"][f].ctypes.data))
+                    p["hot_cnt"][f] = cnt.value
+                    p["hot_xy"].append(xy)
+            out[L] = p
+        return out
+
     def debug_refine_clock(self):
         """Phase clock of the most recent refinement (option cc_lds = 1 | 512): 12 int64, see the header."""
         out = np.zeros(12, dtype=np.int64)

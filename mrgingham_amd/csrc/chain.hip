@@ -57,6 +57,7 @@ void begin_op(mrgingham_amd_ctx* ctx, int max_level) {
     (void)max_level;
     ctx->cur = (ctx->cur + 1) % ctx->nsets;  // this set was last used nsets calls ago
     ctx->status_copied[ctx->cur] = false;    // (until this op's end_op has queued its copy)
+    ctx->pixel_stage.valid = false;          // (mrgingham_amd_debug_pixel_products: the scratch is about to change)
     if (ctx->cc_pending[ctx->cur]) hipStreamWaitEvent(ctx->pix, ctx->ev_cc_done[ctx->cur], 0);
     // The hot-pixel counters of this set are zero here: they are zeroed at allocation and again by
     // end_op behind the component kernels that consumed them -- on the component stream, off the
@@ -338,6 +339,20 @@ static int finish_level_call(mrgingham_amd_ctx* ctx, const LevelBatch& lb, int t
     MRG_HIP_CHECK(hipGetLastError());
     return 0;
 }
+// the scratch of such a call (`pitch` points per frame when it refines: `points`), its op begun, and its pixel stream:
+// level image (w x h) and response of `level`
+static int level_pixels(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level, int w, int h, int pitch, bool points,
+                        LevelBatch& lb) {
+    int rc;
+    MRG_HIP_CHECK(hipSetDevice(ctx->device));
+    if ((rc = choose_sets(ctx, fr))) return rc;
+    if ((rc = ensure_level(ctx, level, fr->nframes, fr->width, fr->height, pitch))) return rc;
+    if (points && (rc = ensure_points(ctx, fr->nframes, pitch))) return rc;
+    begin_op(ctx, level);
+    if (level > 0) launch_one_level_image(fr, level, (uint8_t*)cur_levels(ctx)[level].img.p, w, h, ctx->pix);
+    lb = queue_level_chess(ctx, fr, level);
+    return 0;
+}
 // detect_batch / refine_batch: level image and response of `level` on the pixel stream, its component search behind them
 static int level_call(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int level, const LevelCallOut& o) {
     int rc = validate_frames(ctx, fr);
@@ -348,13 +363,8 @@ static int level_call(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, in
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "Got an unreasonable image_pyramid_level = %d", level);
     if (fr->nframes == 0) return 0;
     if ((rc = check_level_call_out(ctx, o))) return rc;
-    MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    if ((rc = choose_sets(ctx, fr))) return rc;
-    if ((rc = ensure_level(ctx, level, fr->nframes, fr->width, fr->height, o.detect ? 0 : o.pitch))) return rc;
-    if (!o.detect && (rc = ensure_points(ctx, fr->nframes, o.pitch))) return rc;
-    begin_op(ctx, level);
-    if (level > 0) launch_one_level_image(fr, level, (uint8_t*)cur_levels(ctx)[level].img.p, w, h, ctx->pix);
-    const LevelBatch lb = queue_level_chess(ctx, fr, level);
+    LevelBatch lb;
+    if ((rc = level_pixels(ctx, fr, level, w, h, o.detect ? 0 : o.pitch, !o.detect, lb))) return rc;
     return finish_level_call(ctx, lb, level, level, ctx->ev_pix[level], o);
 }
 
@@ -418,6 +428,29 @@ static void chain_pixels_dense(mrgingham_amd_ctx* ctx, const mrgingham_amd_frame
     ctx->last_merged = merged;
 }
 
+// the scratch of a chain call, which schedule it takes (*sparse), and its op begun
+static int chain_begin(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int start_level, int points_pitch, bool* sparse) {
+    int rc;
+    MRG_HIP_CHECK(hipSetDevice(ctx->device));
+    *sparse = sparse_applies(ctx, start_level, (long long)fr->width * fr->height * fr->nframes);
+    if (*sparse) ctx->sparse_seen = true;
+    if ((rc = choose_sets(ctx, fr))) return rc;
+    for (int L = 0; L <= start_level; ++L)
+        if ((rc = ensure_level(ctx, L, fr->nframes, fr->width, fr->height, points_pitch))) return rc;
+    if ((rc = ensure_points(ctx, fr->nframes, points_pitch))) return rc;
+    if (*sparse && !ctx->sparse_stat.p) {
+        if ((rc = ensure(ctx, ctx->sparse_stat, 256))) return rc;
+        MRG_HIP_CHECK(hipMemset(ctx->sparse_stat.p, 0, 256));
+    }
+    begin_op(ctx, start_level);
+    return 0;
+}
+// the pixel stream of a chain call: the launch plan of the step
+static void chain_pixels(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int start_level, bool sparse, ChainPlan& p) {
+    if (sparse) chain_pixels_sparse(ctx, fr, start_level, p);
+    else chain_pixels_dense(ctx, fr, start_level, p);
+}
+
 // component stream: detect at the top (mrgingham.cc:50), candidates -> corners
 // (find_grid.cc:353-354), then refine level by level (mrgingham.cc:87-99)
 static int chain_components(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int start_level, const ChainPlan& p,
@@ -444,6 +477,50 @@ static int chain_components(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* 
         if (!no_cc) launch_cc_refine(p.lbs[L], tables_of(ctx, L), L, io, 0, nf, cc);
     }
     return 0;
+}
+
+// cc_on_response_batch: the scratch of the call (`pitch` points per frame when it refines: `points`), its op begun, and
+// its pixel stream: the caller's response into the scratch, its hot list beside it
+static int response_pixels(mrgingham_amd_ctx* ctx, const int16_t* d_response, const uint8_t* d_level_image, int nframes, int w, int h,
+                           int pitch, bool points, LevelBatch& lb) {
+    int rc;
+    MRG_HIP_CHECK(hipSetDevice(ctx->device));
+    // the level-0 scratch of a w x h "frame": the response is the level image's as far as the
+    // component search is concerned; `level` only enters through the coordinate scale
+    if ((rc = ensure_level(ctx, 0, nframes, w, h, pitch))) return rc;
+    if (points && (rc = ensure_points(ctx, nframes, pitch))) return rc;
+    begin_op(ctx, 0);
+    lb.nframes = nframes;
+    lb.w = w;
+    lb.h = h;
+    lb.img = d_level_image;
+    lb.img_pitch = (long long)w * h;
+    lb.img_stride = w;
+    lb.resp = (int16_t*)cur_levels(ctx)[0].resp.p;
+    lb.resp_pitch = (long long)w * h;
+    launch_hot_from_response(d_response, lb, tables_of(ctx, 0), 0, nframes, ctx->pix);
+    hipEventRecord(ctx->ev_pix[0], ctx->pix);
+    note_pending(ctx, 0, nframes);
+    return 0;
+}
+
+// TEST HOOK (mrgingham_amd_debug_pixel_stage): behind the pixel stream of an op that queued nothing else -- the hot
+// counters to the host (end_op zeroes them for the set's next op), the op ended, everything waited for
+static int finish_pixel_stage(mrgingham_amd_ctx* ctx, int nframes, unsigned img_levels, unsigned list_levels) {
+    order_after_previous(ctx, {}, {});  // (this op touches no buffer of the caller's)
+    MRG_HIP_CHECK(hipStreamSynchronize(ctx->pix));
+    auto& ps = ctx->pixel_stage;
+    ps.cnf = ctx->counters_nf;
+    ps.hot_cnt.resize((size_t)(kMaxLevel + 1) * ps.cnf);
+    MRG_HIP_CHECK(hipMemcpy(ps.hot_cnt.data(), hot_cnt_of(ctx, 0), ps.hot_cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    end_op(ctx);
+    MRG_HIP_CHECK(hipGetLastError());
+    ps.set = ctx->cur;
+    ps.nframes = nframes;
+    ps.img_levels = img_levels;
+    ps.list_levels = list_levels;
+    ps.valid = true;
+    return mrgingham_amd_sync(ctx);
 }
 
 }  // namespace mrg
@@ -475,18 +552,8 @@ int mrgingham_amd_chain_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames
     if (fr->nframes == 0) return 0;
     if (!d_points || !d_levels || !d_npoints || points_pitch <= 0)
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "NULL point buffers");
-    MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    const bool sparse = sparse_applies(ctx, start_level, (long long)fr->width * fr->height * fr->nframes);
-    if (sparse) ctx->sparse_seen = true;
-    if ((rc = choose_sets(ctx, fr))) return rc;
-    for (int L = 0; L <= start_level; ++L)
-        if ((rc = ensure_level(ctx, L, fr->nframes, fr->width, fr->height, points_pitch))) return rc;
-    if ((rc = ensure_points(ctx, fr->nframes, points_pitch))) return rc;
-    if (sparse && !ctx->sparse_stat.p) {
-        if ((rc = ensure(ctx, ctx->sparse_stat, 256))) return rc;
-        MRG_HIP_CHECK(hipMemset(ctx->sparse_stat.p, 0, 256));
-    }
-    begin_op(ctx, start_level);
+    bool sparse;
+    if ((rc = chain_begin(ctx, fr, start_level, points_pitch, &sparse))) return rc;
     auto& ps = ctx->pts[ctx->cur];
     DetectOut out{(int32_t*)ps.cand_xy.p, points_pitch, (int32_t*)ps.cand_counts.p};
     out.points = d_points;
@@ -495,10 +562,8 @@ int mrgingham_amd_chain_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames
     out.points_pitch = points_pitch;
     const RefineIO io = refine_io_of(ctx, ctx->cur, d_points, d_levels, d_npoints, points_pitch, nullptr);
     order_point_buffers(ctx, fr->nframes, points_pitch, d_points, d_levels, d_npoints, nullptr);
-    // the pixel stream: the launch plan of the step
     ChainPlan plan;
-    if (sparse) chain_pixels_sparse(ctx, fr, start_level, plan);
-    else chain_pixels_dense(ctx, fr, start_level, plan);
+    chain_pixels(ctx, fr, start_level, sparse, plan);
     // the component stream, level by level behind it
     if ((rc = chain_components(ctx, fr, start_level, plan, out, io))) return rc;
     end_op(ctx);
@@ -521,25 +586,70 @@ int mrgingham_amd_cc_on_response_batch(mrgingham_amd_ctx* ctx, const int16_t* d_
     int rc = check_level_call_out(ctx, o);
     if (rc) return rc;
     if (nframes == 0) return 0;
-    MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    // the level-0 scratch of a w x h "frame": the response is the level image's as far as the
-    // component search is concerned; `level` only enters through the coordinate scale
-    if ((rc = ensure_level(ctx, 0, nframes, w, h, o.detect ? 0 : points_pitch))) return rc;
-    if (!o.detect && (rc = ensure_points(ctx, nframes, points_pitch))) return rc;
-    begin_op(ctx, 0);
     LevelBatch lb;
-    lb.nframes = nframes;
-    lb.w = w;
-    lb.h = h;
-    lb.img = d_level_image;
-    lb.img_pitch = (long long)w * h;
-    lb.img_stride = w;
-    lb.resp = (int16_t*)cur_levels(ctx)[0].resp.p;
-    lb.resp_pitch = (long long)w * h;
-    launch_hot_from_response(d_response, lb, tables_of(ctx, 0), 0, nframes, ctx->pix);
-    hipEventRecord(ctx->ev_pix[0], ctx->pix);
-    note_pending(ctx, 0, nframes);
+    if ((rc = response_pixels(ctx, d_response, d_level_image, nframes, w, h, o.detect ? 0 : points_pitch, !o.detect, lb))) return rc;
     return finish_level_call(ctx, lb, 0, level, ctx->ev_pix[0], o);
+}
+
+int mrgingham_amd_debug_pixel_stage(mrgingham_amd_ctx* ctx, int mode, const mrgingham_amd_frames* fr, int level, int points_pitch,
+                                    const int16_t* d_response) {
+    if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
+    if (mode == MRGINGHAM_AMD_PIXELS_RESPONSE) {
+        fb_drain(ctx);
+        if (!fr || fr->nframes <= 0 || fr->width <= 0 || fr->height <= 0 || fr->width > 32767 || fr->height > 32767 || !d_response)
+            return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad response batch descriptor");
+        LevelBatch lb;
+        const int rc = response_pixels(ctx, d_response, nullptr, fr->nframes, fr->width, fr->height, 0, false, lb);
+        return rc ? rc : finish_pixel_stage(ctx, fr->nframes, 0, 1u);
+    }
+    if (mode != MRGINGHAM_AMD_PIXELS_CHAIN && mode != MRGINGHAM_AMD_PIXELS_LEVEL)
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "unknown pixel stage %d", mode);
+    int rc = validate_frames(ctx, fr);
+    if (rc) return rc;
+    fb_drain(ctx);
+    int w, h;
+    if (level_dims(fr->width, fr->height, level, &w, &h))
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "Got an unreasonable image_pyramid_level = %d", level);
+    if (fr->nframes == 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "no frames");
+    if (mode == MRGINGHAM_AMD_PIXELS_LEVEL) {
+        LevelBatch lb;
+        if ((rc = level_pixels(ctx, fr, level, w, h, 0, false, lb))) return rc;
+        return finish_pixel_stage(ctx, fr->nframes, level > 0 ? 1u << level : 0u, 1u << level);
+    }
+    if (points_pitch <= 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "points_pitch");
+    bool sparse;
+    if ((rc = chain_begin(ctx, fr, level, points_pitch, &sparse))) return rc;
+    ChainPlan plan;
+    chain_pixels(ctx, fr, level, sparse, plan);
+    const unsigned all = (2u << level) - 1u;
+    return finish_pixel_stage(ctx, fr->nframes, all & ~1u, sparse ? 1u << level : all);
+}
+
+int mrgingham_amd_debug_pixel_products(mrgingham_amd_ctx* ctx, int level, int frame, uint8_t* h_image, int16_t* h_response,
+                                       int32_t* h_hot_cnt, int32_t* h_cap, uint32_t* h_hot_xy, uint32_t* h_gidx) {
+    if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
+    const auto& ps = ctx->pixel_stage;
+    if (!ps.valid) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "no pixel stage to read: mrgingham_amd_debug_pixel_stage comes first");
+    const bool lists = h_response || h_hot_cnt || h_cap || h_hot_xy || h_gidx;
+    if (level < 0 || level > kMaxLevel || frame < 0 || frame >= ps.nframes || (h_image && !(ps.img_levels >> level & 1u)) ||
+        (lists && !(ps.list_levels >> level & 1u)) || (h_hot_xy && (!h_hot_cnt || !h_cap)))
+    {
+        ctx->err = "not a product of the last pixel stage";  // (quiet: callers probe with this)
+        return MRGINGHAM_AMD_ERR_ARG;
+    }
+    MRG_HIP_CHECK(hipSetDevice(ctx->device));
+    const LevelScratch& L = ctx->lvs[ps.set][level];
+    const size_t px = (size_t)L.w * L.h, gpx = (size_t)((L.w + 7) / 8) * L.h;
+    if (h_image) MRG_HIP_CHECK(hipMemcpy(h_image, (const uint8_t*)L.img.p + frame * px, px, hipMemcpyDeviceToHost));
+    if (h_response) MRG_HIP_CHECK(hipMemcpy(h_response, (const int16_t*)L.resp.p + frame * px, px * 2, hipMemcpyDeviceToHost));
+    if (h_hot_cnt) *h_hot_cnt = ps.hot_cnt[(size_t)level * ps.cnf + frame];
+    if (h_cap) *h_cap = L.cap;
+    if (h_hot_xy) {
+        const size_t n = (size_t)(*h_hot_cnt < L.cap ? (*h_hot_cnt > 0 ? *h_hot_cnt : 0) : L.cap);
+        if (n) MRG_HIP_CHECK(hipMemcpy(h_hot_xy, (const uint32_t*)L.hot_xy.p + (size_t)frame * L.cap, n * 4, hipMemcpyDeviceToHost));
+    }
+    if (h_gidx && gpx) MRG_HIP_CHECK(hipMemcpy(h_gidx, (const uint2*)L.gidx.p + frame * gpx, gpx * 8, hipMemcpyDeviceToHost));
+    return MRGINGHAM_AMD_OK;
 }
 
 }  // extern "C"

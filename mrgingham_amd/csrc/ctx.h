@@ -150,6 +150,15 @@ struct mrgingham_amd_ctx {
     // launch (measured slower: 1.171 ms)
     int multi_level = 1;
     int last_fused = 0, last_merged = 0;  // mrgingham_amd_chain_info
+    // TEST HOOK mrgingham_amd_debug_pixel_stage: what it left for mrgingham_amd_debug_pixel_products.  The hot counters
+    // are a host copy ([level][counters_nf]: end_op zeroes the device's); everything else is read out of scratch set
+    // `set`, which the next op may overwrite -- begin_op says so (valid = false)
+    struct PixelStage {
+        bool valid = false;
+        int set = 0, nframes = 0, cnf = 0;
+        unsigned img_levels = 0, list_levels = 0;  // bit L: the level image / the response, list and map of level L are products
+        std::vector<int32_t> hot_cnt;
+    } pixel_stage;
     // option "sparse_refine": chain_batch computes the response of the levels BELOW the start level only in the cells
     // around the points it refines there (chain.hip: chain_pixels_sparse, queue_sparse_levels)
     int sparse_refine = 1;     // (default: where it pays)
