@@ -51,7 +51,10 @@ extern "C" {
  *      mrgingham_amd_probe_image, _files_plan, _find_boards_files (a list of image files to boards, loader and detector
  *      pipelined on two contexts).
  *      Later, additive: mrgingham_amd_debug_pixel_stage, _debug_pixel_products (test hooks: the pixel stage of a call alone
- *      and what it hands to the component search). */
+ *      and what it hands to the component search).
+ *      Later, additive: mrgingham_amd_png_scanlines, _png_reconstruct_batch, _png_reconstruct_geometry, _read_pngs_batch (PNG:
+ *      inflate on the host, row filters and grey on the device); option "png_chunk_frames"; mrgingham_amd_find_boards_files_ex
+ *      (loader flags: MRGINGHAM_AMD_FILES_PNG_DEVICE).  Off unless asked for: every earlier call behaves as before. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -444,6 +447,51 @@ int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
                                    int height, uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads,
                                    int32_t* h_status);
 
+/* PNG, first half (host only, no device needed): the chunk walk and the inflate of a file held in memory, under the rules
+ * of mrgingham_amd_read_image's decoder -- IHDR first, once and 13 bytes long, sides at most 32767 (checked before
+ * anything is sized), IDAT chunks concatenated, no interlace, 8 or 16 bits, colour types 0, 2, 3 (8 bit), 4, 6.  scan (may
+ * be NULL: sizes only, nothing is inflated) receives the FILTERED scanlines as they leave zlib: row y at
+ * scan + (rowbytes + 1) * y, its filter byte first, rowbytes = width * bpp with bpp = 1, 3, 2, 4 bytes for colour types
+ * 0, 2, 4, 6 at 8 bit and twice that at 16.  Returns 0; MRGINGHAM_AMD_PNG_NOT_TAKEN for a readable file the device route
+ * leaves to mrgingham_amd_read_image -- colour type 3, palette: sizes reported, scan untouched --; -1 for everything the
+ * decoder rejects (interlace, other depths, chunk order, an inflate error or another inflated length) and for ANY filter
+ * byte above 4, checked here so that the device never meets one; -2 scan_capacity (bytes) below (rowbytes + 1) * height
+ * (sizes are still reported).  Never throws, never reads or writes out of bounds on a crafted file. */
+#define MRGINGHAM_AMD_PNG_NOT_TAKEN -3
+int mrgingham_amd_png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan_capacity, int* width,
+                                int* height, int* bits, int* color_type);
+
+/* PNG, second half: the row filters (None, Sub, Up, Average, Paeth) undone and the samples reduced to grey for nframes
+ * frames on the device, byte for byte what mrgingham_amd_read_image computes on the host.  d_scan: frame f's scanlines, as
+ * above, at d_scan + f*scan_pitch (BYTES; d_scan 4-byte aligned, scan_pitch >= (width*bpp + 1)*height); every filter byte
+ * is 0 .. 4 (mrgingham_amd_png_scanlines has checked it).  bits 8 or 16, color_type 0, 2, 4 or 6.  d_out: uint8_t frames
+ * for bits 8, uint16_t frames for bits 16 (native endian, from the file's big-endian pairs); frame f row y at
+ * d_out + f*frame_pitch + y*stride, ELEMENTS; only the width x height samples are written, what lies between width and
+ * stride stays untouched.  Grey is the first channel of types 0 and 4, (R*4899 + G*9617 + B*1868 + 8192) >> 14 of types 2
+ * and 6; alpha is ignored.  One workgroup per frame; asynchronous on `stream` (NULL = default); allocates nothing beyond
+ * context scratch (one padded row per frame).  Arguments are checked like mrgingham_amd_jpeg_idct_batch's
+ * (MRGINGHAM_AMD_ERR_ARG, nothing written). */
+int mrgingham_amd_png_reconstruct_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_scan, int64_t scan_pitch, int nframes,
+                                        int width, int height, int bits, int color_type, void* d_out,
+                                        int64_t frame_pitch, int stride, void* stream);
+
+/* The two constants of that kernel's schedule, for tests that place their shapes on its seams: the rows of a frame in
+ * flight at once (the lanes of its workgroup) and the pixels of a row a lane reconstructs per step. */
+void mrgingham_amd_png_reconstruct_geometry(int* rows_in_flight, int* segment_pixels);
+
+/* nfiles PNG files of ONE size and depth straight into device frames (layout and element type as d_out above): nthreads
+ * host threads (<= 0: all cores, at most 32) inflate a chunk of files into page-locked staging while the chunk before it
+ * uploads and runs mrgingham_amd_png_reconstruct_batch (one launch per run of files of one colour type); neither the
+ * reconstructed nor the grey pixels exist on the host.  A palette file is decoded by the host threads with
+ * mrgingham_amd_read_image's decoder and uploaded: same bytes.  h_status[f]: 0 decoded, -1 unreadable / unsupported /
+ * malformed (or not a PNG), -2 a PNG of another size or depth; the frame of a failed file is zero-filled.  SYNCHRONOUS:
+ * d_out is complete on return.  Returns MRGINGHAM_AMD_OK also when files failed.  Completes the find_boards jobs in
+ * flight first and restores the caller's HIP device.  The chunk buffers are those of mrgingham_amd_read_jpegs_batch, within
+ * the same 1 GiB (12 MP grey: ~40 files each; option "png_chunk_frames"). */
+int mrgingham_amd_read_pngs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
+                                  int bits, void* d_out, int64_t frame_pitch, int stride, int nthreads,
+                                  int32_t* h_status);
+
 /* The same preprocessing for one HOST image (out: dense width x height bytes, host): what the Python
  * recipe of find_board.docstring:8-10 does with cv2 before find_board.  Uses the calling thread's
  * context.  Returns 0, or -2 on an argument or device error. */
@@ -575,7 +623,7 @@ typedef struct mrgingham_amd_files_options {
     int device;       /* -1: the device of the calling thread's context (mrgingham_amd_thread_device) */
 } mrgingham_amd_files_options;
 #define MRGINGHAM_AMD_FILES_CHUNKS 0           /* chunks that went through the ring */
-#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) */
+#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch */
 #define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (PGM / PNG) */
 #define MRGINGHAM_AMD_FILES_ONE_IMAGE 3        /* files through the one-image path */
 #define MRGINGHAM_AMD_FILES_UNREADABLE 4       /* files with status -1 ([1] + [2] + [3] + [4] = nfiles) */
@@ -585,6 +633,16 @@ typedef struct mrgingham_amd_files_options {
 int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
                                     double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
                                     void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats);
+
+/* mrgingham_amd_find_boards_files with loader flags (0: exactly that call).  MRGINGHAM_AMD_FILES_PNG_DEVICE: runs of
+ * consecutive 8-bit PNG slots of a chunk go through mrgingham_amd_read_pngs_batch on the loader context, like the JPEG
+ * runs -- the host threads only inflate -- and are counted under MRGINGHAM_AMD_FILES_DEVICE_LOADED; palette files keep
+ * the host decoder (and MRGINGHAM_AMD_FILES_HOST_DECODED), 16-bit files the one-image path.  Same outputs. */
+#define MRGINGHAM_AMD_FILES_PNG_DEVICE 1
+int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
+                                       double* h_boards, signed char* h_levels, signed char* h_found_level,
+                                       int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
+                                       double* stats, int nstats, int loader_flags);
 
 /* Where the find_boards calls of this context spent their HOST time since the last reset, and what their grid-finder
  * threads did (the reference's find_grid_from_points, mrgingham.cc:51, is the host part of the product call; on a busy
@@ -735,6 +793,7 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         by their scratch budget; n > 0 = at most n frames per chunk.  Results never depend on it.
  *   "jpeg_chunk_frames"   test hook: 0 (default) = mrgingham_amd_read_jpegs_batch cuts its files into chunks by its scratch
  *                         budget; n > 0 = at most n files per chunk.  Results never depend on it.
+ *   "png_chunk_frames"    test hook: the same for mrgingham_amd_read_pngs_batch.
  *   "jpeg_entropy"        0 (default): mrgingham_amd_read_jpegs_batch entropy-decodes on its host threads; 1: files with
  *                         restart intervals are Huffman-decoded on the device, one lane per interval.  Same frames and statuses.
  *   "jpeg_entropy_max_interval"  MCUs per restart interval the device accepts (default 1024, at least 1; files above it go

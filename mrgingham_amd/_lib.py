@@ -53,6 +53,8 @@ EXPORTS = [
     "mrgingham_amd_jpeg_restart_intervals", "mrgingham_amd_jpeg_entropy_batch", "mrgingham_amd_jpeg_sync_rounds",
     "mrgingham_amd_find_boards_submit_ex", "mrgingham_amd_probe_image", "mrgingham_amd_files_plan",
     "mrgingham_amd_find_boards_files", "mrgingham_amd_debug_pixel_stage", "mrgingham_amd_debug_pixel_products",
+    "mrgingham_amd_png_scanlines", "mrgingham_amd_png_reconstruct_batch", "mrgingham_amd_png_reconstruct_geometry",
+    "mrgingham_amd_read_pngs_batch", "mrgingham_amd_find_boards_files_ex",
 ]
 
 
@@ -147,6 +149,16 @@ def lib():
         L.mrgingham_amd_files_plan.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, ctypes.POINTER(ctypes.c_int32)]
         L.mrgingham_amd_find_boards_files.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp, c_vp,
                                                       c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int]
+    if hasattr(L, "mrgingham_amd_png_reconstruct_batch"):
+        L.mrgingham_amd_png_scanlines.argtypes = [c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t] + [ctypes.POINTER(c_int)] * 4
+        L.mrgingham_amd_png_reconstruct_batch.argtypes = [c_vp, c_vp, ctypes.c_int64, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                                          ctypes.c_int64, c_int, c_vp]
+        L.mrgingham_amd_png_reconstruct_geometry.argtypes = [ctypes.POINTER(c_int)] * 2
+        L.mrgingham_amd_png_reconstruct_geometry.restype = None
+        L.mrgingham_amd_read_pngs_batch.argtypes = [c_vp, ctypes.POINTER(ctypes.c_char_p), c_int, c_int, c_int, c_int, c_vp,
+                                                    ctypes.c_int64, c_int, c_int, c_vp]
+        L.mrgingham_amd_find_boards_files_ex.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
+                                                         c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]
     L.mrgingham_amd_host_alloc.argtypes = [ctypes.c_size_t]

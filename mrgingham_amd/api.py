@@ -174,6 +174,55 @@ def jpeg_sync_rounds(data, subsequence=128):
     return rounds.value, n.value
 
 
+class _PngNotTaken:
+    """What png_scanlines returns for a readable PNG that the device route leaves to read_image (a palette file)."""
+    def __repr__(self):
+        return "PNG_NOT_TAKEN"
+
+
+PNG_NOT_TAKEN = _PngNotTaken()
+_PNG_BPP = {(8, 0): 1, (8, 2): 3, (8, 4): 2, (8, 6): 4, (16, 0): 2, (16, 2): 6, (16, 4): 4, (16, 6): 8}
+
+
+def png_scanlines(data):
+    """Chunk walk + inflate of a PNG held in memory (host only; mrgingham_amd_png_scanlines): -> (scanlines uint8
+    [height, rowbytes + 1], (height, width), bits, color_type) -- the FILTERED rows as they leave zlib, each behind its
+    filter byte (0 .. 4), rowbytes = width * bpp; what Detector.png_reconstruct takes.  PNG_NOT_TAKEN for a readable file
+    the device route does not take (colour type 3, palette: read_image decodes it).  None when the data is not a PNG this
+    library reads (interlace, depths other than 8 / 16, chunk order, inflate errors, a filter byte above 4, ...)."""
+    L = _lib.lib()
+    buf = bytes(data)
+    w, h, b, ct = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    sizes = (ctypes.byref(w), ctypes.byref(h), ctypes.byref(b), ctypes.byref(ct))
+    rc = L.mrgingham_amd_png_scanlines(buf, len(buf), None, 0, *sizes)
+    if rc == -3:
+        return PNG_NOT_TAKEN
+    if rc != 0:
+        return None
+    scan = np.empty((h.value, w.value * _PNG_BPP[b.value, ct.value] + 1), dtype=np.uint8)
+    if L.mrgingham_amd_png_scanlines(buf, len(buf), scan.ctypes.data, scan.size, *sizes) != 0:
+        return None
+    return scan, (h.value, w.value), b.value, ct.value
+
+
+def png_scanlines_size(data):
+    """(height, width, bits, color_type) of a PNG held in memory from its chunks alone (nothing is inflated; palette files
+    included); None when it is not one this library reads."""
+    buf = bytes(data)
+    w, h, b, ct = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = _lib.lib().mrgingham_amd_png_scanlines(buf, len(buf), None, 0, ctypes.byref(w), ctypes.byref(h), ctypes.byref(b), ctypes.byref(ct))
+    if rc not in (0, -3):
+        return None
+    return h.value, w.value, b.value, ct.value
+
+
+def png_reconstruct_geometry():
+    """(rows_in_flight, segment_pixels) of the PNG reconstruction kernel's schedule (mrgingham_amd_png_reconstruct_geometry)."""
+    r, s = ctypes.c_int(), ctypes.c_int()
+    _lib.lib().mrgingham_amd_png_reconstruct_geometry(ctypes.byref(r), ctypes.byref(s))
+    return r.value, s.value
+
+
 def read_image(filename, cli_scaling=False):
     """Decode a binary PGM, non-interlaced PNG or baseline JPEG to uint8 [H, W] with the library's own decoder (host only).
     16-bit files: the high byte (cv::imread(IMREAD_GRAYSCALE)) or, with cli_scaling, the CLI's
@@ -221,7 +270,7 @@ FILES_STATS = ("chunks", "files_device_loader", "files_host_decoded", "files_one
 
 
 def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_radius=1, refine=True, batch=64, nthreads=0,
-                      entropy="host", device=None, progress=None):
+                      entropy="host", device=None, progress=None, png="host"):
     """A list of image files (binary PGM, PNG, baseline JPEG; any sizes) to boards (mrgingham_amd_find_boards_files): a
     loader thread fills chunks of `batch` equally-sized frames on the device -- JPEG through the batch loader,
     entropy="device": Huffman-decoded on the device as well -- while the calling thread preprocesses and searches the
@@ -230,9 +279,13 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
     level every corner ended at; found int8 [n], the level the board was found at or -1; status int32 [n], 0 processed,
     -1 unreadable; stats dict, FILES_STATS).  progress(nfinal, boards, levels, found, status) is called from this thread
     with non-decreasing values of nfinal and the arrays the call is going to return: their entries [0, nfinal) are final,
-    the last call passes n.  device None: the calling thread's device."""
+    the last call passes n.  device None: the calling thread's device.  png="device": the runs of 8-bit PNG files of a chunk
+    go through the PNG batch loader (Detector.read_pngs: the host threads only inflate) and count as files_device_loader;
+    same numbers."""
     if entropy not in ("host", "device"):
         raise ValueError('find_boards_files: entropy is "host" or "device"')
+    if png not in ("host", "device"):
+        raise ValueError('find_boards_files: png is "host" or "device"')
     _require_device()
     L = _lib.lib()
     names = [os.fsencode(p) for p in paths]
@@ -254,8 +307,8 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
                 raised.append(e)
     cb = _lib.PROGRESS_F(on_progress)
     arr = (ctypes.c_char_p * max(n, 1))(*names)
-    rc = L.mrgingham_amd_find_boards_files(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
-                                           status.ctypes.data, cb, None, stats.ctypes.data, len(stats))
+    rc = L.mrgingham_amd_find_boards_files_ex(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
+                                              status.ctypes.data, cb, None, stats.ctypes.data, len(stats), int(png == "device"))
     if raised:
         raise raised[0]
     if rc == -1:
@@ -857,6 +910,63 @@ class Detector:
         with self._with_options(jpeg_entropy=int(entropy == "device"), jpeg_sync=int(bool(sync))):
             self._check(self.L.mrgingham_amd_read_jpegs_batch(self.ctx, arr, B, W, H, frames.data_ptr(), H * W, W, int(nthreads),
                                                               status.ctypes.data))
+        return frames, status
+
+    def png_reconstruct(self, scan, height, width, bits, color_type, out=None):
+        """The row filters of inflated PNG scanlines undone and the samples reduced to grey on the device
+        (mrgingham_amd_png_reconstruct_batch), on torch's current stream: scan uint8 [B, height, width*bpp + 1] device tensor,
+        frame by frame what png_scanlines gives (bits 8 or 16, color_type 0, 2, 4 or 6) -> uint8 (bits 8) or uint16 (bits 16)
+        [B, height, width], the samples read_image's decoder gives for the file.  `out`: a [B, height, >= width] device
+        tensor of that type (unit column stride) to write into; what lies beyond `width` is not touched."""
+        t = self.torch
+        bpp = _PNG_BPP.get((int(bits), int(color_type)))
+        if bpp is None:
+            raise ValueError("png_reconstruct: bits 8 or 16, color_type 0, 2, 4 or 6")
+        if not (scan.is_cuda and scan.dtype == t.uint8 and scan.dim() == 3 and scan.is_contiguous()
+                and tuple(scan.shape[1:]) == (height, width * bpp + 1)):
+            raise ValueError("png_reconstruct: scan is a contiguous uint8 [B,height,width*bpp+1] tensor on the device")
+        B = scan.shape[0]
+        dtype = t.uint8 if bits == 8 else t.uint16
+        if out is None:
+            out = t.empty((B, height, width), dtype=dtype, device=scan.device)
+        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
+                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
+            raise ValueError("png_reconstruct: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
+        stream = t.cuda.current_stream(scan.device).cuda_stream
+        self._check(self.L.mrgingham_amd_png_reconstruct_batch(
+            self.ctx, scan.data_ptr(), height * (width * bpp + 1), B, int(width), int(height), int(bits), int(color_type), out.data_ptr(),
+            out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+        return out[:, :, :width]
+
+    def read_pngs(self, paths, nthreads=0):
+        """PNG files of one size and depth straight into device frames (mrgingham_amd_read_pngs_batch): `nthreads` host
+        threads (0: all cores, at most 32) inflate, the device undoes the row filters and reduces colour to grey.  ->
+        (frames uint8 or uint16 [B,H,W] on the device, status int32 [B] numpy: 0 decoded, -1 unreadable / unsupported /
+        malformed, -2 a PNG of another size or depth; failed frames are zero).  Size and depth are those of the first file
+        whose header parses (none does: uint8 frames [B,0,0]).  Palette files are decoded by the host threads: same bytes.
+        Synchronous."""
+        t = self.torch
+        names = [os.fsencode(p) for p in paths]
+        B = len(names)
+        status = np.full((B,), -1, dtype=np.int32)
+        H = W = 0
+        bits = 8
+        for name in names:
+            try:
+                with open(name, "rb") as f:
+                    head = png_scanlines_size(f.read())
+            except OSError:
+                head = None
+            if head is not None:
+                H, W, bits, _ = head
+                break
+        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
+        if B == 0 or H == 0:
+            return frames, status
+        arr = (ctypes.c_char_p * B)(*names)
+        t.cuda.current_stream(self.device).synchronize()
+        self._check(self.L.mrgingham_amd_read_pngs_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
+                                                         status.ctypes.data))
         return frames, status
 
     BLOBS_STATS = ("calls", "chunks", "nodes", "contours", "points", "device_ms", "host_ms", "frames")

@@ -45,11 +45,13 @@ struct Options {
     int debug_sequence_x = -1, debug_sequence_y = -1;
     int batch = 0;                // --batch N: frames per chunk of mrgingham_amd_find_boards_files; 0 = not given
     bool entropy_device = false;  // --jpeg-entropy device
+    bool png_device = false;      // --png-reconstruct device
 } opt;
 
 const char* kUsage =
     "Usage: %s [--gridn N] [--noclahe] [--blur radius] [--level l] [--no-refine] [--jobs N]\n"
-    "          [--gpus N|all] [--batch N [--jpeg-entropy host|device]] [--debug] [--debug-sequence x,y]\n"
+    "          [--gpus N|all] [--batch N [--jpeg-entropy host|device] [--png-reconstruct host|device]]\n"
+    "          [--debug] [--debug-sequence x,y]\n"
     "          imageglobs...\n"
     "\n"
     "Finds the chessboard in every image (binary PGM, PNG or baseline JPEG) and writes a vnlog table\n"
@@ -75,6 +77,8 @@ const char* kUsage =
     "                  image is reported like without --batch, and processing goes on: in this mode no worker stops.\n"
     "                  Not with --debug, --blobs or --gpus above 1\n"
     "  --jpeg-entropy host|device   with --batch: where JPEG files are Huffman-decoded (default host: --jobs threads)\n"
+    "  --png-reconstruct host|device   with --batch: where the row filters of PNG files are undone and colour is reduced\n"
+    "                  to grey (default host; device: the --jobs threads only inflate)\n"
     "  --blobs         find a grid of dark circles instead of a chessboard (no --level, no refinement)\n"
     "  --debug         one image only: write the preprocessed image, the level images, the ChESS\n"
     "                  responses and the corner vnlogs to /tmp like the reference does\n"
@@ -269,8 +273,9 @@ int run_batch() {
     o.jpeg_entropy = opt.entropy_device;
     o.device = -1;
     double stats[MRGINGHAM_AMD_FILES_STATS] = {};
-    const int rc = mrgingham_amd_find_boards_files(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
-                                                   B.status.data(), batch_progress, &B, stats, MRGINGHAM_AMD_FILES_STATS);
+    const int rc = mrgingham_amd_find_boards_files_ex(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
+                                                      B.status.data(), batch_progress, &B, stats, MRGINGHAM_AMD_FILES_STATS,
+                                                      opt.png_device ? MRGINGHAM_AMD_FILES_PNG_DEVICE : 0);
     fflush(stdout);
     if (getenv("MRGINGHAM_AMD_CLI_TIMING"))
         fprintf(stderr, "batch: %.0f chunks; files: %.0f device loader, %.0f host-decoded, %.0f one at a time, %.0f unreadable; "
@@ -294,8 +299,9 @@ int main(int argc, char* argv[]) {
         {"debug-sequence", required_argument, nullptr, 'D'}, {"help", no_argument, nullptr, 'h'},
         {"gpus", required_argument, nullptr, 'G'},     {"batch", required_argument, nullptr, 'T'},
         {"jpeg-entropy", required_argument, nullptr, 'E'},
+        {"png-reconstruct", required_argument, nullptr, 'P'},
         {nullptr, 0, nullptr, 0}};
-    bool doblobs = false, entropy_given = false;
+    bool doblobs = false, entropy_given = false, png_given = false;
     int c;
     while ((c = getopt_long(argc, argv, "hj:b:l:", longopts, nullptr)) != -1) {
         switch (c) {
@@ -340,6 +346,15 @@ int main(int argc, char* argv[]) {
                 entropy_given = true;
                 opt.entropy_device = !strcmp(optarg, "device");
                 break;
+            case 'P':
+                if (strcmp(optarg, "host") && strcmp(optarg, "device")) {
+                    fprintf(stderr, "--png-reconstruct takes 'host' or 'device', got '%s'\n", optarg);
+                    fprintf(stderr, kUsage, argv[0]);
+                    return 1;
+                }
+                png_given = true;
+                opt.png_device = !strcmp(optarg, "device");
+                break;
             default:
                 fprintf(stderr, "Unknown option\n");
                 fprintf(stderr, kUsage, argv[0]);
@@ -348,6 +363,10 @@ int main(int argc, char* argv[]) {
     }
     if (entropy_given && !opt.batch) {
         fprintf(stderr, "--jpeg-entropy is only accepted with --batch\n");
+        return 1;
+    }
+    if (png_given && !opt.batch) {
+        fprintf(stderr, "--png-reconstruct is only accepted with --batch\n");
         return 1;
     }
     if (opt.batch && (opt.debug || doblobs || opt.gpus > 1 || opt.gpus == -1)) {

@@ -173,7 +173,7 @@ static std::vector<DevBuf*> all_buffers(mrgingham_amd_ctx* ctx) {
     for (DevBuf* b : {&ctx->io_counts, &ctx->aux_img, &ctx->io_frame, &ctx->io_out, &ctx->pre_scratch, &ctx->pre_tmp,
                       &ctx->pre_out, &ctx->pre16_scratch, &ctx->io_frame16, &ctx->dbg_img, &ctx->dbg_resp, &ctx->blob_scratch, &ctx->blob_nodes, &ctx->blob_out,
                       &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->jpeg_dev[0], &ctx->jpeg_dev[1], &ctx->jpeg_huff_dev[0], &ctx->jpeg_huff_dev[1],
-                      &ctx->jpeg_sync_dev[0], &ctx->jpeg_sync_dev[1], &ctx->jpeg_sync_rec[0], &ctx->jpeg_sync_rec[1]})
+                      &ctx->jpeg_sync_dev[0], &ctx->jpeg_sync_dev[1], &ctx->jpeg_sync_rec[0], &ctx->jpeg_sync_rec[1], &ctx->png_row})
         v.push_back(b);
     return v;
 }
@@ -641,6 +641,11 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
     if (!strcmp(name, "jpeg_chunk_frames")) {
         if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_chunk_frames: 0 (by the scratch budget) or a frame count");
         ctx->jpeg_chunk_frames = value;
+        return 0;
+    }
+    if (!strcmp(name, "png_chunk_frames")) {
+        if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "png_chunk_frames: 0 (by the scratch budget) or a file count");
+        ctx->png_chunk_frames = value;
         return 0;
     }
     if (!strcmp(name, "jpeg_entropy")) {

@@ -226,6 +226,12 @@ struct mrgingham_amd_ctx {
     int jpeg_sync_subsequence = 128;  // (measured: DESIGN.md section 4.10)
     int jpeg_sync_max_rounds = 0;
     int jpeg_sync_time_phase = 0;
+    // mrgingham_amd_read_pngs_batch / _png_reconstruct_batch (png_recon.hip): the loader's two chunk slots are the JPEG loader's
+    // (jpeg_dev, jpeg_pin, jpeg_ev, within jpeg_coef_budget: both loaders are synchronous); png_row: per frame of a launch the
+    // padded row that lane R - 1 hands to lane 0 of the next round; option "png_chunk_frames" (test hook): at most that
+    // many files per chunk, 0 = by the budget
+    mrg::DevBuf png_row;
+    int png_chunk_frames = 0;
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
     // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
     // context of THIS context's device, created on first use -- not on the calling thread's default context, which

@@ -1,5 +1,5 @@
 // Host side of libmrgingham_amd.so, a list of image files to boards (mrgingham_amd_find_boards_files): the schedule that
-// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip), of the preprocessing (preprocess.hip) and of the board
+// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip, png_recon.hip), of the preprocessing (preprocess.hip) and of the board
 // detector (boards.hip) fed from a list of several sizes and formats.  No kernel of its own.
 //
 //   loader thread, LOADER context            calling thread, DETECTOR context
@@ -8,6 +8,7 @@
 //   PGM / PNG -> page-locked staging         pix stream waits for the slot's upload event
 //     (host threads), upload, event          preprocess_batch on the pix stream, find_boards_submit_ex
 //   JPEG runs -> read_jpegs_batch            collect chunk c - k, scatter its results, advance the final prefix
+//   (PNG runs -> read_pngs_batch where the caller set MRGINGHAM_AMD_FILES_PNG_DEVICE)
 //   chunk c loaded                           (one-image files are processed when the prefix reaches them)
 //
 // The ring has three slots; slot c % 3 holds chunk c from its load to its collect.  What orders the two contexts:
@@ -35,6 +36,8 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 struct FileInfo {
     int w = 0, h = 0, bits = 0, kind = 0;  // kind 0: the probe rejected the file
+    bool png_device = false;               // a PNG that goes through read_pngs_batch (MRGINGHAM_AMD_FILES_PNG_DEVICE)
+    bool batch_loader() const { return kind == 3 || png_device; }
 };
 
 struct Chunk {
@@ -101,7 +104,7 @@ int load_chunk(Run& R, int c) {
     // PGM / PNG: the host threads decode into the staging of the slot, consecutive slots go up in one copy
     std::vector<int> host;
     for (int k = 0; k < n; ++k)
-        if (R.info[(size_t)ch.files[(size_t)k]].kind != 3) host.push_back(k);
+        if (!R.info[(size_t)ch.files[(size_t)k]].batch_loader()) host.push_back(k);
     if (!host.empty()) {
         std::atomic<int> next{0};
         auto worker = [&]() {
@@ -127,19 +130,27 @@ int load_chunk(Run& R, int c) {
         MRG_HIP_CHECK(hipEventRecord(S.ev_up, s));
         S.uploaded = true;
     }
-    // JPEG: every run of consecutive slots is one call of the batch loader, straight into the chunk's frames
-    long njpeg_ok = 0;
+    // JPEG, and PNG where the caller asked for it: every run of consecutive slots of one of them is one call of its batch
+    // loader, straight into the chunk's frames
+    long nbatch_ok = 0;
+    auto route = [&](int k) {
+        const FileInfo& f = R.info[(size_t)ch.files[(size_t)k]];
+        return f.kind == 3 ? 1 : f.png_device ? 2 : 0;
+    };
     for (int k = 0; k < n;) {
-        if (R.info[(size_t)ch.files[(size_t)k]].kind != 3) { ++k; continue; }
+        const int via = route(k);
+        if (!via) { ++k; continue; }
         int j = k + 1;
-        while (j < n && R.info[(size_t)ch.files[(size_t)j]].kind == 3) ++j;
+        while (j < n && route(j) == via) ++j;
         std::vector<const char*> run;
         for (int i = k; i < j; ++i) run.push_back(R.names[ch.files[(size_t)i]]);
-        const int rc = mrgingham_amd_read_jpegs_batch(ctx, run.data(), j - k, ch.w, ch.h, S.d_raw + (size_t)k * pitch, (int64_t)pitch,
-                                                      ch.w, R.nthreads, S.load_status.data() + k);
+        const int rc = via == 1 ? mrgingham_amd_read_jpegs_batch(ctx, run.data(), j - k, ch.w, ch.h, S.d_raw + (size_t)k * pitch, (int64_t)pitch,
+                                                                 ch.w, R.nthreads, S.load_status.data() + k)
+                                : mrgingham_amd_read_pngs_batch(ctx, run.data(), j - k, ch.w, ch.h, 8, S.d_raw + (size_t)k * pitch, (int64_t)pitch,
+                                                                ch.w, R.nthreads, S.load_status.data() + k);
         if (rc) return rc;
         for (int i = k; i < j; ++i) {
-            if (S.load_status[(size_t)i] == 0) ++njpeg_ok;
+            if (S.load_status[(size_t)i] == 0) ++nbatch_ok;
             else S.load_status[(size_t)i] = -1;
         }
         k = j;
@@ -147,7 +158,7 @@ int load_chunk(Run& R, int c) {
     long nhost_ok = 0;
     for (int k : host) nhost_ok += S.load_status[(size_t)k] == 0;
     std::lock_guard<std::mutex> lk(R.pipe.mu);
-    R.pipe.n_device_loaded += njpeg_ok;
+    R.pipe.n_device_loaded += nbatch_ok;
     R.pipe.n_host_decoded += nhost_ok;
     return 0;
 }
@@ -204,7 +215,15 @@ int mrgingham_amd_files_plan(const int32_t* key, int nfiles, int batch_frames, i
 int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
                                     double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
                                     void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats) {
-    if (nfiles < 0 || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
+    return mrgingham_amd_find_boards_files_ex(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
+                                              nstats, 0);
+}
+
+int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
+                                       double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
+                                       void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
+                                       int loader_flags) {
+    if (nfiles < 0 || (loader_flags & ~MRGINGHAM_AMD_FILES_PNG_DEVICE) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
         o->blur_radius > 64 || o->device < -1 || nstats < 0 || (nstats > 0 && !stats) ||
         (nfiles > 0 && (!filenames || !h_boards || !h_levels || !h_found_level || !h_status)))
         return MRGINGHAM_AMD_ERR_ARG;
@@ -239,6 +258,9 @@ int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, co
             for (int i; (i = next.fetch_add(1)) < nfiles;) {
                 FileInfo& f = R.info[(size_t)i];
                 if (!probe_image(filenames[i], &f.w, &f.h, &f.bits, &f.kind)) f = FileInfo{};
+                // (palette files keep the host decoder: read_pngs_batch would hand them to it anyway, one by one)
+                if ((loader_flags & MRGINGHAM_AMD_FILES_PNG_DEVICE) && f.kind == 2 && f.bits == 8)
+                    f.png_device = png_header(filenames[i], nullptr, nullptr, nullptr) != 3;
             }
         };
         HostPool probe_pool;
@@ -255,7 +277,7 @@ int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, co
         key[(size_t)i] = (int32_t)(((uint32_t)f.h << 15) | (uint32_t)f.w);  // (sides are at most 32767)
         const size_t fp = frame_pitch_of(f.w, f.h);
         if (fp > max_frame) max_frame = fp;
-        if (f.kind != 3 && fp > max_host_frame) max_host_frame = fp;
+        if (!f.batch_loader() && fp > max_host_frame) max_host_frame = fp;
     }
     R.batch = o->batch_frames > 0 ? o->batch_frames : 64;
     if (max_frame && (size_t)R.batch > kBufferBytes / max_frame) R.batch = (int)(kBufferBytes / max_frame);
@@ -387,7 +409,7 @@ int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, co
                 continue;
             }
             if (f.ticket < 0) {  // counted as loaded by the loader: as a one-image file from here on
-                --(R.info[(size_t)i].kind == 3 ? rerouted_device : rerouted_host);
+                --(R.info[(size_t)i].batch_loader() ? rerouted_device : rerouted_host);
                 one_image(i);
                 continue;
             }

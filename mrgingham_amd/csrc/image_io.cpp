@@ -1,6 +1,8 @@
 // See image_io.h.
 #include "image_io.h"
 #include "jpeg.h"
+#include "png_filter.h"
+#include "../../include/mrgingham_amd.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -70,17 +72,22 @@ static bool decode_pgm(const std::vector<uint8_t>& b, Image& im) {
 
 static inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | (p[1] << 16) | (p[2] << 8) | p[3]; }
 
-static bool decode_png(const std::vector<uint8_t>& b, Image& im) {
+// The chunk walk of a PNG held in memory: the signature, IHDR first, once and 13 bytes long, sides within the library's
+// limit (checked BEFORE anything is sized from them), IDAT chunks concatenated, PLTE kept, up to IEND.  ch: channels.
+struct PngHead {
+    int w = 0, h = 0, bits = 0, ctype = -1, ch = 0;
+};
+
+static bool png_chunks(const uint8_t* b, size_t nbytes, PngHead& hd, std::vector<uint8_t>* idat, std::vector<uint8_t>* plte) {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-    if (b.size() < 8 + 25 || memcmp(b.data(), sig, 8)) return false;
+    if (nbytes < 8 + 25 || memcmp(b, sig, 8)) return false;
     size_t p = 8;
-    int w = 0, h = 0, bits = 0, ctype = -1, interlace = 0;
-    bool have_ihdr = false;
-    std::vector<uint8_t> idat, plte;
-    while (p + 12 <= b.size()) {
+    int interlace = 0;
+    bool have_ihdr = false, have_idat = false;
+    while (p + 12 <= nbytes) {
         const uint32_t len = be32(&b[p]);
         const char* type = (const char*)&b[p + 4];
-        if (p + 12 + (size_t)len > b.size()) return false;
+        if (p + 12 + (size_t)len > nbytes) return false;
         const uint8_t* d = &b[p + 8];
         if (!memcmp(type, "IHDR", 4)) {
             // exactly one IHDR, first, 13 bytes; sides within the library's limit (a crafted header must
@@ -88,55 +95,90 @@ static bool decode_png(const std::vector<uint8_t>& b, Image& im) {
             if (have_ihdr || p != 8 || len != 13) return false;
             const uint32_t uw = be32(d), uh = be32(d + 4);
             if (uw == 0 || uh == 0 || uw > (uint32_t)kMaxSide || uh > (uint32_t)kMaxSide) return false;
-            w = (int)uw; h = (int)uh; bits = d[8]; ctype = d[9]; interlace = d[12];
+            hd.w = (int)uw; hd.h = (int)uh; hd.bits = d[8]; hd.ctype = d[9]; interlace = d[12];
             have_ihdr = true;
         } else if (!have_ihdr) return false;  // any other chunk before IHDR
-        else if (!memcmp(type, "PLTE", 4)) plte.assign(d, d + len);
-        else if (!memcmp(type, "IDAT", 4)) idat.insert(idat.end(), d, d + len);
+        else if (!memcmp(type, "PLTE", 4)) { if (plte) plte->assign(d, d + len); }
+        else if (!memcmp(type, "IDAT", 4)) { if (idat) idat->insert(idat->end(), d, d + len); have_idat = have_idat || len > 0; }
         else if (!memcmp(type, "IEND", 4)) break;
         p += 12 + (size_t)len;
     }
-    if (!have_ihdr || idat.empty() || interlace != 0 || (bits != 8 && bits != 16)) return false;
-    int ch;
-    switch (ctype) {
-        case 0: ch = 1; break;
-        case 2: ch = 3; break;
-        case 3: ch = 1; if (bits != 8) return false; break;
-        case 4: ch = 2; break;
-        case 6: ch = 4; break;
+    if (!have_ihdr || !have_idat || interlace != 0 || (hd.bits != 8 && hd.bits != 16)) return false;
+    switch (hd.ctype) {
+        case 0: hd.ch = 1; break;
+        case 2: hd.ch = 3; break;
+        case 3: hd.ch = 1; if (hd.bits != 8) return false; break;
+        case 4: hd.ch = 2; break;
+        case 6: hd.ch = 4; break;
         default: return false;
     }
-    const size_t bpp = (size_t)ch * bits / 8, rowb = (size_t)w * bpp;
+    return true;
+}
+
+int png_header(const char* path, int* width, int* height, int* bits) {
+    if (!path) return -1;
+    FILE* f = fopen(path, "rb");
+    if (!f) return -1;
+    uint8_t b[33];
+    const size_t got = fread(b, 1, sizeof(b), f);
+    fclose(f);
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    if (got != sizeof(b) || memcmp(b, sig, 8) || be32(&b[8]) != 13 || memcmp(&b[12], "IHDR", 4)) return -1;
+    if (width) *width = (int)(be32(&b[16]) & 0x7fffffffu);
+    if (height) *height = (int)(be32(&b[20]) & 0x7fffffffu);
+    if (bits) *bits = b[24];
+    return b[25];
+}
+
+int png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan_capacity, int* width, int* height, int* bits,
+                  int* color_type) {
+    if (!data) return -1;
+    try {
+        PngHead hd;
+        std::vector<uint8_t> idat;
+        if (!png_chunks(data, nbytes, hd, scan ? &idat : nullptr, nullptr)) return -1;
+        if (width) *width = hd.w;
+        if (height) *height = hd.h;
+        if (bits) *bits = hd.bits;
+        if (color_type) *color_type = hd.ctype;
+        if (hd.ctype == 3) return kPngNotTaken;
+        if (!scan) return 0;
+        const size_t rowb = (size_t)hd.w * hd.ch * hd.bits / 8, need = (rowb + 1) * (size_t)hd.h;
+        if (scan_capacity < need) return -2;
+        uLongf rawlen = (uLongf)need;
+        if (uncompress(scan, &rawlen, idat.data(), (uLong)idat.size()) != Z_OK || rawlen != need) return -1;
+        // the kernel never meets a filter type it has no predictor for
+        for (int y = 0; y < hd.h; ++y)
+            if (scan[(rowb + 1) * y] >= kPngFilters) return -1;
+        return 0;
+    } catch (...) {  // std::bad_alloc
+        return -1;
+    }
+}
+
+static bool decode_png(const std::vector<uint8_t>& b, Image& im) {
+    PngHead hd;
+    std::vector<uint8_t> idat, plte;
+    if (!png_chunks(b.data(), b.size(), hd, &idat, &plte)) return false;
+    const int w = hd.w, h = hd.h, bits = hd.bits, ctype = hd.ctype;
+    const size_t bpp = (size_t)hd.ch * bits / 8, rowb = (size_t)w * bpp;
     std::vector<uint8_t> raw((rowb + 1) * (size_t)h);
     uLongf rawlen = (uLongf)raw.size();
     if (uncompress(raw.data(), &rawlen, idat.data(), (uLong)idat.size()) != Z_OK || rawlen != raw.size()) return false;
     std::vector<uint8_t> img(rowb * (size_t)h);
     for (int y = 0; y < h; ++y) {
         const uint8_t ft = raw[(rowb + 1) * y];
+        if (ft >= kPngFilters) return false;
         const uint8_t* s = &raw[(rowb + 1) * y + 1];
         uint8_t* o = &img[rowb * y];
         const uint8_t* up = y ? o - rowb : nullptr;
         for (size_t i = 0; i < rowb; ++i) {
             const int a = i >= bpp ? o[i - bpp] : 0, bb = up ? up[i] : 0, c = (up && i >= bpp) ? up[i - bpp] : 0;
-            int pred = 0;
-            switch (ft) {
-                case 0: pred = 0; break;
-                case 1: pred = a; break;
-                case 2: pred = bb; break;
-                case 3: pred = (a + bb) >> 1; break;
-                case 4: {
-                    const int pa = abs(bb - c), pb = abs(a - c), pc = abs(a + bb - 2 * c);
-                    pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? bb : c);
-                    break;
-                }
-                default: return false;
-            }
-            o[i] = (uint8_t)(s[i] + pred);
+            o[i] = (uint8_t)(s[i] + png_predict(ft, a, bb, c));
         }
     }
     const size_t n = (size_t)w * h;
     im.w = w; im.h = h; im.depth = bits;
-    auto grey = [](uint32_t r, uint32_t g, uint32_t bl) { return (r * 4899u + g * 9617u + bl * 1868u + 8192u) >> 14; };
     if (bits == 8) {
         about_to_hold(im, n, 0);
         im.px8.resize(n);
@@ -145,8 +187,8 @@ static bool decode_png(const std::vector<uint8_t>& b, Image& im) {
             if (ctype == 0 || ctype == 4) im.px8[i] = q[0];
             else if (ctype == 3) {
                 if ((size_t)q[0] * 3 + 2 >= plte.size()) return false;
-                im.px8[i] = (uint8_t)grey(plte[q[0] * 3], plte[q[0] * 3 + 1], plte[q[0] * 3 + 2]);
-            } else im.px8[i] = (uint8_t)grey(q[0], q[1], q[2]);
+                im.px8[i] = (uint8_t)png_grey(plte[q[0] * 3], plte[q[0] * 3 + 1], plte[q[0] * 3 + 2]);
+            } else im.px8[i] = (uint8_t)png_grey(q[0], q[1], q[2]);
         }
     } else {
         about_to_hold(im, 0, n);
@@ -154,7 +196,7 @@ static bool decode_png(const std::vector<uint8_t>& b, Image& im) {
         for (size_t i = 0; i < n; ++i) {
             const uint8_t* q = &img[i * bpp];
             auto s16 = [&](int k) { return (uint32_t)((q[2 * k] << 8) | q[2 * k + 1]); };
-            im.px16[i] = (uint16_t)((ctype == 0 || ctype == 4) ? s16(0) : grey(s16(0), s16(1), s16(2)));
+            im.px16[i] = (uint16_t)((ctype == 0 || ctype == 4) ? s16(0) : png_grey(s16(0), s16(1), s16(2)));
         }
     }
     return true;
@@ -366,3 +408,8 @@ void to_8bit(const Image& im, std::vector<uint8_t>& out) {
 }
 
 }  // namespace mrg
+
+extern "C" int mrgingham_amd_png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan_capacity, int* width,
+                                           int* height, int* bits, int* color_type) {
+    return mrg::png_scanlines(data, nbytes, scan, scan_capacity, width, height, bits, color_type);
+}

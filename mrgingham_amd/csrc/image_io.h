@@ -31,6 +31,17 @@ bool read_image(const char* path, Image& im);
 // short or breaks a rule (sides above 32767 included), a PGM shorter than its header promises.  A file that passes may
 // still fail to decode.  Never throws, never sizes anything from an unchecked field.
 bool probe_image(const char* path, int* width, int* height, int* bits, int* kind);
+// The host half of the PNG device route (mrgingham_amd_png_scanlines): decode_png's header and chunk rules, then the
+// inflated, still filtered scanlines -- row y is scan[(rowbytes + 1) * y]: its filter byte, then rowbytes bytes -- into
+// `scan` (NULL: sizes only).  0 taken; kPngNotTaken readable, but a palette file (the host decoder's alone: sizes are
+// reported, nothing is inflated); -1 whatever decode_png rejects, a filter byte above 4 included; -2 scan_capacity
+// below (rowbytes + 1) * height (sizes are still reported).  Never throws.
+constexpr int kPngNotTaken = -3;
+int png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan_capacity, int* width, int* height, int* bits,
+                  int* color_type);
+// The IHDR fields of a PNG file as they stand, nothing judged (a routing hint: png_scanlines decides what is readable):
+// returns the colour type byte, -1 for a file that does not begin with a PNG signature and a whole IHDR.
+int png_header(const char* path, int* width, int* height, int* bits);
 // the whole file into buf (false: missing, unreadable or empty)
 bool read_file(const char* path, std::vector<uint8_t>& buf);
 // 16 -> 8 bit the way the reference CLI does it: convertTo(CV_8U, 255./65535.) (mrgingham-from-image.cc:91)
