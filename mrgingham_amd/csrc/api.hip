@@ -43,6 +43,30 @@ int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes) {
     return 0;
 }
 
+// (the step of ensure_pinned, for the one caller that goes on without the memory: ensure_level_set)
+static hipError_t grow_pinned(PinBuf& b, size_t bytes, int slack_divisor, bool zero_on_growth) {
+    if (bytes <= b.bytes) return hipSuccess;
+    if (b.p) {
+        const hipError_t e = hipHostFree(b.p);
+        if (e != hipSuccess) return e;
+        b = PinBuf();
+    }
+    const size_t want = bytes + (slack_divisor ? bytes / slack_divisor : 0);
+    const hipError_t e = hipHostMalloc(&b.p, want, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return e;
+    }
+    b.bytes = want;
+    if (zero_on_growth) memset(b.p, 0, want);
+    return hipSuccess;
+}
+
+int ensure_pinned(mrgingham_amd_ctx* ctx, PinBuf& b, size_t bytes, int slack_divisor, bool zero_on_growth) {
+    MRG_HIP_CHECK(grow_pinned(b, bytes, slack_divisor, zero_on_growth));
+    return 0;
+}
+
 // Rows between host and device (or device and device): ONE plain copy whenever both sides are dense (every caller's usual case).  The 2-D copy
 // of the runtime is a slow path into pageable memory and serialises the threads of a process.
 hipError_t copy_rows_async(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows,
@@ -117,19 +141,8 @@ int ensure_level_set(mrgingham_amd_ctx* ctx, int set, int level, int nframes, in
         // the page-locked mirrors of the status words (end_op copies into them) change size with it: here, where the
         // device is idle and nothing is queued.  A mirror that cannot be had stays away until the next growth (the sync
         // then makes a blocking copy: harvest_set)
-        const size_t words = (size_t)(kMaxLevel + 1) * cnf;
-        for (int k = 0; k < kMaxSets; ++k) {
-            if (ctx->status_pin[k]) hipHostFree(ctx->status_pin[k]);
-            ctx->status_pin[k] = nullptr;
-            ctx->status_pin_words[k] = 0;
-            void* p = nullptr;
-            if (hipHostMalloc(&p, words * sizeof(int32_t), hipHostMallocDefault) == hipSuccess) {
-                ctx->status_pin[k] = (int32_t*)p;
-                ctx->status_pin_words[k] = words;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
+        for (int k = 0; k < kMaxSets; ++k)
+            if (grow_pinned(ctx->status_pin[k], (size_t)(kMaxLevel + 1) * cnf * sizeof(int32_t), 0, false) != hipSuccess) (void)hipGetLastError();
         ctx->counters_nf = cnf;
     }
     if ((rc = ensure(ctx, L.hot_xy, nf * (size_t)cap * 4))) return rc;
@@ -172,9 +185,18 @@ static std::vector<DevBuf*> all_buffers(mrgingham_amd_ctx* ctx) {
         for (DevBuf* b : {&j.d_cnt, &j.d_pts, &j.d_pts0}) v.push_back(b);
     for (DevBuf* b : {&ctx->io_counts, &ctx->aux_img, &ctx->io_frame, &ctx->io_out, &ctx->pre_scratch, &ctx->pre_tmp,
                       &ctx->pre_out, &ctx->pre16_scratch, &ctx->io_frame16, &ctx->dbg_img, &ctx->dbg_resp, &ctx->blob_scratch, &ctx->blob_nodes, &ctx->blob_out,
-                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->jpeg_dev[0], &ctx->jpeg_dev[1], &ctx->jpeg_huff_dev[0], &ctx->jpeg_huff_dev[1],
+                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->loader_slot[0].dev, &ctx->loader_slot[1].dev, &ctx->jpeg_huff_dev[0], &ctx->jpeg_huff_dev[1],
                       &ctx->jpeg_sync_dev[0], &ctx->jpeg_sync_dev[1], &ctx->jpeg_sync_rec[0], &ctx->jpeg_sync_rec[1], &ctx->png_row})
         v.push_back(b);
+    return v;
+}
+// Every page-locked buffer a context owns (for destroy; mrgingham_amd_scratch_bytes counts device memory only).
+static std::vector<PinBuf*> all_pinned(mrgingham_amd_ctx* ctx) {
+    std::vector<PinBuf*> v{&ctx->io_pin};
+    for (PinBuf& b : ctx->status_pin) v.push_back(&b);
+    for (int k = 0; k < 2; ++k)
+        for (PinBuf* b : {&ctx->loader_slot[k].pin, &ctx->jpeg_huff_pin[k], &ctx->jpeg_sync_pin[k]}) v.push_back(b);
+    for (auto& j : ctx->jobs) v.push_back(&j.pin);
     return v;
 }
 
@@ -317,7 +339,7 @@ static int harvest_set(mrgingham_amd_ctx* ctx, int set, int* rc) {
     const int32_t* host;
     const bool pinned = ctx->status_copied[set];  // (end_op's copy: the whole block, sized by counters_nf like the words)
     if (pinned) {  // (the set's stream has been waited for: the copy end_op queued has landed)
-        host = ctx->status_pin[set] + (size_t)lo * cnf;
+        host = (const int32_t*)ctx->status_pin[set].p + (size_t)lo * cnf;
     } else {
         ctx->host_status.resize(nwords);
         MRG_HIP_CHECK(hipMemcpy(ctx->host_status.data(), status_words(ctx, set, lo), sizeof(int32_t) * nwords, hipMemcpyDeviceToHost));
@@ -332,7 +354,7 @@ static int harvest_set(mrgingham_amd_ctx* ctx, int set, int* rc) {
         for (int f = 0; f < nact && !any; ++f) any = hw[f] != 0;
         const int r = inspect_status(ctx, set, level, hw, nact, status_words(ctx, set, level), rc, false);
         if (r) return r;
-        if (any && pinned) memset(ctx->status_pin[set] + (size_t)level * cnf, 0, (size_t)nact * sizeof(int32_t));  // (cleared on the device: here too)
+        if (any && pinned) memset((int32_t*)ctx->status_pin[set].p + (size_t)level * cnf, 0, (size_t)nact * sizeof(int32_t));  // (cleared on the device: here too)
     }
     return 0;
 }
@@ -467,18 +489,13 @@ void mrgingham_amd_destroy(mrgingham_amd_ctx* ctx) {
     if (ctx->ev_ext) hipEventDestroy(ctx->ev_ext);
     for (hipEvent_t e : ctx->blob_ev)
         if (e) hipEventDestroy(e);
-    if (ctx->io_pin) hipHostFree(ctx->io_pin);
+    for (PinBuf* b : all_pinned(ctx))
+        if (b->p) hipHostFree(b->p);
     if (ctx->io_res_pin) hipHostFree(ctx->io_res_pin);
-    for (int k = 0; k < kMaxSets; ++k)
-        if (ctx->status_pin[k]) hipHostFree(ctx->status_pin[k]);
     for (hipEvent_t e : ctx->io_ev)
         if (e) hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->jpeg_pin[k]) hipHostFree(ctx->jpeg_pin[k]);
-        if (ctx->jpeg_huff_pin[k]) hipHostFree(ctx->jpeg_huff_pin[k]);
-        if (ctx->jpeg_sync_pin[k]) hipHostFree(ctx->jpeg_sync_pin[k]);
-        if (ctx->jpeg_ev[k]) hipEventDestroy(ctx->jpeg_ev[k]);
-    }
+    for (auto& slot : ctx->loader_slot)
+        if (slot.ev) hipEventDestroy(slot.ev);
     if (ctx->mg_done) hipEventDestroy(ctx->mg_done);
     if (ctx->mg_stream) hipStreamDestroy(ctx->mg_stream);
     for (auto& j : ctx->jobs) {
@@ -486,7 +503,6 @@ void mrgingham_amd_destroy(mrgingham_amd_ctx* ctx) {
         if (j.ev_b) hipEventDestroy(j.ev_b);
         if (j.ev_a0) hipEventDestroy(j.ev_a0);
         if (j.ev_b0) hipEventDestroy(j.ev_b0);
-        if (j.pin) hipHostFree(j.pin);
     }
     if (ctx->pix) hipStreamDestroy(ctx->pix);
     for (hipStream_t c : ctx->ccs)

@@ -308,7 +308,7 @@ static FbPinned fb_layout(void* base, int nlev, int B, int cap, int N) {
 // else before fb_host_end (submit queues the next batch's device passes there).
 static void fb_grid_worker(mrgingham_amd_ctx::BoardsJob* job) {
     const int B = job->fr.nframes, N = job->gridn * job->gridn, cap = job->cap, nlev = job->nlev;
-    const FbPinned pin = fb_layout(job->pin, nlev, B, cap, N);
+    const FbPinned pin = fb_layout(job->pin.p, nlev, B, cap, N);
     GridScratch scratch;
     const GridPhaseClock c0 = g_grid_clock;
     struct Leave {   // this thread's share of the batch's grid-finder time into the context's totals
@@ -344,7 +344,7 @@ static int fb_host_begin(mrgingham_amd_ctx* ctx, mrgingham_amd_ctx::BoardsJob& j
     job.grid_running = false;
     MRG_HIP_CHECK(hipEventSynchronize(job.ev_a));
     add_elapsed_ms(ctx->fb_dev_ms[0], job.ev_a0, job.ev_a);
-    const FbPinned pin = fb_layout(job.pin, nlev, B, cap, N);
+    const FbPinned pin = fb_layout(job.pin.p, nlev, B, cap, N);
     int rc = 0;
     // Frames whose candidates did not fit: again at full capacity (detect_full_capacity); the tables of the level grow
     // for the batches to come.
@@ -388,7 +388,7 @@ static int fb_host_end(mrgingham_amd_ctx* ctx, mrgingham_amd_ctx::BoardsJob& job
         job.grid_running = false;
     }
     FB_LAP(3);
-    const FbPinned pin = fb_layout(job.pin, nlev, B, cap, N);
+    const FbPinned pin = fb_layout(job.pin.p, nlev, B, cap, N);
     int rc = 0;
     int top = 0, nref = 0;
     for (int k = 0; k < B && job.do_refine; ++k) {
@@ -444,7 +444,7 @@ static int fb_finish(mrgingham_amd_ctx* ctx, mrgingham_amd_ctx::BoardsJob& job) 
         MRG_HIP_CHECK(hipEventSynchronize(job.ev_b));
         FB_LAP(5);
         add_elapsed_ms(ctx->fb_dev_ms[1], job.ev_b0, job.ev_b);
-        const FbPinned pin = fb_layout(job.pin, job.nlev, B, job.cap, N);
+        const FbPinned pin = fb_layout(job.pin.p, job.nlev, B, job.cap, N);
         bool overflowed = false;
         for (int k = 0; k < B && !rc; ++k) {
             const int Lf = job.h_found[k];
@@ -582,14 +582,7 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
             (rc = ensure(ctx, nj.d_pts, fb_align((size_t)B * N * 16) + fb_align((size_t)B * N) + (size_t)B * 4)) ||
             (rc = ensure(ctx, nj.d_pts0, fb_align((size_t)B * N * 16) + (size_t)B * N)))
             return rc;
-        const size_t need = fb_layout(nullptr, nlev, B, cap, N).bytes;
-        if (need > nj.pin_bytes) {
-            if (nj.pin) hipHostFree(nj.pin);
-            nj.pin = nullptr;
-            nj.pin_bytes = 0;
-            MRG_HIP_CHECK(hipHostMalloc(&nj.pin, need + need / 4, hipHostMallocDefault));
-            nj.pin_bytes = need + need / 4;
-        }
+        if ((rc = ensure_pinned(ctx, nj.pin, fb_layout(nullptr, nlev, B, cap, N).bytes, 4, false))) return rc;
         if (!nj.ev_a) MRG_HIP_CHECK(hipEventCreate(&nj.ev_a));
         if (!nj.ev_b) MRG_HIP_CHECK(hipEventCreate(&nj.ev_b));
         if (!nj.ev_a0) MRG_HIP_CHECK(hipEventCreate(&nj.ev_a0));
@@ -650,7 +643,7 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
         }
         launch_cc_detect_levels(lbs, dts, job.levs, douts, job.nlev, B, cc);
     }
-    const FbPinned pin = fb_layout(job.pin, job.nlev, B, cap, N);
+    const FbPinned pin = fb_layout(job.pin.p, job.nlev, B, cap, N);
     if (e == hipSuccess)  // counts | candidates: one block on both sides
         e = hipMemcpyAsync(pin.cnt, job.d_cnt.p, fb_align((size_t)job.nlev * B * 4) + (size_t)job.nlev * B * cap * 8, hipMemcpyDeviceToHost, cc);
     if (e == hipSuccess) e = hipEventRecord(job.ev_a, cc);

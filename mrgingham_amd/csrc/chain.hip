@@ -109,8 +109,8 @@ void end_op(mrgingham_amd_ctx* ctx) {
     // the op does not wait for the copy; mrgingham_amd_sync waits for the stream) into their page-locked mirror
     // (ensure_level_set allocates it; without one, or when the copy cannot be queued, the sync makes a blocking copy)
     ctx->status_copied[set] = false;
-    if (!ctx->status_pin[set]) return;
-    if (hipMemcpyAsync(ctx->status_pin[set], status_of(ctx, 0), ctx->status_pin_words[set] * sizeof(int32_t), hipMemcpyDeviceToHost,
+    if (!ctx->status_pin[set].p) return;
+    if (hipMemcpyAsync(ctx->status_pin[set].p, status_of(ctx, 0), ctx->status_pin[set].bytes, hipMemcpyDeviceToHost,
                        cur_cc(ctx)) == hipSuccess)
         ctx->status_copied[set] = true;
     else

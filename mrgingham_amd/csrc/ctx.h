@@ -3,7 +3,7 @@
 // status words, the pixel-only _batch entry points), chain.hip (the detector's stream scheduling: detect / refine /
 // chain calls, kernel timing, the sparse schedule), multi.hip (several devices), reference.hip (the reference's own C
 // symbols over one frame), boards.hip (find_boards: the level search, synchronous and pipelined), blobs_api.hip (the
-// blob detector and the circle-grid finder over a batch).
+// blob detector and the circle-grid finder over a batch), loader.hip (what the file-list loaders share).
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -11,6 +11,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mrgingham_amd.h"
@@ -23,6 +24,11 @@ namespace mrg {
 constexpr int kMaxLevel = 10;  // find_chessboard_corners.cc:433-436
 
 struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+// page-locked host memory, grown on demand like a DevBuf (ensure_pinned)
+struct PinBuf {
     void* p = nullptr;
     size_t bytes = 0;
 };
@@ -100,6 +106,21 @@ struct HostPool {
         for (auto& t : threads) t.join();
     }
 };
+
+// body(i) for every i of 0 .. n-1, handed out one at a time to at most nthreads threads of the pool (the caller is one of
+// them).  With a State, every thread owns one for the whole run and the body is body(i, state): buffers that are reused
+// from file to file.
+template <class State = char, class F>
+void for_files(HostPool& pool, int nthreads, int n, F&& body) {
+    std::atomic<int> next{0};
+    pool.run(nthreads < n ? nthreads : n, [&] {
+        State state{};
+        for (int i; (i = next.fetch_add(1)) < n;) {
+            if constexpr (std::is_invocable_v<F&, int>) body(i);
+            else body(i, state);
+        }
+    });
+}
 
 constexpr int kMaxSets = 3;  // scratch sets a context can rotate through (option "scratch_sets": 2 or 3)
 
@@ -180,12 +201,10 @@ struct mrgingham_amd_ctx {
     void* io_res_pin = nullptr;  // page-locked: count + first candidates of the single-frame detector
     // page-locked copies of the sets' status words ([level][counters_nf], what mrgingham_amd_sync inspects): they follow every
     // op on its component stream (end_op), so that the sync behind it reads host memory instead of making a blocking copy;
-    // allocated with counters2 (ensure_level_set): status_pin_words is what counters_nf implies, or 0 where that failed
-    int32_t* status_pin[kMaxSets] = {};
-    size_t status_pin_words[kMaxSets] = {};
+    // allocated with counters2 (ensure_level_set): status_pin.bytes is what counters_nf implies, or 0 where that failed
+    mrg::PinBuf status_pin[kMaxSets];
     bool status_copied[kMaxSets] = {};  // the LAST op on the set left its words in status_pin
-    void* io_pin = nullptr;  // page-locked staging of mrgingham_ChESS_response_5's way back
-    size_t io_pin_bytes = 0;
+    mrg::PinBuf io_pin;  // page-locked staging of mrgingham_ChESS_response_5's way back
     hipEvent_t io_ev[4] = {};
     mrg::DevBuf clk;  // two u64: shader cycles and constant-rate ticks of the probed workgroups (mrgingham_amd_sclk_mhz)
     mrg::DevBuf pre_scratch, pre_tmp, pre_out, pre16_scratch, io_frame16, dbg_img, dbg_resp, blob_scratch, blob_nodes, blob_out;
@@ -195,14 +214,20 @@ struct mrgingham_amd_ctx {
     int blob_chunk_frames = 0;
     hipEvent_t blob_ev[2] = {};  // around a chunk's kernels while kernel timing is on
     double blob_stat[8] = {};    // mrgingham_amd_blobs_stats (+ [7]: frames)
-    // mrgingham_amd_read_jpegs_batch (jpeg_idct.hip): two chunks of files in flight, one being parsed into its page-locked
-    // staging (coefficients | tables) while the other uploads into its device image and runs the inverse DCT; option
-    // "jpeg_chunk_frames" (test hook): at most that many frames per chunk, 0 = by jpeg_coef_budget
-    mrg::DevBuf jpeg_dev[2];
-    void* jpeg_pin[2] = {};
-    size_t jpeg_pin_bytes[2] = {};
-    hipEvent_t jpeg_ev[2] = {};
-    size_t jpeg_coef_budget = (size_t)1 << 30;  // both device buffers together
+    // The two chunk slots of the file loaders (loader.hip: loader_ring): two chunks of files in flight, one being decoded
+    // into its page-locked staging while the other uploads into its device image and runs its kernels; `ev` follows the
+    // chunk's last launch.  mrgingham_amd_read_jpegs_batch (jpeg_idct.hip; staging: coefficients | tables) and
+    // mrgingham_amd_read_pngs_batch (png_recon.hip; staging: scanlines) both use them.  Their calls never overlap,
+    // because both are synchronous, and each call sizes and fills what it reads: nothing a call leaves in a slot matters
+    // to the next.  The staging is zero only until its first use (ensure_pinned zeroes it when it grows); that is enough,
+    // because the IDCT kernel never reads a block outside width x height, and every decoded file covers those.
+    // Option "jpeg_chunk_frames" (test hook): at most that many frames per chunk, 0 = by jpeg_coef_budget
+    struct LoaderSlot {
+        mrg::DevBuf dev;
+        mrg::PinBuf pin;
+        hipEvent_t ev = nullptr;
+    } loader_slot[2];
+    size_t jpeg_coef_budget = (size_t)1 << 30;  // both device buffers together, for either loader
     int jpeg_chunk_frames = 0;
     // the device entropy path of the loader and mrgingham_amd_jpeg_entropy_batch (jpeg_huff.hip): per chunk slot one
     // staging image (frame records | tables | interval records | compressed bytes | one status byte per interval),
@@ -210,8 +235,7 @@ struct mrgingham_amd_ctx {
     // decode, 1: the device where the file has restart intervals), "jpeg_entropy_max_interval" (MCUs one lane may be
     // handed), "jpeg_entropy_memset" (0: lanes write whole blocks, 1: the area is zeroed in front and lanes store non-zeros)
     mrg::DevBuf jpeg_huff_dev[2];
-    void* jpeg_huff_pin[2] = {};
-    size_t jpeg_huff_pin_bytes[2] = {};
+    mrg::PinBuf jpeg_huff_pin[2];
     int jpeg_entropy = 0;
     int jpeg_entropy_max_interval = 1024;
     int jpeg_entropy_memset = 0;
@@ -220,16 +244,14 @@ struct mrgingham_amd_ctx {
     // subsequences.  Options "jpeg_sync" (0: such files keep the host decoder), "jpeg_sync_subsequence" (bytes per lane),
     // "jpeg_sync_max_rounds" (0: 8192 / jpeg_sync_subsequence), "jpeg_sync_time_phase" (tools: what kernel timing brackets)
     mrg::DevBuf jpeg_sync_dev[2], jpeg_sync_rec[2];
-    void* jpeg_sync_pin[2] = {};
-    size_t jpeg_sync_pin_bytes[2] = {};
+    mrg::PinBuf jpeg_sync_pin[2];
     int jpeg_sync = 0;
     int jpeg_sync_subsequence = 128;  // (measured: DESIGN.md section 4.10)
     int jpeg_sync_max_rounds = 0;
     int jpeg_sync_time_phase = 0;
-    // mrgingham_amd_read_pngs_batch / _png_reconstruct_batch (png_recon.hip): the loader's two chunk slots are the JPEG loader's
-    // (jpeg_dev, jpeg_pin, jpeg_ev, within jpeg_coef_budget: both loaders are synchronous); png_row: per frame of a launch the
-    // padded row that lane R - 1 hands to lane 0 of the next round; option "png_chunk_frames" (test hook): at most that
-    // many files per chunk, 0 = by the budget
+    // mrgingham_amd_read_pngs_batch / _png_reconstruct_batch (png_recon.hip): the loader runs on loader_slot, within
+    // jpeg_coef_budget; png_row: per frame of a launch the padded row that lane R - 1 hands to lane 0 of the next round;
+    // option "png_chunk_frames" (test hook): at most that many files per chunk, 0 = by the budget
     mrg::DevBuf png_row;
     int png_chunk_frames = 0;
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
@@ -258,8 +280,7 @@ struct mrgingham_amd_ctx {
         // d_cnt = counts | candidates (first pass), d_pts = boards | levels | point counts (refinement), d_pts0 = boards |
         // levels as they went in (what the dense repeat of a sparse refinement starts from)
         mrg::DevBuf d_cnt, d_pts, d_pts0;
-        void* pin = nullptr;  // pinned host staging: counts, candidates | boards, levels, point counts
-        size_t pin_bytes = 0;
+        mrg::PinBuf pin;  // pinned host staging: counts, candidates | boards, levels, point counts
         // the host part in progress (fb_host_begin .. fb_host_end): candidate lists of frames re-run at full capacity,
         // the frame counter of the grid-finder threads
         std::vector<std::vector<int32_t>> big;
@@ -316,6 +337,8 @@ constexpr int kCellsPerPoint = 9;  // sparse refinement: distinct cells the 3 x 
 // api.hip: errors, buffers, level scratch
 int fail(mrgingham_amd_ctx* ctx, int code, const char* fmt, ...);
 int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes);
+// at least `bytes` of page-locked memory; growth allocates bytes + bytes / slack_divisor (0: no slack), zeroed if asked
+int ensure_pinned(mrgingham_amd_ctx* ctx, PinBuf& b, size_t bytes, int slack_divisor, bool zero_on_growth);
 hipError_t copy_rows_async(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows,
                            hipMemcpyKind kind, hipStream_t s);
 int level_dims(int W, int H, int level, int* w, int* h);
@@ -360,7 +383,23 @@ int host_threads(int nthreads);
 // jpeg_idct.hip
 void launch_jpeg_idct(const int16_t* d_coef, int64_t coef_pitch, const uint16_t* d_quant, int nframes, int width, int height,
                       int blocks_w, uint8_t* d_out, int64_t frame_pitch, int stride, hipStream_t s);
-int ensure_pin(mrgingham_amd_ctx* ctx, int slot, size_t bytes);
+
+// loader.hip: what the file-list loaders (read_jpegs_batch, its device-entropy route, read_pngs_batch) share
+// the descriptor of a file list and its frames: 0, or MRGINGHAM_AMD_ERR_ARG with "bad <format> file batch descriptor"
+// (elem: bytes per sample, 1 or 2; a NULL entry of filenames is refused)
+int check_file_batch(mrgingham_amd_ctx* ctx, const char* format, const char* const* filenames, int nfiles, int width, int height,
+                     size_t elem, const void* d_out, int64_t frame_pitch, int stride, const int32_t* h_status);
+// zeroes width x height samples of `elem` bytes of frame `frame` (of a file that failed)
+hipError_t zero_frame(void* d_out, int64_t frame, int64_t frame_pitch, int stride, int width, int height, size_t elem, hipStream_t s);
+// The two-slot chunk ring on ctx->pix: chunks of `chunk` files alternate between the slots (one slot if there is one
+// chunk), whose device buffers are grown to dev_bytes and whose staging to pin_bytes (0: the stage grows it when it
+// needs it).  Per chunk: wait for the event of the slot's previous chunk and, given `finish`, finish(k) behind it; then
+// stage(k, f0, n) decodes files [f0, f0 + n) on the host and queues their uploads and launches; the slot's event is
+// recorded; after(k, f0, n), if given, queues what goes behind the record (the zeroing of failed frames).  At the end
+// the chunks still in flight are finished in slot order (only if there is a `finish`) and the stream is synchronised.
+using LoaderStage = std::function<int(int k, int f0, int n)>;
+int loader_ring(mrgingham_amd_ctx* ctx, int nfiles, int chunk, size_t dev_bytes, size_t pin_bytes, const LoaderStage& stage,
+                const LoaderStage& after, const std::function<int(int k)>& finish);
 // jpeg_huff.hip: mrgingham_amd_read_jpegs_batch with option "jpeg_entropy" 1 (arguments checked, geometry chosen there)
 int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
                               uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status, int bw, int bh,

@@ -106,20 +106,15 @@ int load_chunk(Run& R, int c) {
     for (int k = 0; k < n; ++k)
         if (!R.info[(size_t)ch.files[(size_t)k]].batch_loader()) host.push_back(k);
     if (!host.empty()) {
-        std::atomic<int> next{0};
-        auto worker = [&]() {
-            Image im;
-            for (int i; (i = next.fetch_add(1)) < (int)host.size();) {
-                const int k = host[(size_t)i];
-                if (read_image(R.names[ch.files[(size_t)k]], im) && im.depth == 8 && im.w == ch.w && im.h == ch.h) {
-                    memcpy(S.pin + (size_t)k * pitch, im.px8.data(), npx);
-                    S.load_status[(size_t)k] = 0;
-                } else {
-                    memset(S.pin + (size_t)k * pitch, 0, npx);  // (the frame is detected on with its chunk; its result is dropped)
-                }
+        for_files<Image>(ctx->pool, R.nthreads, (int)host.size(), [&](int i, Image& im) {
+            const int k = host[(size_t)i];
+            if (read_image(R.names[ch.files[(size_t)k]], im) && im.depth == 8 && im.w == ch.w && im.h == ch.h) {
+                memcpy(S.pin + (size_t)k * pitch, im.px8.data(), npx);
+                S.load_status[(size_t)k] = 0;
+            } else {
+                memset(S.pin + (size_t)k * pitch, 0, npx);  // (the frame is detected on with its chunk; its result is dropped)
             }
-        };
-        ctx->pool.run(R.nthreads < (int)host.size() ? R.nthreads : (int)host.size(), worker);
+        });
         for (size_t i = 0; i < host.size();) {
             size_t j = i + 1;
             while (j < host.size() && host[j] == host[j - 1] + 1) ++j;
@@ -253,18 +248,14 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
     R.info.resize((size_t)nfiles);
     std::vector<int32_t> key((size_t)nfiles, -1);
     {
-        std::atomic<int> next{0};
-        auto worker = [&]() {
-            for (int i; (i = next.fetch_add(1)) < nfiles;) {
-                FileInfo& f = R.info[(size_t)i];
-                if (!probe_image(filenames[i], &f.w, &f.h, &f.bits, &f.kind)) f = FileInfo{};
-                // (palette files keep the host decoder: read_pngs_batch would hand them to it anyway, one by one)
-                if ((loader_flags & MRGINGHAM_AMD_FILES_PNG_DEVICE) && f.kind == 2 && f.bits == 8)
-                    f.png_device = png_header(filenames[i], nullptr, nullptr, nullptr) != 3;
-            }
-        };
         HostPool probe_pool;
-        probe_pool.run(R.nthreads < nfiles ? R.nthreads : nfiles, worker);
+        for_files(probe_pool, R.nthreads, nfiles, [&](int i) {
+            FileInfo& f = R.info[(size_t)i];
+            if (!probe_image(filenames[i], &f.w, &f.h, &f.bits, &f.kind)) f = FileInfo{};
+            // (palette files keep the host decoder: read_pngs_batch would hand them to it anyway, one by one)
+            if ((loader_flags & MRGINGHAM_AMD_FILES_PNG_DEVICE) && f.kind == 2 && f.bits == 8)
+                f.png_device = png_header(filenames[i], nullptr, nullptr, nullptr) != 3;
+        });
     }
     size_t max_frame = 0, max_host_frame = 0;
     for (int i = 0; i < nfiles; ++i) {

@@ -8,7 +8,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
 
 #include "ctx.h"
 #include "image_io.h"
@@ -201,15 +200,7 @@ int sync_files(mrgingham_amd_ctx* ctx, int k, FileJob* jobs, int n, JpegSyncChun
 int ensure_image(mrgingham_amd_ctx* ctx, int slot, size_t bytes) {
     int rc;
     if (bytes > ctx->jpeg_huff_dev[slot].bytes && (rc = ensure(ctx, ctx->jpeg_huff_dev[slot], bytes + bytes / 4))) return rc;
-    if (bytes <= ctx->jpeg_huff_pin_bytes[slot]) return 0;
-    if (ctx->jpeg_huff_pin[slot]) {
-        MRG_HIP_CHECK(hipHostFree(ctx->jpeg_huff_pin[slot]));
-        ctx->jpeg_huff_pin[slot] = nullptr;
-        ctx->jpeg_huff_pin_bytes[slot] = 0;
-    }
-    MRG_HIP_CHECK(hipHostMalloc(&ctx->jpeg_huff_pin[slot], bytes + bytes / 4, hipHostMallocDefault));
-    ctx->jpeg_huff_pin_bytes[slot] = bytes + bytes / 4;
-    return 0;
+    return ensure_pinned(ctx, ctx->jpeg_huff_pin[slot], bytes, 4, false);
 }
 
 // Queues a filled image of slot k: the upload, the zeroing the chosen variant needs, the kernel, the status bytes back.
@@ -217,7 +208,7 @@ int ensure_image(mrgingham_amd_ctx* ctx, int slot, size_t bytes) {
 // coefficient area zeroed (the caller does not fill them itself).
 int queue_huff(mrgingham_amd_ctx* ctx, int k, const Layout& l, const FileJob* jobs, int n, int16_t* d_coef, int64_t coef_pitch,
                size_t area_elems, bool zero_others, hipStream_t s) {
-    char* pin = (char*)ctx->jpeg_huff_pin[k];
+    char* pin = (char*)ctx->jpeg_huff_pin[k].p;
     char* dev = (char*)ctx->jpeg_huff_dev[k].p;
     MRG_HIP_CHECK(hipMemcpyAsync(dev, pin, l.status, hipMemcpyHostToDevice, s));
     const bool front = ctx->jpeg_entropy_memset != 0;
@@ -275,125 +266,104 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
                               uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status, int bw, int bh,
                               int chunk) {
     const size_t per_frame = (size_t)bw * bh * 64;  // elements
-    const size_t coef_bytes = (size_t)chunk * per_frame * sizeof(int16_t), slot_bytes = coef_bytes + (size_t)chunk * 64 * sizeof(uint16_t);
-    const int nslots = nfiles > chunk ? 2 : 1;
-    int rc;
-    for (int k = 0; k < nslots; ++k) {
-        if ((rc = ensure(ctx, ctx->jpeg_dev[k], slot_bytes))) return rc;
-        if (!ctx->jpeg_ev[k]) MRG_HIP_CHECK(hipEventCreateWithFlags(&ctx->jpeg_ev[k], hipEventDisableTiming));
-    }
+    const size_t slot_bytes = (size_t)chunk * (per_frame * sizeof(int16_t) + 64 * sizeof(uint16_t));
     hipStream_t s = ctx->pix;
     std::vector<FileJob> jobs[2];
     std::vector<std::vector<uint8_t>> files[2];
     Layout lay[2];
     JpegSyncChunk sync[2];
     int first[2] = {0, 0}, count[2] = {0, 0};
-    bool busy[2] = {false, false};
+    // (the coefficient staging of a slot is grown where there is a file for the host threads to decode)
+    auto host_coef = [&](int k) { return ensure_pinned(ctx, ctx->loader_slot[k].pin, slot_bytes, 0, true); };
     // the chunk in slot k has passed the stream: its status bytes are on the host.  A file with a failed interval is
     // unreadable, and its frame is zeroed behind the transform that has run over it.
     // A file of the sync path whose write pass failed is unreadable as well; one that did not converge within the cap is
     // known only now: the pool threads decode those, their coefficient slices are uploaded and the transform runs over
     // their frames again (the table is in the image already).
     auto finish = [&](int k) -> int {
-        MRG_HIP_CHECK(hipEventSynchronize(ctx->jpeg_ev[k]));
-        busy[k] = false;
         std::vector<int> late;
         for (int i = 0; i < count[k]; ++i) {
             const FileJob& j = jobs[k][i];
             int32_t st = 0;
-            if (j.status == 0) st = all_decoded((const char*)ctx->jpeg_huff_pin[k], lay[k], j) ? 0 : -1;
+            if (j.status == 0) st = all_decoded((const char*)ctx->jpeg_huff_pin[k].p, lay[k], j) ? 0 : -1;
             else if (j.sync >= 0) st = jpeg_sync_status(ctx, k, sync[k], j.sync, nullptr);
             if (st == -3) late.push_back(i);
             if (st == -1) {
                 h_status[first[k] + i] = -1;
-                MRG_HIP_CHECK(hipMemset2DAsync(d_out + (size_t)(first[k] + i) * frame_pitch, (size_t)stride, 0, (size_t)width, (size_t)height, s));
+                MRG_HIP_CHECK(zero_frame(d_out, first[k] + i, frame_pitch, stride, width, height, 1, s));
             }
         }
         if (late.empty()) return 0;
         int rc;
-        if ((rc = ensure_pin(ctx, k, slot_bytes))) return rc;
-        int16_t* h_coef = (int16_t*)ctx->jpeg_pin[k];
-        std::atomic<int> next{0};
-        const int nlate = (int)late.size();
-        auto decode = [&]() {
-            for (int q; (q = next.fetch_add(1)) < nlate;) {
-                const int i = late[(size_t)q];
-                const FileJob& j = jobs[k][i];
-                JpegInfo info;
-                h_status[first[k] + i] = jpeg_coefficients(j.data, j.nbytes, h_coef + (size_t)i * per_frame, per_frame, bw, &info) == 0 ? 0 : -1;
-            }
-        };
-        ctx->pool.run(nthreads < nlate ? nthreads : nlate, decode);
-        char* dev = (char*)ctx->jpeg_dev[k].p;
+        if ((rc = host_coef(k))) return rc;
+        int16_t* h_coef = (int16_t*)ctx->loader_slot[k].pin.p;
+        for_files(ctx->pool, nthreads, (int)late.size(), [&](int q) {
+            const int i = late[(size_t)q];
+            const FileJob& j = jobs[k][i];
+            JpegInfo info;
+            h_status[first[k] + i] = jpeg_coefficients(j.data, j.nbytes, h_coef + (size_t)i * per_frame, per_frame, bw, &info) == 0 ? 0 : -1;
+        });
+        char* dev = (char*)ctx->loader_slot[k].dev.p;
         const uint16_t* d_quant = (const uint16_t*)((char*)ctx->jpeg_huff_dev[k].p + lay[k].quant);
         for (int i : late) {
-            uint8_t* frame = d_out + (size_t)(first[k] + i) * frame_pitch;
             if (h_status[first[k] + i] != 0) {
-                MRG_HIP_CHECK(hipMemset2DAsync(frame, (size_t)stride, 0, (size_t)width, (size_t)height, s));
+                MRG_HIP_CHECK(zero_frame(d_out, first[k] + i, frame_pitch, stride, width, height, 1, s));
                 continue;
             }
             int16_t* d_slice = (int16_t*)dev + (size_t)i * per_frame;
             MRG_HIP_CHECK(hipMemcpyAsync(d_slice, h_coef + (size_t)i * per_frame, per_frame * sizeof(int16_t), hipMemcpyHostToDevice, s));
-            launch_jpeg_idct(d_slice, (int64_t)per_frame, d_quant + (size_t)i * 64, 1, width, height, bw, frame, frame_pitch, stride, s);
+            launch_jpeg_idct(d_slice, (int64_t)per_frame, d_quant + (size_t)i * 64, 1, width, height, bw,
+                             d_out + (size_t)(first[k] + i) * frame_pitch, frame_pitch, stride, s);
         }
         MRG_HIP_CHECK(hipGetLastError());
         MRG_HIP_CHECK(hipStreamSynchronize(s));  // (the slot's staging is filled again next)
         return 0;
     };
-    for (int f0 = 0, k = 0; f0 < nfiles; f0 += chunk, k ^= nslots - 1) {
-        const int n = nfiles - f0 < chunk ? nfiles - f0 : chunk;
-        if (busy[k] && (rc = finish(k))) return rc;
+    auto stage = [&](int k, int f0, int n) -> int {
+        int rc;
         jobs[k].resize((size_t)chunk);
         files[k].resize((size_t)chunk);
         first[k] = f0;
         count[k] = n;
         // 1. host threads read and scan
-        std::atomic<int> next{0};
-        auto scan = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                FileJob& j = jobs[k][i];
-                j.data = nullptr;
-                try {
-                    if (read_file(filenames[f0 + i], files[k][i])) {
-                        j.data = files[k][i].data();
-                        j.nbytes = files[k][i].size();
-                    }
-                    plan_file(ctx, j, width, height, bw, bh);
-                } catch (...) {  // std::bad_alloc on a file too large to hold
-                    j.status = -1;
+        for_files(ctx->pool, nthreads, n, [&](int i) {
+            FileJob& j = jobs[k][i];
+            j.data = nullptr;
+            try {
+                if (read_file(filenames[f0 + i], files[k][i])) {
+                    j.data = files[k][i].data();
+                    j.nbytes = files[k][i].size();
                 }
+                plan_file(ctx, j, width, height, bw, bh);
+            } catch (...) {  // std::bad_alloc on a file too large to hold
+                j.status = -1;
             }
-        };
-        ctx->pool.run(nthreads < n ? nthreads : n, scan);
+        });
         lay[k] = lay_out(jobs[k].data(), n);
         if ((rc = ensure_image(ctx, k, lay[k].total))) return rc;
         if ((rc = sync_files(ctx, k, jobs[k].data(), n, &sync[k]))) return rc;
         int nhost = 0;
         for (int i = 0; i < n; ++i) nhost += jobs[k][i].status == -3 && jobs[k][i].sync < 0;
-        if (nhost && (rc = ensure_pin(ctx, k, slot_bytes))) return rc;
+        if (nhost && (rc = host_coef(k))) return rc;
+        int16_t* h_coef = (int16_t*)ctx->loader_slot[k].pin.p;
         // 2. the files the device takes go into the image; 3. the others are decoded by the same threads as without the
         // option, into the coefficient staging
-        int16_t* h_coef = (int16_t*)ctx->jpeg_pin[k];
-        char* image = (char*)ctx->jpeg_huff_pin[k];
-        next = 0;
-        auto fill = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                FileJob& j = jobs[k][i];
-                int32_t st = j.status;
-                if (j.sync >= 0) {  // (decoded unless finish() finds otherwise)
-                    jpeg_sync_fill(ctx, k, sync[k], j.sync, bh, bw);
-                    st = 0;
-                } else if (st == -3) {
-                    JpegInfo info;
-                    st = jpeg_coefficients(j.data, j.nbytes, h_coef + (size_t)i * per_frame, per_frame, bw, &info) == 0 ? 0 : -1;
-                }
-                fill_image(image, lay[k], j, i, bh, bw);
-                if (j.status == -3 && st == 0) memcpy((uint16_t*)(image + lay[k].quant) + (size_t)i * 64, j.scan.info.quant, 64 * sizeof(uint16_t));
-                h_status[f0 + i] = st;
+        char* image = (char*)ctx->jpeg_huff_pin[k].p;
+        for_files(ctx->pool, nthreads, n, [&](int i) {
+            FileJob& j = jobs[k][i];
+            int32_t st = j.status;
+            if (j.sync >= 0) {  // (decoded unless finish() finds otherwise)
+                jpeg_sync_fill(ctx, k, sync[k], j.sync, bh, bw);
+                st = 0;
+            } else if (st == -3) {
+                JpegInfo info;
+                st = jpeg_coefficients(j.data, j.nbytes, h_coef + (size_t)i * per_frame, per_frame, bw, &info) == 0 ? 0 : -1;
             }
-        };
-        ctx->pool.run(nthreads < n ? nthreads : n, fill);
-        char* dev = (char*)ctx->jpeg_dev[k].p;
+            fill_image(image, lay[k], j, i, bh, bw);
+            if (j.status == -3 && st == 0) memcpy((uint16_t*)(image + lay[k].quant) + (size_t)i * 64, j.scan.info.quant, 64 * sizeof(uint16_t));
+            h_status[f0 + i] = st;
+        });
+        char* dev = (char*)ctx->loader_slot[k].dev.p;
         for (int i = 0; i < n; ++i)  // only the slices the host has decoded are uploaded as coefficients
             if (jobs[k][i].status == -3 && jobs[k][i].sync < 0 && h_status[f0 + i] == 0)
                 MRG_HIP_CHECK(hipMemcpyAsync(dev + (size_t)i * per_frame * sizeof(int16_t), h_coef + (size_t)i * per_frame,
@@ -403,16 +373,14 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
         launch_jpeg_idct((const int16_t*)dev, (int64_t)per_frame, (const uint16_t*)((char*)ctx->jpeg_huff_dev[k].p + lay[k].quant), n, width,
                          height, bw, d_out + (size_t)f0 * frame_pitch, frame_pitch, stride, s);
         MRG_HIP_CHECK(hipGetLastError());
-        MRG_HIP_CHECK(hipEventRecord(ctx->jpeg_ev[k], s));
-        busy[k] = true;
-        for (int i = 0; i < n; ++i)
-            if (h_status[f0 + i] != 0)
-                MRG_HIP_CHECK(hipMemset2DAsync(d_out + (size_t)(f0 + i) * frame_pitch, (size_t)stride, 0, (size_t)width, (size_t)height, s));
-    }
-    for (int k = 0; k < nslots; ++k)
-        if (busy[k] && (rc = finish(k))) return rc;
-    MRG_HIP_CHECK(hipStreamSynchronize(s));
-    return MRGINGHAM_AMD_OK;
+        return 0;
+    };
+    auto zero_failed = [&](int, int f0, int n) -> int {
+        for (int i = f0; i < f0 + n; ++i)
+            if (h_status[i] != 0) MRG_HIP_CHECK(zero_frame(d_out, i, frame_pitch, stride, width, height, 1, s));
+        return 0;
+    };
+    return loader_ring(ctx, nfiles, chunk, slot_bytes, 0, stage, zero_failed, finish);
 }
 
 }  // namespace mrg
@@ -465,35 +433,27 @@ int mrgingham_amd_jpeg_entropy_batch(mrgingham_amd_ctx* ctx, const uint8_t* cons
         int n = 0;
         for (size_t bytes = 0; f0 + n < nfiles && n < 4096 && (n == 0 || bytes + nbytes[f0 + n] <= ((size_t)256 << 20)); ++n) bytes += nbytes[f0 + n];
         jobs.resize((size_t)n);
-        std::atomic<int> next{0};
-        auto scan = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                jobs[i].data = data[f0 + i];
-                jobs[i].nbytes = nbytes[f0 + i];
-                try {
-                    plan_file(ctx, jobs[i], width, height, blocks_w, blocks_h);
-                } catch (...) {
-                    jobs[i].status = -1;
-                }
+        for_files(ctx->pool, nthreads, n, [&](int i) {
+            jobs[i].data = data[f0 + i];
+            jobs[i].nbytes = nbytes[f0 + i];
+            try {
+                plan_file(ctx, jobs[i], width, height, blocks_w, blocks_h);
+            } catch (...) {
+                jobs[i].status = -1;
             }
-        };
-        ctx->pool.run(nthreads < n ? nthreads : n, scan);
+        });
         const Layout l = lay_out(jobs.data(), n);
         int rc;
         if ((rc = ensure_image(ctx, 0, l.total))) return rc;
         JpegSyncChunk sync;
         if ((rc = sync_files(ctx, 0, jobs.data(), n, &sync))) return rc;
-        char* image = (char*)ctx->jpeg_huff_pin[0];
-        next = 0;
-        auto fill = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                fill_image(image, l, jobs[i], i, blocks_h, blocks_w);
-                if (jobs[i].sync < 0) continue;  // (its table goes up with the others; taken back below if it fails)
-                jpeg_sync_fill(ctx, 0, sync, jobs[i].sync, blocks_h, blocks_w);
-                memcpy((uint16_t*)(image + l.quant) + (size_t)i * 64, jobs[i].scan.info.quant, 64 * sizeof(uint16_t));
-            }
-        };
-        ctx->pool.run(nthreads < n ? nthreads : n, fill);
+        char* image = (char*)ctx->jpeg_huff_pin[0].p;
+        for_files(ctx->pool, nthreads, n, [&](int i) {
+            fill_image(image, l, jobs[i], i, blocks_h, blocks_w);
+            if (jobs[i].sync < 0) return;  // (its table goes up with the others; taken back below if it fails)
+            jpeg_sync_fill(ctx, 0, sync, jobs[i].sync, blocks_h, blocks_w);
+            memcpy((uint16_t*)(image + l.quant) + (size_t)i * 64, jobs[i].scan.info.quant, 64 * sizeof(uint16_t));
+        });
         int16_t* coef = d_coef + (size_t)f0 * (size_t)coef_pitch;
         if ((rc = queue_huff(ctx, 0, l, jobs.data(), n, coef, coef_pitch, area, true, s))) return rc;
         if ((rc = jpeg_sync_launch(ctx, 0, sync, coef, coef_pitch, area, s))) return rc;

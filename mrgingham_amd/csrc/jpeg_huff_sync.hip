@@ -231,18 +231,6 @@ __global__ __launch_bounds__(kLanes) void jpeg_sync_write_kernel(const uint8_t* 
     if (rc) atomicOr(&words[f].flags, (uint32_t)rc);
 }
 
-int ensure_host(mrgingham_amd_ctx* ctx, int slot, size_t bytes) {
-    if (bytes <= ctx->jpeg_sync_pin_bytes[slot]) return 0;
-    if (ctx->jpeg_sync_pin[slot]) {
-        MRG_HIP_CHECK(hipHostFree(ctx->jpeg_sync_pin[slot]));
-        ctx->jpeg_sync_pin[slot] = nullptr;
-        ctx->jpeg_sync_pin_bytes[slot] = 0;
-    }
-    MRG_HIP_CHECK(hipHostMalloc(&ctx->jpeg_sync_pin[slot], bytes + bytes / 4, hipHostMallocDefault));
-    ctx->jpeg_sync_pin_bytes[slot] = bytes + bytes / 4;
-    return 0;
-}
-
 }  // namespace
 
 namespace mrg {
@@ -285,7 +273,7 @@ int jpeg_sync_lay_out(mrgingham_amd_ctx* ctx, int k, JpegSyncChunk* ch) {
     ch->total = ch->words + n * sizeof(SyncWords);
     if (ch->nrecords >= ((size_t)1 << 31)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "too many JPEG subsequences in one chunk");
     int rc;
-    if ((rc = ensure_host(ctx, k, ch->total))) return rc;
+    if ((rc = ensure_pinned(ctx, ctx->jpeg_sync_pin[k], ch->total, 4, false))) return rc;
     if ((rc = ensure(ctx, ctx->jpeg_sync_dev[k], ch->words))) return rc;
     // device only: words | spec | two record buffers | starts
     const size_t recs = ch->nrecords * sizeof(JpegSyncRecord);
@@ -294,7 +282,7 @@ int jpeg_sync_lay_out(mrgingham_amd_ctx* ctx, int k, JpegSyncChunk* ch) {
 }
 
 void jpeg_sync_fill(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int i, int blocks_h, int pitch_blocks) {
-    char* image = (char*)ctx->jpeg_sync_pin[k];
+    char* image = (char*)ctx->jpeg_sync_pin[k].p;
     const JpegSyncFile& j = ch.files[(size_t)i];
     const JpegScan& sc = *j.scan;
     SyncFrame fr;
@@ -320,7 +308,7 @@ int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int
                      hipStream_t s) {
     const int n = (int)ch.files.size();
     if (n == 0) return 0;
-    char* pin = (char*)ctx->jpeg_sync_pin[k];
+    char* pin = (char*)ctx->jpeg_sync_pin[k].p;
     char* dev = (char*)ctx->jpeg_sync_dev[k].p;
     char* scratch = (char*)ctx->jpeg_sync_rec[k].p;
     const uint32_t S = (uint32_t)ctx->jpeg_sync_subsequence, R = (uint32_t)jpeg_sync_max_rounds(ctx);
@@ -376,7 +364,7 @@ int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int
 }
 
 int32_t jpeg_sync_status(const mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int i, int* rounds) {
-    const SyncWords w = ((const SyncWords*)((const char*)ctx->jpeg_sync_pin[k] + ch.words))[i];
+    const SyncWords w = ((const SyncWords*)((const char*)ctx->jpeg_sync_pin[k].p + ch.words))[i];
     if (rounds) *rounds = (int)w.last_changed;
     if (w.flags & kNotConverged) return -3;
     return (w.flags & kScanReached) && (w.flags & kReached) && !(w.flags & kError) ? 0 : -1;

@@ -4,12 +4,12 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
 
 #include "ctx.h"
 #include "image_io.h"
 #include "jpeg.h"
 #include "jpeg_idct8.h"
+#include "loader.h"
 
 using namespace mrg;
 
@@ -118,20 +118,6 @@ void launch_jpeg_idct(const int16_t* d_coef, int64_t coef_pitch, const uint16_t*
     }
 }
 
-// page-locked staging of one chunk slot, grown on demand (zeroed once: blocks no file covers are uploaded as they are)
-int ensure_pin(mrgingham_amd_ctx* ctx, int slot, size_t bytes) {
-    if (bytes <= ctx->jpeg_pin_bytes[slot]) return 0;
-    if (ctx->jpeg_pin[slot]) {
-        MRG_HIP_CHECK(hipHostFree(ctx->jpeg_pin[slot]));
-        ctx->jpeg_pin[slot] = nullptr;
-        ctx->jpeg_pin_bytes[slot] = 0;
-    }
-    MRG_HIP_CHECK(hipHostMalloc(&ctx->jpeg_pin[slot], bytes, hipHostMallocDefault));
-    ctx->jpeg_pin_bytes[slot] = bytes;
-    memset(ctx->jpeg_pin[slot], 0, bytes);
-    return 0;
-}
-
 }  // namespace mrg
 
 extern "C" {
@@ -167,11 +153,8 @@ int mrgingham_amd_jpeg_idct_batch(mrgingham_amd_ctx* ctx, const int16_t* d_coef,
 
 int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
                                    uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status) {
-    if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
-    if (nfiles < 0 || width <= 0 || height <= 0 || stride < width || frame_pitch < 0 || (nfiles > 0 && (!filenames || !d_out || !h_status)))
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad JPEG file batch descriptor");
-    if (width > 32767 || height > 32767)
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "frames larger than 32767 pixels per side are not supported");
+    int rc = check_file_batch(ctx, "JPEG", filenames, nfiles, width, height, 1, d_out, frame_pitch, stride, h_status);
+    if (rc) return rc;
     if (nfiles == 0) return 0;
     fb_drain(ctx);
     const CallerDevice caller_device_;
@@ -188,65 +171,47 @@ int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
     };
     const int bw = padded(width), bh = padded(height);
     const size_t per_frame = (size_t)bw * bh * 64;  // elements
-    size_t fit = ctx->jpeg_coef_budget / 2 / (per_frame * sizeof(int16_t));
-    int chunk = fit < 1 ? 1 : fit > (size_t)nfiles ? nfiles : (int)fit;
-    if (chunk > nthreads) chunk -= chunk % nthreads;  // whole rounds of the host threads
-    if (ctx->jpeg_chunk_frames > 0 && chunk > ctx->jpeg_chunk_frames) chunk = ctx->jpeg_chunk_frames;
+    const int chunk = loader_chunk_frames(ctx->jpeg_coef_budget, per_frame * sizeof(int16_t), nfiles, nthreads, ctx->jpeg_chunk_frames);
     if (ctx->jpeg_entropy)  // files with restart intervals are Huffman-decoded on the device (jpeg_huff.hip)
         return read_jpegs_device_entropy(ctx, filenames, nfiles, width, height, d_out, frame_pitch, stride, nthreads, h_status, bw, bh, chunk);
     const size_t coef_bytes = (size_t)chunk * per_frame * sizeof(int16_t), slot_bytes = coef_bytes + (size_t)chunk * 64 * sizeof(uint16_t);
-    const int nslots = nfiles > chunk ? 2 : 1;
-    int rc;
-    for (int k = 0; k < nslots; ++k) {
-        if ((rc = ensure(ctx, ctx->jpeg_dev[k], slot_bytes))) return rc;
-        if ((rc = ensure_pin(ctx, k, slot_bytes))) return rc;
-        if (!ctx->jpeg_ev[k]) MRG_HIP_CHECK(hipEventCreateWithFlags(&ctx->jpeg_ev[k], hipEventDisableTiming));
-    }
     hipStream_t s = ctx->pix;
-    bool busy[2] = {false, false};
-    for (int f0 = 0, k = 0; f0 < nfiles; f0 += chunk, k ^= nslots - 1) {
-        const int n = nfiles - f0 < chunk ? nfiles - f0 : chunk;
-        if (busy[k]) MRG_HIP_CHECK(hipEventSynchronize(ctx->jpeg_ev[k]));  // the upload out of this staging is done
-        int16_t* h_coef = (int16_t*)ctx->jpeg_pin[k];
-        uint16_t* h_quant = (uint16_t*)((char*)ctx->jpeg_pin[k] + coef_bytes);
-        std::atomic<int> next{0};
-        auto worker = [&]() {
-            std::vector<uint8_t> file;
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                int32_t st = -1;
-                JpegInfo info;
-                try {
-                    if (read_file(filenames[f0 + i], file) && jpeg_coefficients(file.data(), file.size(), nullptr, 0, 0, &info) == 0) {
-                        if (info.width != width || info.height != height) st = -2;
-                        else if (jpeg_coefficients(file.data(), file.size(), h_coef + (size_t)i * per_frame, per_frame, bw, &info) == 0) st = 0;
-                    }
-                } catch (...) {  // std::bad_alloc on a file too large to hold
-                    st = -1;
+    auto stage = [&](int k, int f0, int n) -> int {
+        int16_t* h_coef = (int16_t*)ctx->loader_slot[k].pin.p;
+        uint16_t* h_quant = (uint16_t*)((char*)h_coef + coef_bytes);
+        for_files<std::vector<uint8_t>>(ctx->pool, nthreads, n, [&](int i, std::vector<uint8_t>& file) {
+            int32_t st = -1;
+            JpegInfo info;
+            try {
+                if (read_file(filenames[f0 + i], file) && jpeg_coefficients(file.data(), file.size(), nullptr, 0, 0, &info) == 0) {
+                    if (info.width != width || info.height != height) st = -2;
+                    else if (jpeg_coefficients(file.data(), file.size(), h_coef + (size_t)i * per_frame, per_frame, bw, &info) == 0) st = 0;
                 }
-                if (st == 0) memcpy(h_quant + (size_t)i * 64, info.quant, sizeof(info.quant));
-                h_status[f0 + i] = st;
+            } catch (...) {  // std::bad_alloc on a file too large to hold
+                st = -1;
             }
-        };
-        ctx->pool.run(nthreads < n ? nthreads : n, worker);
-        // one upload (coefficients | tables, laid out alike on both sides), one launch; failed files: zeros afterwards
-        char* dev = (char*)ctx->jpeg_dev[k].p;
+            if (st == 0) memcpy(h_quant + (size_t)i * 64, info.quant, sizeof(info.quant));
+            h_status[f0 + i] = st;
+        });
+        // one upload (coefficients | tables, laid out alike on both sides), one launch
+        char* dev = (char*)ctx->loader_slot[k].dev.p;
         if (n == chunk) {
-            MRG_HIP_CHECK(hipMemcpyAsync(dev, ctx->jpeg_pin[k], slot_bytes, hipMemcpyHostToDevice, s));
+            MRG_HIP_CHECK(hipMemcpyAsync(dev, h_coef, slot_bytes, hipMemcpyHostToDevice, s));
         } else {  // the last, shorter chunk: not the unused coefficient slots in between
-            MRG_HIP_CHECK(hipMemcpyAsync(dev, ctx->jpeg_pin[k], (size_t)n * per_frame * sizeof(int16_t), hipMemcpyHostToDevice, s));
+            MRG_HIP_CHECK(hipMemcpyAsync(dev, h_coef, (size_t)n * per_frame * sizeof(int16_t), hipMemcpyHostToDevice, s));
             MRG_HIP_CHECK(hipMemcpyAsync(dev + coef_bytes, h_quant, (size_t)n * 64 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         }
         launch_jpeg_idct((const int16_t*)dev, (int64_t)per_frame, (const uint16_t*)(dev + coef_bytes), n, width, height, bw,
                          d_out + (size_t)f0 * frame_pitch, frame_pitch, stride, s);
         MRG_HIP_CHECK(hipGetLastError());
-        MRG_HIP_CHECK(hipEventRecord(ctx->jpeg_ev[k], s));
-        busy[k] = true;
-        for (int i = 0; i < n; ++i)
-            if (h_status[f0 + i] != 0)
-                MRG_HIP_CHECK(hipMemset2DAsync(d_out + (size_t)(f0 + i) * frame_pitch, (size_t)stride, 0, (size_t)width, (size_t)height, s));
-    }
-    MRG_HIP_CHECK(hipStreamSynchronize(s));
-    return MRGINGHAM_AMD_OK;
+        return 0;
+    };
+    auto zero_failed = [&](int, int f0, int n) -> int {  // failed files: zeros afterwards
+        for (int i = f0; i < f0 + n; ++i)
+            if (h_status[i] != 0) MRG_HIP_CHECK(zero_frame(d_out, i, frame_pitch, stride, width, height, 1, s));
+        return 0;
+    };
+    return loader_ring(ctx, nfiles, chunk, slot_bytes, slot_bytes, stage, zero_failed, nullptr);
 }
 
 }  // extern "C"

@@ -5,10 +5,11 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <atomic>
+#include <algorithm>
 
 #include "ctx.h"
 #include "image_io.h"
+#include "loader.h"
 #include "png_filter.h"
 
 using namespace mrg;
@@ -200,88 +201,56 @@ int mrgingham_amd_png_reconstruct_batch(mrgingham_amd_ctx* ctx, const uint8_t* d
 
 int mrgingham_amd_read_pngs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height, int bits,
                                   void* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status) {
-    if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
-    if (nfiles < 0 || width <= 0 || height <= 0 || (bits != 8 && bits != 16) || stride < width || frame_pitch < 0 ||
-        (nfiles > 0 && (!filenames || !d_out || !h_status)) || (bits == 16 && ((uintptr_t)d_out & 1)))
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad PNG file batch descriptor");
-    if (width > 32767 || height > 32767)
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "frames larger than 32767 pixels per side are not supported");
-    for (int i = 0; i < nfiles; ++i)
-        if (!filenames[i]) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad PNG file batch descriptor");
+    const size_t es = bits == 8 ? 1 : bits == 16 ? 2 : 0;
+    int rc = check_file_batch(ctx, "PNG", filenames, nfiles, width, height, es, d_out, frame_pitch, stride, h_status);
+    if (rc) return rc;
     if (nfiles == 0) return 0;
     fb_drain(ctx);
     const CallerDevice caller_device_;
     MRG_HIP_CHECK(hipSetDevice(ctx->device));
     nthreads = host_threads(nthreads);
-    const size_t es = (size_t)bits / 8;
     uint8_t* const out = (uint8_t*)d_out;
 
     // every file of a chunk gets ONE area of the staging, sized for the widest pixel the headers of this size and depth
     // announce (a palette file's host-decoded bytes fit any area: width * height < (width + 1) * height)
-    int most_bpp = 1;
-    {
-        std::vector<int> file_bpp((size_t)nfiles, 0);
-        std::atomic<int> next{0};
-        auto worker = [&]() {
-            for (int i; (i = next.fetch_add(1)) < nfiles;) {
-                int w = 0, h = 0, b = 0;
-                const int ct = png_header(filenames[i], &w, &h, &b);
-                if (ct >= 0 && w == width && h == height && b == bits) file_bpp[(size_t)i] = png_bpp(b, ct);
-            }
-        };
-        ctx->pool.run(nthreads < nfiles ? nthreads : nfiles, worker);
-        for (int v : file_bpp) most_bpp = v > most_bpp ? v : most_bpp;
-    }
+    std::vector<int> file_bpp((size_t)nfiles, 1);
+    for_files(ctx->pool, nthreads, nfiles, [&](int i) {
+        int w = 0, h = 0, b = 0;
+        const int ct = png_header(filenames[i], &w, &h, &b);
+        if (ct >= 0 && w == width && h == height && b == bits) file_bpp[(size_t)i] = png_bpp(b, ct);
+    });
+    const int most_bpp = *std::max_element(file_bpp.begin(), file_bpp.end());
     const size_t area = (((size_t)width * most_bpp + 1) * height + 15) & ~(size_t)15;
-    size_t fit = ctx->jpeg_coef_budget / 2 / area;
-    int chunk = fit < 1 ? 1 : fit > (size_t)nfiles ? nfiles : (int)fit;
-    if (chunk > nthreads) chunk -= chunk % nthreads;  // whole rounds of the host threads
-    if (ctx->png_chunk_frames > 0 && chunk > ctx->png_chunk_frames) chunk = ctx->png_chunk_frames;
-    // the chunk slots are the JPEG loader's (two calls of the loaders never overlap: both are synchronous)
-    const int nslots = nfiles > chunk ? 2 : 1;
-    int rc;
-    for (int k = 0; k < nslots; ++k) {
-        if ((rc = ensure(ctx, ctx->jpeg_dev[k], (size_t)chunk * area))) return rc;
-        if ((rc = ensure_pin(ctx, k, (size_t)chunk * area))) return rc;
-        if (!ctx->jpeg_ev[k]) MRG_HIP_CHECK(hipEventCreateWithFlags(&ctx->jpeg_ev[k], hipEventDisableTiming));
-    }
+    const int chunk = loader_chunk_frames(ctx->jpeg_coef_budget, area, nfiles, nthreads, ctx->png_chunk_frames);
     hipStream_t s = ctx->pix;
-    bool busy[2] = {false, false};
     std::vector<int> kind((size_t)chunk);  // per file of the chunk: its colour type, 3 = decoded on the host, -1 = failed
-    for (int f0 = 0, k = 0; f0 < nfiles; f0 += chunk, k ^= nslots - 1) {
-        const int n = nfiles - f0 < chunk ? nfiles - f0 : chunk;
-        if (busy[k]) MRG_HIP_CHECK(hipEventSynchronize(ctx->jpeg_ev[k]));  // the upload out of this staging is done
-        uint8_t* h_scan = (uint8_t*)ctx->jpeg_pin[k];
-        std::atomic<int> next{0};
-        auto worker = [&]() {
-            std::vector<uint8_t> file;
-            Image im;
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                int32_t st = -1;
-                int w = 0, h = 0, b = 0, ct = -1;
-                uint8_t* dst = h_scan + (size_t)i * area;
-                try {
-                    if (read_file(filenames[f0 + i], file)) {
-                        const int head = png_scanlines(file.data(), file.size(), nullptr, 0, &w, &h, &b, &ct);
-                        if (head == 0 || head == kPngNotTaken) {
-                            if (w != width || h != height || b != bits) st = -2;
-                            else if (head == 0) st = png_scanlines(file.data(), file.size(), dst, area, &w, &h, &b, &ct) == 0 ? 0 : -1;
-                            else if (read_image(filenames[f0 + i], im) && im.depth == 8 && im.w == width && im.h == height) {
-                                memcpy(dst, im.px8.data(), (size_t)width * height);  // the device route does not take it: the host decoder's bytes
-                                st = 0;
-                            }
+    struct Buffers { std::vector<uint8_t> file; Image im; };
+    auto stage = [&](int k, int f0, int n) -> int {
+        uint8_t* h_scan = (uint8_t*)ctx->loader_slot[k].pin.p;
+        for_files<Buffers>(ctx->pool, nthreads, n, [&](int i, Buffers& t) {
+            int32_t st = -1;
+            int w = 0, h = 0, b = 0, ct = -1;
+            uint8_t* dst = h_scan + (size_t)i * area;
+            try {
+                if (read_file(filenames[f0 + i], t.file)) {
+                    const int head = png_scanlines(t.file.data(), t.file.size(), nullptr, 0, &w, &h, &b, &ct);
+                    if (head == 0 || head == kPngNotTaken) {
+                        if (w != width || h != height || b != bits) st = -2;
+                        else if (head == 0) st = png_scanlines(t.file.data(), t.file.size(), dst, area, &w, &h, &b, &ct) == 0 ? 0 : -1;
+                        else if (read_image(filenames[f0 + i], t.im) && t.im.depth == 8 && t.im.w == width && t.im.h == height) {
+                            memcpy(dst, t.im.px8.data(), (size_t)width * height);  // the device route does not take it: the host decoder's bytes
+                            st = 0;
                         }
                     }
-                } catch (...) {  // std::bad_alloc on a file too large to hold
-                    st = -1;
                 }
-                kind[(size_t)i] = st == 0 ? ct : -1;
-                h_status[f0 + i] = st;
+            } catch (...) {  // std::bad_alloc on a file too large to hold
+                st = -1;
             }
-        };
-        ctx->pool.run(nthreads < n ? nthreads : n, worker);
+            kind[(size_t)i] = st == 0 ? ct : -1;
+            h_status[f0 + i] = st;
+        });
         // one upload, one launch per run of files of one colour type; failed files: zeros
-        uint8_t* dev = (uint8_t*)ctx->jpeg_dev[k].p;
+        uint8_t* dev = (uint8_t*)ctx->loader_slot[k].dev.p;
         MRG_HIP_CHECK(hipMemcpyAsync(dev, h_scan, (size_t)n * area, hipMemcpyHostToDevice, s));
         for (int i = 0; i < n;) {
             int e = i + 1;
@@ -292,19 +261,18 @@ int mrgingham_amd_read_pngs_batch(mrgingham_amd_ctx* ctx, const char* const* fil
                     MRG_HIP_CHECK(hipMemcpy2DAsync(out + (size_t)(f0 + q) * frame_pitch * es, (size_t)stride, dev + (size_t)q * area, (size_t)width,
                                                    (size_t)width, (size_t)height, hipMemcpyDeviceToDevice, s));
             } else if (kind[(size_t)i] >= 0) {
+                int rc;
                 if ((rc = launch_png_recon(ctx, dev + (size_t)i * area, (int64_t)area, e - i, width, height, bits, kind[(size_t)i], o, frame_pitch, stride, s)))
                     return rc;
             } else {
-                for (int q = i; q < e; ++q)
-                    MRG_HIP_CHECK(hipMemset2DAsync(out + (size_t)(f0 + q) * frame_pitch * es, (size_t)stride * es, 0, (size_t)width * es, (size_t)height, s));
+                for (int q = i; q < e; ++q) MRG_HIP_CHECK(zero_frame(d_out, f0 + q, frame_pitch, stride, width, height, es, s));
             }
             i = e;
         }
-        MRG_HIP_CHECK(hipEventRecord(ctx->jpeg_ev[k], s));
-        busy[k] = true;
-    }
-    MRG_HIP_CHECK(hipStreamSynchronize(s));
-    return MRGINGHAM_AMD_OK;
+        return 0;
+    };
+    // the chunk slots are shared with the JPEG loader (ctx.h: loader_slot)
+    return loader_ring(ctx, nfiles, chunk, (size_t)chunk * area, (size_t)chunk * area, stage, nullptr, nullptr);
 }
 
 }  // extern "C"

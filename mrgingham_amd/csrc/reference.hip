@@ -419,16 +419,10 @@ void mrgingham_ChESS_response_5(int16_t* response, const uint8_t* image, int w, 
         // caller's array as soon as the copy that carries it has landed.
         const bool small = bytes < (4u << 20);
         const int kChunks = small ? 1 : 4;
-        if (bytes > ctx->io_pin_bytes) {
-            if (ctx->io_pin) hipHostFree(ctx->io_pin);
-            ctx->io_pin = nullptr;
-            ctx->io_pin_bytes = 0;
-            if (hipHostMalloc(&ctx->io_pin, bytes + bytes / 8, hipHostMallocDefault) != hipSuccess) ctx->io_pin = nullptr;
-            else ctx->io_pin_bytes = bytes + bytes / 8;
-        }
+        (void)ensure_pinned(ctx, ctx->io_pin, bytes, 8, false);  // (without it: the message below)
         for (int c = 0; c < kChunks; ++c)
             if (!ctx->io_ev[c]) hipEventCreateWithFlags(&ctx->io_ev[c], hipEventDisableTiming);
-        if (!ctx->io_pin || !ctx->io_ev[kChunks - 1]) {
+        if (!ctx->io_pin.p || !ctx->io_ev[kChunks - 1]) {
             fprintf(stderr, "mrgingham_amd: ChESS response failed: no page-locked staging\n");
             return;
         }
@@ -436,14 +430,14 @@ void mrgingham_ChESS_response_5(int16_t* response, const uint8_t* image, int w, 
         for (int c = 0; c < kChunks && e == hipSuccess; ++c) {
             const int y0 = c * rows_per, y1 = y0 + rows_per < h ? y0 + rows_per : h;
             if (y1 > y0)
-                e = hipMemcpyAsync((char*)ctx->io_pin + (size_t)y0 * w * 2, (const char*)ctx->io_out.p + (size_t)y0 * w * 2,
+                e = hipMemcpyAsync((char*)ctx->io_pin.p + (size_t)y0 * w * 2, (const char*)ctx->io_out.p + (size_t)y0 * w * 2,
                                    (size_t)(y1 - y0) * w * 2, hipMemcpyDeviceToHost, ctx->pix);
             if (e == hipSuccess) e = hipEventRecord(ctx->io_ev[c], ctx->pix);
         }
         if (e == hipSuccess) {
             std::atomic<int> next{0};
             std::atomic<int> failed{0};
-            const int16_t* pin = (const int16_t*)ctx->io_pin;
+            const int16_t* pin = (const int16_t*)ctx->io_pin.p;
             const int device = ctx->device;
             hipEvent_t* evs = ctx->io_ev;
             constexpr int kBlock = 32;  // rows per work item

@@ -73,20 +73,30 @@ def test_plan_fixed_shapes():
         mrgingham_amd.files_plan([1, 2], 0)
 
 
-def test_plan_program_under_sanitizers(tmp_path):
-    """tests/boundary/files_plan_main.cpp includes files_plan.h and runs as a program of its own."""
+def _run_under_sanitizers(tmp_path, name, *args):
+    """tests/boundary/<name>_main.cpp, which includes a host-only header of csrc/, built and run as a program of its own."""
     probe = tmp_path / "probe.cpp"
     probe.write_text("int main() { return 0; }\n")
     flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
     r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
     if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
         pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "files_plan")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "files_plan_main.cpp"),
+    exe = str(tmp_path / name)
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", name + "_main.cpp"),
                         "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe, "1500"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
+
+
+def test_plan_program_under_sanitizers(tmp_path):
+    """tests/boundary/files_plan_main.cpp includes files_plan.h and runs as a program of its own."""
+    _run_under_sanitizers(tmp_path, "files_plan", "1500")
+
+
+def test_loader_chunk_program_under_sanitizers(tmp_path):
+    """tests/boundary/loader_plan_main.cpp: loader.h's loader_chunk_frames against a hand-made table and its properties."""
+    _run_under_sanitizers(tmp_path, "loader_plan", "4000")
 
 
 def _decoder_says(path):

@@ -184,6 +184,11 @@ def test_read_jpegs_loader_boundary(det, seven_files):
                 (names, 2, 48, 64, out.data_ptr(), 64 * 53, 53, 2, None)):
         assert L.mrgingham_amd_read_jpegs_batch(det.ctx, *bad) == ERR_ARG
     assert L.mrgingham_amd_read_jpegs_batch(None, *args) == ERR_ARG
+    out.fill_(9)                                                                      # a NULL entry in the list: refused up front
+    status[:] = 5
+    holed = (ctypes.c_char_p * 2)(os.fsencode(seven_files[0]), None)
+    assert L.mrgingham_amd_read_jpegs_batch(det.ctx, holed, *args[1:]) == ERR_ARG
+    assert (out == 9).all() and status.tolist() == [5, 5]
     frames, st = det.read_jpegs([str(seven_files[0]) + ".missing"])
     assert tuple(frames.shape) == (1, 0, 0) and st.tolist() == [-1]
 

@@ -2,7 +2,8 @@
 # Do the device functions of <old.hip> come out instruction for instruction from <new.hip> [<new2.hip> ...] together?
 # usage: tools/isa_same.sh <old.hip> <new.hip> [<new2.hip> ...] [-- extra hipcc flags, e.g. -DMRG_EXPERIMENT]
 # (<old.hip> may lie anywhere, e.g. `git show HEAD~1:mrgingham_amd/csrc/cc.hip > /tmp/cc_old.hip`: csrc/ is on the include path)
-# Every file is compiled with the library's flags to device assembly; of every function `_ZN3mrg...:` the text up to its
+# Every file is compiled with the library's flags to device assembly; of every function `_ZN3mrg...:` (and of the kernels
+# of an anonymous namespace, `_ZN12_GLOBAL__N_1...:`; functions only, not the constant tables) the text up to its
 # .Lfunc_end is kept, without comments (`;` to the end of the line), with every local label `.L<name><number>` written `.L`
 # (their numbering differs between any two compilations), without trailing blanks and empty lines.  One line per function:
 # `same` or `DIFFERENT`; `MISSING` / `EXTRA` for a symbol only one side has.  Exit status 1 unless all are `same`.
@@ -20,14 +21,15 @@ functions_of() {  # <file.hip> <directory>: one file per function, named by its 
     /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -I"$R/mrgingham_amd/csrc" "${@:3}" \
         --offload-device-only -S "$1" -o "$2.s"
     awk -v d="$2" '
-        /^_ZN3mrg[A-Za-z0-9_]*:/ { out = d "/" substr($1, 1, length($1) - 1) }
+        /^[ \t]*\.type[ \t].*,@function/ { f = $2; sub(/,.*/, "", f); isfn[f] = 1 }
+        /^_ZN(3mrg|12_GLOBAL__N_1)[A-Za-z0-9_]*:/ { n = substr($1, 1, length($1) - 1); out = (n in isfn) ? d "/" n : "" }
         /^\.Lfunc_end/           { out = "" }
         out != "" { l = $0; sub(/;.*/, "", l); gsub(/\.L[A-Za-z_]*[0-9_]*/, ".L", l); sub(/[ \t]+$/, "", l); if (l != "") print l > out }' "$2.s"
 }
 functions_of "$OLD" "$T/old" "$@"
 for f in "${NEW[@]}"; do functions_of "$f" "$T/new" "$@"; done
 bad=0
-for s in $(ls "$T/old" "$T/new" | grep '^_ZN3mrg' | sort -u); do
+for s in $(ls "$T/old" "$T/new" | grep -E '^_ZN(3mrg|12_GLOBAL__N_1)' | sort -u); do
     if [ ! -e "$T/new/$s" ]; then r=MISSING; elif [ ! -e "$T/old/$s" ]; then r=EXTRA
     elif cmp -s "$T/old/$s" "$T/new/$s"; then r=same; else r=DIFFERENT; fi
     [ $r = same ] || bad=1
