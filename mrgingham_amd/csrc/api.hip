@@ -32,6 +32,7 @@ int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes) {
     if (b.p) {
         MRG_HIP_CHECK(hipDeviceSynchronize());
         MRG_HIP_CHECK(hipFree(b.p));
+        ctx->scratch_total -= (long long)b.bytes;
         b.p = nullptr;
         b.bytes = 0;
     }
@@ -40,7 +41,16 @@ int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes) {
     const size_t want = bytes + (bytes < (64u << 20) ? bytes / 8 : 0) + 256;
     MRG_HIP_CHECK(hipMalloc(&b.p, want));
     b.bytes = want;
+    ctx->scratch_total += (long long)want;
     return 0;
+}
+
+void release(mrgingham_amd_ctx* ctx, DevBuf& b) {
+    if (!b.p) return;
+    (void)hipFree(b.p);
+    ctx->scratch_total -= (long long)b.bytes;
+    b.p = nullptr;
+    b.bytes = 0;
 }
 
 // (the step of ensure_pinned, for the one caller that goes on without the memory: ensure_level_set)
@@ -49,7 +59,8 @@ static hipError_t grow_pinned(PinBuf& b, size_t bytes, int slack_divisor, bool z
     if (b.p) {
         const hipError_t e = hipHostFree(b.p);
         if (e != hipSuccess) return e;
-        b = PinBuf();
+        b.p = nullptr;
+        b.bytes = 0;
     }
     const size_t want = bytes + (slack_divisor ? bytes / slack_divisor : 0);
     const hipError_t e = hipHostMalloc(&b.p, want, hipHostMallocDefault);
@@ -160,46 +171,6 @@ int ensure_level_set(mrgingham_amd_ctx* ctx, int set, int level, int nframes, in
     return 0;
 }
 
-// Every device buffer a context owns (one list for destroy and for mrgingham_amd_scratch_bytes).
-static std::vector<DevBuf*> level_set_buffers(mrgingham_amd_ctx* ctx, int set, bool with_points) {
-    std::vector<DevBuf*> v;
-    for (LevelScratch& L : ctx->lvs[set])
-        for (DevBuf* b : {&L.img, &L.resp, &L.gidx, &L.hot_xy, &L.parent, &L.comp_cnt, &L.roots, &L.comp_first, &L.comp_box,
-                          &L.arena, &L.cand, &L.sortkeys})
-            v.push_back(b);
-    if (!with_points) return v;
-    auto& ps = ctx->pts[set];
-    for (DevBuf* b : {&ps.leader, &ps.need, &ps.nseeds, &ps.seeds, &ps.sroot, &ps.cand_xy, &ps.cand_counts, &ps.cell_list, &ps.cell_cnt, &ps.flag_list})
-        v.push_back(b);
-    return v;
-}
-static std::vector<DevBuf*> all_buffers(mrgingham_amd_ctx* ctx) {
-    std::vector<DevBuf*> v;
-    for (int set = 0; set < kMaxSets; ++set) {
-        for (DevBuf* b : level_set_buffers(ctx, set, true)) v.push_back(b);
-        v.push_back(&ctx->counters2[set]);
-    }
-    v.push_back(&ctx->sparse_stat);
-    for (DevBuf* b : {&ctx->mg_pts, &ctx->mg_lv, &ctx->mg_np}) v.push_back(b);
-    for (auto& j : ctx->jobs)
-        for (DevBuf* b : {&j.d_cnt, &j.d_pts, &j.d_pts0}) v.push_back(b);
-    for (DevBuf* b : {&ctx->io_counts, &ctx->aux_img, &ctx->io_frame, &ctx->io_out, &ctx->pre_scratch, &ctx->pre_tmp,
-                      &ctx->pre_out, &ctx->pre16_scratch, &ctx->io_frame16, &ctx->dbg_img, &ctx->dbg_resp, &ctx->blob_scratch, &ctx->blob_nodes, &ctx->blob_out,
-                      &ctx->fb_xy, &ctx->fb_cnt, &ctx->fb_pts, &ctx->fb_lv, &ctx->fb_np, &ctx->fb_frames, &ctx->fb_frames2, &ctx->loader_slot[0].dev, &ctx->loader_slot[1].dev, &ctx->jpeg_huff_dev[0], &ctx->jpeg_huff_dev[1],
-                      &ctx->jpeg_sync_dev[0], &ctx->jpeg_sync_dev[1], &ctx->jpeg_sync_rec[0], &ctx->jpeg_sync_rec[1], &ctx->png_row})
-        v.push_back(b);
-    return v;
-}
-// Every page-locked buffer a context owns (for destroy; mrgingham_amd_scratch_bytes counts device memory only).
-static std::vector<PinBuf*> all_pinned(mrgingham_amd_ctx* ctx) {
-    std::vector<PinBuf*> v{&ctx->io_pin};
-    for (PinBuf& b : ctx->status_pin) v.push_back(&b);
-    for (int k = 0; k < 2; ++k)
-        for (PinBuf* b : {&ctx->loader_slot[k].pin, &ctx->jpeg_huff_pin[k], &ctx->jpeg_sync_pin[k]}) v.push_back(b);
-    for (auto& j : ctx->jobs) v.push_back(&j.pin);
-    return v;
-}
-
 // How many scratch sets (= calls whose component searches may be in flight) this batch shape gets, unless the
 // option "scratch_sets" fixed it: three while three sets of the whole chain's scratch stay below 8 GB (small
 // frames, whose search chain is much longer than their pixel kernels: 64 x 640x480 chains 280 k -> 399 k
@@ -216,11 +187,11 @@ int choose_sets(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr) {
     if (want == ctx->nsets) return 0;
     const int rc = mrgingham_amd_sync(ctx);
     if (want < ctx->nsets)  // the sets that leave the rotation give their scratch back (a larger batch has arrived)
-        for (int set = want; set < ctx->nsets; ++set) {
-            for (DevBuf* b : level_set_buffers(ctx, set, false))  // (the small per-point scratch stays: it is sized for all sets)
-                if (b->p) { hipFree(b->p); *b = DevBuf(); }
-            for (LevelScratch& L : ctx->lvs[set]) { L.nframes = 0; L.w = L.h = 0; L.pitch = 0; }
-        }
+        for (int set = want; set < ctx->nsets; ++set)
+            for (LevelScratch& L : ctx->lvs[set]) {  // (the small per-point scratch stays: it is sized for all sets)
+                L.for_each_buffer([ctx](DevBuf& b) { release(ctx, b); });
+                L.nframes = 0; L.w = L.h = 0; L.pitch = 0;
+            }
     ctx->nsets = want;
     ctx->cur = 0;
     return rc;
@@ -439,19 +410,17 @@ mrgingham_amd_ctx* mrgingham_amd_create(int device_ordinal) {
         uint32_t mask[8] = {}, inv[8];
         for (int b = 0; b < 8 * cc_cus; ++b) mask[b >> 5] |= 1u << (b & 31);
         for (int i = 0; i < 8; ++i) inv[i] = ~mask[i];
-        for (int k = 0; ok && k < kMaxSets; ++k) ok = hipExtStreamCreateWithCUMask(&ctx->ccs[k], 8, mask) == hipSuccess;
+        for (int k = 0; ok && k < kMaxSets; ++k) ok = hipExtStreamCreateWithCUMask(&ctx->ccs[k].h, 8, mask) == hipSuccess;
         ok = ok &&
-             (pix_compl ? hipExtStreamCreateWithCUMask(&ctx->pix, 8, inv)
-                        : hipStreamCreateWithPriority(&ctx->pix, hipStreamNonBlocking, prio_lo)) == hipSuccess;
+             (pix_compl ? hipExtStreamCreateWithCUMask(&ctx->pix.h, 8, inv)
+                        : hipStreamCreateWithPriority(&ctx->pix.h, hipStreamNonBlocking, prio_lo)) == hipSuccess;
     } else {
-        ok = hipStreamCreateWithPriority(&ctx->pix, hipStreamNonBlocking, prio_lo) == hipSuccess;
+        ok = hipStreamCreateWithPriority(&ctx->pix.h, hipStreamNonBlocking, prio_lo) == hipSuccess;
         for (int k = 0; ok && k < kMaxSets; ++k)
-            ok = hipStreamCreateWithPriority(&ctx->ccs[k], hipStreamNonBlocking, prio_hi) == hipSuccess;
+            ok = hipStreamCreateWithPriority(&ctx->ccs[k].h, hipStreamNonBlocking, prio_hi) == hipSuccess;
     }
-    for (int k = 0; ok && k < kMaxSets; ++k)
-        ok = hipEventCreateWithFlags(&ctx->ev_cc_done[k], hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; ok && i <= kMaxLevel; ++i)
-        ok = hipEventCreateWithFlags(&ctx->ev_pix[i], hipEventDisableTiming) == hipSuccess;
+    for (int k = 0; ok && k < kMaxSets; ++k) ok = ctx->ev_cc_done[k].create(hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; ok && i <= kMaxLevel; ++i) ok = ctx->ev_pix[i].create(hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         fprintf(stderr, "mrgingham_amd: could not create HIP streams/events\n");
         mrgingham_amd_destroy(ctx);
@@ -478,36 +447,7 @@ void mrgingham_amd_destroy(mrgingham_amd_ctx* ctx) {
     if (ctx->one) mrgingham_amd_destroy(ctx->one);
     hipSetDevice(ctx->device);
     hipDeviceSynchronize();
-    for (DevBuf* b : all_buffers(ctx))
-        if (b->p) hipFree(b->p);
-    for (auto& pr : ctx->events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    for (auto e : ctx->event_pool) hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_pix)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_cc_done)
-        if (e) hipEventDestroy(e);
-    if (ctx->ev_ext) hipEventDestroy(ctx->ev_ext);
-    for (hipEvent_t e : ctx->blob_ev)
-        if (e) hipEventDestroy(e);
-    for (PinBuf* b : all_pinned(ctx))
-        if (b->p) hipHostFree(b->p);
-    if (ctx->io_res_pin) hipHostFree(ctx->io_res_pin);
-    for (hipEvent_t e : ctx->io_ev)
-        if (e) hipEventDestroy(e);
-    for (auto& slot : ctx->loader_slot)
-        if (slot.ev) hipEventDestroy(slot.ev);
-    if (ctx->mg_done) hipEventDestroy(ctx->mg_done);
-    if (ctx->mg_stream) hipStreamDestroy(ctx->mg_stream);
-    for (auto& j : ctx->jobs) {
-        if (j.ev_a) hipEventDestroy(j.ev_a);
-        if (j.ev_b) hipEventDestroy(j.ev_b);
-        if (j.ev_a0) hipEventDestroy(j.ev_a0);
-        if (j.ev_b0) hipEventDestroy(j.ev_b0);
-    }
-    if (ctx->pix) hipStreamDestroy(ctx->pix);
-    for (hipStream_t c : ctx->ccs)
-        if (c) hipStreamDestroy(c);
-    delete ctx;
+    delete ctx;  // (every buffer, event and stream of the context is a member that frees itself: ctx.h, OWNERS)
 }
 
 int mrgingham_amd_debug_paths(mrgingham_amd_ctx* ctx, int level, int nframes, int32_t* h_paths) {
@@ -538,8 +478,7 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
 
 long long mrgingham_amd_scratch_bytes(const mrgingham_amd_ctx* ctx) {
     if (!ctx) return 0;
-    long long total = 0;
-    for (const DevBuf* b : all_buffers(const_cast<mrgingham_amd_ctx*>(ctx))) total += (long long)b->bytes;
+    long long total = ctx->scratch_total;
     if (ctx->one) total += mrgingham_amd_scratch_bytes(ctx->one);
     return total;
 }
@@ -719,13 +658,14 @@ double mrgingham_amd_chess_kernel_ms(mrgingham_amd_ctx* ctx, int* nlaunches) {
     hipDeviceSynchronize();
     double total = 0.;
     int n = 0;
-    for (auto& pr : ctx->events) {
+    TimingEvents& te = ctx->timing_events;
+    for (auto& pr : te.pairs) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) { total += ms; ++n; }
-        ctx->event_pool.push_back(pr.first);
-        ctx->event_pool.push_back(pr.second);
     }
-    ctx->events.clear();
+    te.pairs.clear();
+    te.idle.clear();  // (nothing is recorded across a read-out: every event is idle again)
+    for (const Event& e : te.all) te.idle.push_back(e);
     if (nlaunches) *nlaunches = n;
     return n ? total / n : 0.;
 }
@@ -759,7 +699,7 @@ int mrgingham_amd_stream_wait(mrgingham_amd_ctx* ctx, void* stream) {
 int mrgingham_amd_after_stream(mrgingham_amd_ctx* ctx, void* stream) {
     if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
     MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->ev_ext) MRG_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_ext, hipEventDisableTiming));
+    MRG_HIP_CHECK(ctx->ev_ext.create(hipEventDisableTiming));
     MRG_HIP_CHECK(hipEventRecord(ctx->ev_ext, (hipStream_t)stream));
     // every kernel of a call is ordered behind the pixel stream's work of that call
     MRG_HIP_CHECK(hipStreamWaitEvent(ctx->pix, ctx->ev_ext, 0));

@@ -747,8 +747,7 @@ int blob_chunk(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int f0, i
     // device time of the chunk's kernels (kernel timing on): events around each of the three stretches of kernels
     const bool timed = ctx->timing;
     if (timed)
-        for (hipEvent_t& e : ctx->blob_ev)
-            if (!e) MRG_HIP_CHECK(hipEventCreate(&e));
+        for (Event& e : ctx->blob_ev) MRG_HIP_CHECK(e.create(hipEventDefault));
     auto kernels_begin = [&] { if (timed) hipEventRecord(ctx->blob_ev[0], s); };
     auto kernels_end = [&] { if (timed) hipEventRecord(ctx->blob_ev[1], s); };
     // the counters back on the host: one copy, one synchronisation

@@ -583,10 +583,7 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
             (rc = ensure(ctx, nj.d_pts0, fb_align((size_t)B * N * 16) + (size_t)B * N)))
             return rc;
         if ((rc = ensure_pinned(ctx, nj.pin, fb_layout(nullptr, nlev, B, cap, N).bytes, 4, false))) return rc;
-        if (!nj.ev_a) MRG_HIP_CHECK(hipEventCreate(&nj.ev_a));
-        if (!nj.ev_b) MRG_HIP_CHECK(hipEventCreate(&nj.ev_b));
-        if (!nj.ev_a0) MRG_HIP_CHECK(hipEventCreate(&nj.ev_a0));
-        if (!nj.ev_b0) MRG_HIP_CHECK(hipEventCreate(&nj.ev_b0));
+        for (Event* e : {&nj.ev_a, &nj.ev_b, &nj.ev_a0, &nj.ev_b0}) MRG_HIP_CHECK(e->create(hipEventDefault));
     }
     begin_op(ctx, top);
     auto& job = ctx->jobs[ctx->cur];

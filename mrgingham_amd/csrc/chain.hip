@@ -10,10 +10,16 @@ namespace mrg {
 // hipEventRecord on the pixel stream is a packet of its own between two kernels (~4 us each in the kernel trace), so
 // a boundary gets ONE: where a level's component search waits for the launch that is timed, the closing mark is that
 // level's hand-over event as well, and a mark that stands between two launches closes nothing and opens the next pair.
-static hipEvent_t timing_event(mrgingham_amd_ctx* ctx) {
-    hipEvent_t e;
-    if (!ctx->event_pool.empty()) { e = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
-    else hipEventCreate(&e);
+hipEvent_t timing_event(mrgingham_amd_ctx* ctx) {
+    TimingEvents& te = ctx->timing_events;
+    if (te.idle.empty()) {
+        Event fresh;
+        if (fresh.create(hipEventDefault) != hipSuccess) return nullptr;
+        te.idle.push_back(fresh);
+        te.all.push_back(std::move(fresh));
+    }
+    const hipEvent_t e = te.idle.back();
+    te.idle.pop_back();
     return e;
 }
 // the opening mark of a pair on `s` when `on` (else NULL): `recorded` if the caller has one on the stream already
@@ -30,7 +36,7 @@ static hipEvent_t timing_open(mrgingham_amd_ctx* ctx, hipStream_t s, bool on, hi
 static hipEvent_t timing_close(mrgingham_amd_ctx* ctx, hipStream_t s, hipEvent_t e0, hipEvent_t handover) {
     hipEvent_t e1 = e0 ? timing_event(ctx) : handover;
     if (e1) hipEventRecord(e1, s);
-    if (e0) ctx->events.emplace_back(e0, e1);
+    if (e0) ctx->timing_events.pairs.emplace_back(e0, e1);
     return e1;
 }
 
@@ -215,7 +221,7 @@ int queue_chess_levels(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, i
                     note_pending(ctx, L, nf);
                 }
             } else if (e0) {
-                ctx->event_pool.push_back(e0);
+                ctx->timing_events.idle.push_back(e0);
             }
         }
     }

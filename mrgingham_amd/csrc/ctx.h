@@ -12,6 +12,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/mrgingham_amd.h"
@@ -23,15 +24,50 @@ namespace mrg {
 
 constexpr int kMaxLevel = 10;  // find_chessboard_corners.cc:433-436
 
+// OWNERS.  What a context holds of the runtime -- device memory, page-locked memory, events, streams -- is a member of one
+// of the four types below and is given back by that member's destructor: nothing lists the members a second time.  All
+// four are move-only, and the raw handle stays readable (p and bytes; an Event or a Stream converts to its handle).
+// device memory, grown on demand (ensure)
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~DevBuf() { if (p) (void)hipFree(p); }
 };
 // page-locked host memory, grown on demand like a DevBuf (ensure_pinned)
 struct PinBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    PinBuf() = default;
+    PinBuf(PinBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    PinBuf& operator=(PinBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
 };
+struct Event {
+    hipEvent_t h = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Event() { if (h) (void)hipEventDestroy(h); }
+    operator hipEvent_t() const { return h; }
+    // created with `flags` on first use
+    hipError_t create(unsigned flags) { return h ? hipSuccess : hipEventCreateWithFlags(&h, flags); }
+};
+// (created in place, by whichever of the runtime's calls the owner wants: hipStreamCreateWithPriority(&s.h, ...))
+struct Stream {
+    hipStream_t h = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Stream& operator=(Stream&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Stream() { if (h) (void)hipStreamDestroy(h); }
+    operator hipStream_t() const { return h; }
+};
+static_assert(!std::is_copy_constructible_v<DevBuf> && !std::is_copy_assignable_v<DevBuf>, "DevBuf owns its memory");
+static_assert(!std::is_copy_constructible_v<PinBuf> && !std::is_copy_assignable_v<PinBuf>, "PinBuf owns its memory");
+static_assert(!std::is_copy_constructible_v<Event> && !std::is_copy_assignable_v<Event>, "Event owns its handle");
+static_assert(!std::is_copy_constructible_v<Stream> && !std::is_copy_assignable_v<Stream>, "Stream owns its handle");
 
 // Scratch of one pyramid level: level images, the dense response and the
 // component tables.  Levels have their own scratch because the pixel kernels of
@@ -40,6 +76,20 @@ struct LevelScratch {
     int w = 0, h = 0, nframes = 0, cap = 0, cand_cap = 0, sort_cap = 0, pitch = 0, shift = -1;
     long long arena_cap = 0;
     DevBuf img, resp, gidx, hot_xy, parent, comp_cnt, roots, comp_first, comp_box, arena, cand, sortkeys;
+    // (for choose_sets, which hands the scratch of a set that leaves the rotation back)
+    template <class F>
+    void for_each_buffer(F&& f) {
+        for (DevBuf* b : {&img, &resp, &gidx, &hot_xy, &parent, &comp_cnt, &roots, &comp_first, &comp_box, &arena, &cand, &sortkeys}) f(*b);
+    }
+};
+
+// Kernel timing (chain.hip, KERNEL TIMING): every timing event the context has ever created, the pairs recorded since
+// mrgingham_amd_chess_kernel_ms last read them, and the events that are in no pair.  The read-out puts every event back
+// among the idle ones, so an event that was taken but never got into a pair (an error in between) is not lost.
+struct TimingEvents {
+    std::vector<Event> all;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;
+    std::vector<hipEvent_t> idle;
 };
 
 }  // namespace mrg
@@ -133,21 +183,21 @@ struct mrgingham_amd_ctx {
     // over the whole batch; `ccs[set]` run the latency-bound component kernels (a serial chain
     // detect -> refine -> refine ... per call) underneath them, one stream per scratch set so that
     // the chains of consecutive calls overlap each other as well.  Events order cc(L) after pix(L).
-    hipStream_t pix = nullptr;
-    hipStream_t ccs[kMaxSets] = {};
+    mrg::Stream pix;
+    mrg::Stream ccs[kMaxSets];
     // Device buffers the last call of each set wrote / read (caller-owned outputs and inputs):
     // consecutive calls run on different component streams, so a call that touches a buffer the
     // previous call wrote (or writes one it read) must wait for it explicitly.
     struct Span { const char* p; size_t n; };
     std::vector<Span> last_w[kMaxSets], last_r[kMaxSets];
-    hipEvent_t ev_pix[mrg::kMaxLevel + 1] = {};
+    mrg::Event ev_pix[mrg::kMaxLevel + 1];
     // Level scratch exists `nsets` times (2, or 3 with option "scratch_sets"): call N+1 fills set (N+1) % nsets on
     // the pixel stream while the component streams still work through the calls before it in the other sets.
     // Two sets keep two component chains in flight, which hides them as long as a chain is shorter than two
     // steps of the pixel kernels; small frames (64 x 640x480: chain 430 us, pixel kernels 62 us) and dense boards
     // want three.
-    hipEvent_t ev_cc_done[kMaxSets] = {};
-    hipEvent_t ev_ext = nullptr;  // mrgingham_amd_after_stream
+    mrg::Event ev_cc_done[kMaxSets];
+    mrg::Event ev_ext;  // mrgingham_amd_after_stream
     bool cc_pending[kMaxSets] = {};
     int cur = 0;  // scratch set of the call being queued
     std::string err;
@@ -193,26 +243,29 @@ struct mrgingham_amd_ctx {
     int cc_schedule = 1;
     int cc_lds = 1;  // component search out of LDS for frames with few hot pixels (option "cc_lds"; bits 1-3: timing ablations)
 
+    // device bytes of this context's scratch (mrgingham_amd_scratch_bytes), kept by ensure and release: atomic, because a
+    // shard of mrgingham_amd_chain_multi grows its context's scratch on the submit thread
+    std::atomic<long long> scratch_total{0};
     mrg::LevelScratch lvs[kMaxSets][mrg::kMaxLevel + 1];
     mrg::DevBuf counters2[kMaxSets];  // per scratch set: hot_cnt words [level][counters_nf], then status words, then path words
     int counters_nf = 0;
     struct PointScratch { mrg::DevBuf leader, need, nseeds, seeds, sroot, cand_xy, cand_counts, cell_list, cell_cnt, flag_list; } pts[kMaxSets];  // per scratch set
     mrg::DevBuf aux_img, io_frame, io_out, io_counts;
-    void* io_res_pin = nullptr;  // page-locked: count + first candidates of the single-frame detector
+    mrg::PinBuf io_res_pin;  // page-locked: count + first candidates of the single-frame detector
     // page-locked copies of the sets' status words ([level][counters_nf], what mrgingham_amd_sync inspects): they follow every
     // op on its component stream (end_op), so that the sync behind it reads host memory instead of making a blocking copy;
     // allocated with counters2 (ensure_level_set): status_pin.bytes is what counters_nf implies, or 0 where that failed
     mrg::PinBuf status_pin[kMaxSets];
     bool status_copied[kMaxSets] = {};  // the LAST op on the set left its words in status_pin
     mrg::PinBuf io_pin;  // page-locked staging of mrgingham_ChESS_response_5's way back
-    hipEvent_t io_ev[4] = {};
+    mrg::Event io_ev[4];
     mrg::DevBuf clk;  // two u64: shader cycles and constant-rate ticks of the probed workgroups (mrgingham_amd_sclk_mhz)
     mrg::DevBuf pre_scratch, pre_tmp, pre_out, pre16_scratch, io_frame16, dbg_img, dbg_resp, blob_scratch, blob_nodes, blob_out;
     // blob detector (blobs.hip): a batch is worked through in chunks of frames whose plane scratch (blob_scratch) stays
     // within the budget; option "blob_chunk_frames" (test hook): at most that many frames per chunk, 0 = by budget
     size_t blob_plane_budget = (size_t)1 << 30;
     int blob_chunk_frames = 0;
-    hipEvent_t blob_ev[2] = {};  // around a chunk's kernels while kernel timing is on
+    mrg::Event blob_ev[2];  // around a chunk's kernels while kernel timing is on
     double blob_stat[8] = {};    // mrgingham_amd_blobs_stats (+ [7]: frames)
     // The two chunk slots of the file loaders (loader.hip: loader_ring): two chunks of files in flight, one being decoded
     // into its page-locked staging while the other uploads into its device image and runs its kernels; `ev` follows the
@@ -225,7 +278,7 @@ struct mrgingham_amd_ctx {
     struct LoaderSlot {
         mrg::DevBuf dev;
         mrg::PinBuf pin;
-        hipEvent_t ev = nullptr;
+        mrg::Event ev;
     } loader_slot[2];
     size_t jpeg_coef_budget = (size_t)1 << 30;  // both device buffers together, for either loader
     int jpeg_chunk_frames = 0;
@@ -272,8 +325,8 @@ struct mrgingham_amd_ctx {
         signed char* h_found = nullptr;
         signed char* h_levels = nullptr;  // optional: the refinement level of every corner, [frame][gridn^2]
         bool do_refine = true;
-        hipEvent_t ev_a = nullptr, ev_b = nullptr;
-        hipEvent_t ev_a0 = nullptr, ev_b0 = nullptr;  // where the two device parts begin (mrgingham_amd_find_boards_stats)
+        mrg::Event ev_a, ev_b;
+        mrg::Event ev_a0, ev_b0;  // where the two device parts begin (mrgingham_amd_find_boards_stats)
         bool refine_queued = false;
         int top = 0;  // the highest level a board of the job was found at (levels below it are refined)
         // device images of the pinned staging, laid out like it (fb_layout) so that each direction is ONE copy:
@@ -291,8 +344,8 @@ struct mrgingham_amd_ctx {
     } jobs[kMaxSets];
     // mrgingham_amd_chain_multi: this context's shard of the outputs before it travels to the first context's device
     mrg::DevBuf mg_pts, mg_lv, mg_np;
-    hipStream_t mg_stream = nullptr;
-    hipEvent_t mg_done = nullptr;
+    mrg::Stream mg_stream;
+    mrg::Event mg_done;
     bool mg_pending = false;
     int next_ticket = 0;
     std::vector<std::pair<int, int>> done_tickets;  // (ticket, status) of jobs completed before they were collected
@@ -312,8 +365,7 @@ struct mrgingham_amd_ctx {
     // dominant-kernel timing
     bool timing = false;
     bool clk_on = false;  // the engine-clock probe of the level-0 response launches (mrgingham_amd_sclk_mhz)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    std::vector<hipEvent_t> event_pool;
+    mrg::TimingEvents timing_events;
     std::vector<int32_t> host_status;
     std::vector<char> io_host_block;  // refine_on_device: the points block as it travels
 };
@@ -336,7 +388,9 @@ constexpr int kCellsPerPoint = 9;  // sparse refinement: distinct cells the 3 x 
 
 // api.hip: errors, buffers, level scratch
 int fail(mrgingham_amd_ctx* ctx, int code, const char* fmt, ...);
+// at least `bytes` of device memory: the only place that allocates context scratch (and counts it)
 int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes);
+void release(mrgingham_amd_ctx* ctx, DevBuf& b);  // gives it back now
 // at least `bytes` of page-locked memory; growth allocates bytes + bytes / slack_divisor (0: no slack), zeroed if asked
 int ensure_pinned(mrgingham_amd_ctx* ctx, PinBuf& b, size_t bytes, int slack_divisor, bool zero_on_growth);
 hipError_t copy_rows_async(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows,
@@ -353,6 +407,8 @@ int harvest_status(mrgingham_amd_ctx* ctx, int set, int level, int* rc, bool qui
 void launch_one_level_image(const mrgingham_amd_frames* fr, int level, uint8_t* out, int w, int h, hipStream_t s);
 
 // chain.hip: the scratch-set rotation of a call, its pixel-stream and component-stream work
+// an idle timing event, or a new one (NULL if it cannot be created); it stays the context's (TimingEvents)
+hipEvent_t timing_event(mrgingham_amd_ctx* ctx);
 void begin_op(mrgingham_amd_ctx* ctx, int max_level);
 void order_after_previous(mrgingham_amd_ctx* ctx, std::initializer_list<mrgingham_amd_ctx::Span> w,
                           std::initializer_list<mrgingham_amd_ctx::Span> r);

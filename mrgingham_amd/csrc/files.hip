@@ -46,9 +46,9 @@ struct Chunk {
 };
 
 struct Slot {
-    uint8_t *d_raw = nullptr, *d_pre = nullptr;
-    uint8_t* pin = nullptr;         // page-locked staging of the host-decoded files
-    hipEvent_t ev_up = nullptr;     // behind the uploads of the chunk in the slot (loader context's pix stream)
+    DevBuf d_raw, d_pre;            // (the slot's own, freed with it: in no context's scratch_bytes)
+    PinBuf pin;                     // page-locked staging of the host-decoded files
+    Event ev_up;                    // behind the uploads of the chunk in the slot (loader context's pix stream)
     bool uploaded = false;          // ... recorded for that chunk
     std::vector<int32_t> load_status;  // per slot of the chunk: 0 loaded, -1 the decoder rejected the file
     std::vector<double> boards;
@@ -98,6 +98,7 @@ int load_chunk(Run& R, int c) {
     const int n = (int)ch.files.size();
     const size_t pitch = frame_pitch_of(ch.w, ch.h), npx = (size_t)ch.w * ch.h;
     hipStream_t s = ctx->pix;
+    uint8_t *const d_raw = (uint8_t*)S.d_raw.p, *const pin = (uint8_t*)S.pin.p;
     S.load_status.assign((size_t)n, -1);
     if (S.uploaded) MRG_HIP_CHECK(hipEventSynchronize(S.ev_up));  // (long done: the chunk that recorded it has been collected)
     S.uploaded = false;
@@ -109,17 +110,17 @@ int load_chunk(Run& R, int c) {
         for_files<Image>(ctx->pool, R.nthreads, (int)host.size(), [&](int i, Image& im) {
             const int k = host[(size_t)i];
             if (read_image(R.names[ch.files[(size_t)k]], im) && im.depth == 8 && im.w == ch.w && im.h == ch.h) {
-                memcpy(S.pin + (size_t)k * pitch, im.px8.data(), npx);
+                memcpy(pin + (size_t)k * pitch, im.px8.data(), npx);
                 S.load_status[(size_t)k] = 0;
             } else {
-                memset(S.pin + (size_t)k * pitch, 0, npx);  // (the frame is detected on with its chunk; its result is dropped)
+                memset(pin + (size_t)k * pitch, 0, npx);  // (the frame is detected on with its chunk; its result is dropped)
             }
         });
         for (size_t i = 0; i < host.size();) {
             size_t j = i + 1;
             while (j < host.size() && host[j] == host[j - 1] + 1) ++j;
             const size_t k0 = (size_t)host[i], bytes = (j - i) * pitch;
-            MRG_HIP_CHECK(hipMemcpyAsync(S.d_raw + k0 * pitch, S.pin + k0 * pitch, bytes, hipMemcpyHostToDevice, s));
+            MRG_HIP_CHECK(hipMemcpyAsync(d_raw + k0 * pitch, pin + k0 * pitch, bytes, hipMemcpyHostToDevice, s));
             i = j;
         }
         MRG_HIP_CHECK(hipEventRecord(S.ev_up, s));
@@ -139,9 +140,9 @@ int load_chunk(Run& R, int c) {
         while (j < n && route(j) == via) ++j;
         std::vector<const char*> run;
         for (int i = k; i < j; ++i) run.push_back(R.names[ch.files[(size_t)i]]);
-        const int rc = via == 1 ? mrgingham_amd_read_jpegs_batch(ctx, run.data(), j - k, ch.w, ch.h, S.d_raw + (size_t)k * pitch, (int64_t)pitch,
+        const int rc = via == 1 ? mrgingham_amd_read_jpegs_batch(ctx, run.data(), j - k, ch.w, ch.h, d_raw + (size_t)k * pitch, (int64_t)pitch,
                                                                  ch.w, R.nthreads, S.load_status.data() + k)
-                                : mrgingham_amd_read_pngs_batch(ctx, run.data(), j - k, ch.w, ch.h, 8, S.d_raw + (size_t)k * pitch, (int64_t)pitch,
+                                : mrgingham_amd_read_pngs_batch(ctx, run.data(), j - k, ch.w, ch.h, 8, d_raw + (size_t)k * pitch, (int64_t)pitch,
                                                                 ch.w, R.nthreads, S.load_status.data() + k);
         if (rc) return rc;
         for (int i = k; i < j; ++i) {
@@ -294,14 +295,7 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
         if (loader_thread.joinable()) loader_thread.join();
         if (R.detector) mrgingham_amd_destroy(R.detector);  // (abandons what is in flight, synchronises the device)
         if (R.loader) mrgingham_amd_destroy(R.loader);
-        hipSetDevice(device);
-        for (Slot& S : R.slots) {
-            if (S.d_raw) hipFree(S.d_raw);
-            if (S.d_pre) hipFree(S.d_pre);
-            if (S.pin) hipHostFree(S.pin);
-            if (S.ev_up) hipEventDestroy(S.ev_up);
-        }
-    };
+    };  // (the slots free themselves when R goes, after the contexts)
     auto setup = [&]() -> int {
         if (nchunks == 0) return 0;
         R.detector = mrgingham_amd_create(device);
@@ -315,11 +309,11 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
         const size_t bytes = (size_t)R.batch * max_frame;
         for (int k = 0; k < nslots; ++k) {
             Slot& S = R.slots[k];
-            if (hipMalloc((void**)&S.d_raw, bytes) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
-            if (preprocess && hipMalloc((void**)&S.d_pre, bytes) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
-            if (max_host_frame && hipHostMalloc((void**)&S.pin, (size_t)R.batch * max_host_frame, hipHostMallocDefault) != hipSuccess)
+            if (hipMalloc(&S.d_raw.p, bytes) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
+            if (preprocess && hipMalloc(&S.d_pre.p, bytes) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
+            if (max_host_frame && hipHostMalloc(&S.pin.p, (size_t)R.batch * max_host_frame, hipHostMallocDefault) != hipSuccess)
                 return MRGINGHAM_AMD_ERR_DEVICE;
-            if (hipEventCreateWithFlags(&S.ev_up, hipEventDisableTiming) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
+            if (S.ev_up.create(hipEventDisableTiming) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
             S.boards.resize((size_t)R.batch * N * 2);
             S.levels.resize((size_t)R.batch * N);
             S.found.resize((size_t)R.batch);
@@ -426,12 +420,12 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
         mrgingham_amd_ctx* ctx = R.detector;
         MRG_HIP_CHECK(hipSetDevice(device));
         if (S.uploaded) MRG_HIP_CHECK(hipStreamWaitEvent(ctx->pix, S.ev_up, 0));
-        mrgingham_amd_frames fr{S.d_raw, (int64_t)pitch, n, ch.w, ch.h, ch.w};
+        mrgingham_amd_frames fr{(uint8_t*)S.d_raw.p, (int64_t)pitch, n, ch.w, ch.h, ch.w};
         int r = 0;
         if (preprocess) {
             // on the pixel stream, like the one-image path: the detector's pixel kernels follow it there
-            r = mrgingham_amd_preprocess_batch(ctx, &fr, o->do_clahe, o->blur_radius, S.d_pre, ctx->pix);
-            fr.frames = S.d_pre;
+            r = mrgingham_amd_preprocess_batch(ctx, &fr, o->do_clahe, o->blur_radius, (uint8_t*)S.d_pre.p, ctx->pix);
+            fr.frames = (uint8_t*)S.d_pre.p;
         }
         int ticket = -1;
         if (!r) {

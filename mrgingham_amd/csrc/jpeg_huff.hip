@@ -224,10 +224,8 @@ int queue_huff(mrgingham_amd_ctx* ctx, int k, const Layout& l, const FileJob* jo
         // kernel timing on: a pair of events around the launches, read by mrgingham_amd_chess_kernel_ms like the response's
         hipEvent_t mark[2] = {nullptr, nullptr};
         if (ctx->timing) {
-            for (hipEvent_t& e : mark) {
-                if (!ctx->event_pool.empty()) { e = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
-                else MRG_HIP_CHECK(hipEventCreate(&e));
-            }
+            for (hipEvent_t& e : mark)
+                if (!(e = timing_event(ctx))) MRG_HIP_CHECK(hipGetLastError());  // (what kept it from being created)
             MRG_HIP_CHECK(hipEventRecord(mark[0], s));
         }
         for (int f0 = 0; f0 < n; f0 += 65535) {
@@ -242,7 +240,7 @@ int queue_huff(mrgingham_amd_ctx* ctx, int k, const Layout& l, const FileJob* jo
         MRG_HIP_CHECK(hipGetLastError());
         if (mark[0]) {
             MRG_HIP_CHECK(hipEventRecord(mark[1], s));
-            ctx->events.emplace_back(mark[0], mark[1]);
+            ctx->timing_events.pairs.emplace_back(mark[0], mark[1]);
         }
         MRG_HIP_CHECK(hipMemcpyAsync(pin + l.status, dev + l.status, l.total - l.status, hipMemcpyDeviceToHost, s));
     }

@@ -324,10 +324,8 @@ int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int
     // rounds, the scan or the write pass alone), read by mrgingham_amd_chess_kernel_ms like the response's
     hipEvent_t mark[2] = {nullptr, nullptr};
     if (ctx->timing)
-        for (hipEvent_t& e : mark) {
-            if (!ctx->event_pool.empty()) { e = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
-            else MRG_HIP_CHECK(hipEventCreate(&e));
-        }
+        for (hipEvent_t& e : mark)
+            if (!(e = timing_event(ctx))) MRG_HIP_CHECK(hipGetLastError());  // (what kept it from being created)
     const int phase = ctx->jpeg_sync_time_phase;
     auto tick = [&](int boundary) -> hipError_t {  // boundary q lies between phase q and phase q + 1 (1 .. 4)
         if (!mark[0]) return hipSuccess;
@@ -358,7 +356,7 @@ int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int
                            (long long)coef_pitch);
     MRG_HIP_CHECK(hipGetLastError());
     MRG_HIP_CHECK(tick(4));
-    if (mark[0]) ctx->events.emplace_back(mark[0], mark[1]);
+    if (mark[0]) ctx->timing_events.pairs.emplace_back(mark[0], mark[1]);
     MRG_HIP_CHECK(hipMemcpyAsync(pin + ch.words, words, (size_t)n * sizeof(SyncWords), hipMemcpyDeviceToHost, s));
     return 0;
 }

@@ -31,7 +31,7 @@ int loader_ring(mrgingham_amd_ctx* ctx, int nfiles, int chunk, size_t dev_bytes,
         auto& slot = ctx->loader_slot[k];
         if ((rc = ensure(ctx, slot.dev, dev_bytes))) return rc;
         if (pin_bytes && (rc = ensure_pinned(ctx, slot.pin, pin_bytes, 0, true))) return rc;
-        if (!slot.ev) MRG_HIP_CHECK(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
+        MRG_HIP_CHECK(slot.ev.create(hipEventDisableTiming));
     }
     hipStream_t s = ctx->pix;
     bool busy[2] = {false, false};

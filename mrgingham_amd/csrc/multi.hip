@@ -31,8 +31,8 @@ static int chain_multi_shard(mrgingham_amd_ctx* ctx, int root_device, const mrgi
     }
     MRG_HIP_CHECK(hipSetDevice(ctx->device));
     if (!ctx->mg_stream) {
-        MRG_HIP_CHECK(hipStreamCreateWithFlags(&ctx->mg_stream, hipStreamNonBlocking));
-        MRG_HIP_CHECK(hipEventCreateWithFlags(&ctx->mg_done, hipEventDisableTiming));
+        MRG_HIP_CHECK(hipStreamCreateWithFlags(&ctx->mg_stream.h, hipStreamNonBlocking));
+        MRG_HIP_CHECK(ctx->mg_done.create(hipEventDisableTiming));
         int can = 0;  // direct peer copies where the link allows them (otherwise HIP stages through the host)
         if (hipDeviceCanAccessPeer(&can, ctx->device, root_device) == hipSuccess && can) {
             hipError_t e = hipDeviceEnablePeerAccess(root_device, 0);

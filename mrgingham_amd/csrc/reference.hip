@@ -142,11 +142,8 @@ bool detect_one_frame_all(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr
         // of a 0.4 ms call).  A frame whose tables overflowed says so in its count (-1): only then the status words are
         // read, the tables grow and the call is made again.
         constexpr int kFast = 4000;  // candidates that travel with the count
-        if (!ctx->io_res_pin && hipHostMalloc(&ctx->io_res_pin, 64 + (size_t)kFast * 8, hipHostMallocDefault) != hipSuccess) {
-            ctx->io_res_pin = nullptr;
-            break;
-        }
-        int32_t* pin_count = (int32_t*)ctx->io_res_pin;
+        if (ensure_pinned(ctx, ctx->io_res_pin, 64 + (size_t)kFast * 8, 0, false)) break;
+        int32_t* pin_count = (int32_t*)ctx->io_res_pin.p;
         int32_t* pin_xy = pin_count + 16;
         hipStream_t cc = ctx->ccs[ctx->cur];
         const int nfast = cap < kFast ? cap : kFast;
@@ -421,7 +418,7 @@ void mrgingham_ChESS_response_5(int16_t* response, const uint8_t* image, int w, 
         const int kChunks = small ? 1 : 4;
         (void)ensure_pinned(ctx, ctx->io_pin, bytes, 8, false);  // (without it: the message below)
         for (int c = 0; c < kChunks; ++c)
-            if (!ctx->io_ev[c]) hipEventCreateWithFlags(&ctx->io_ev[c], hipEventDisableTiming);
+            (void)ctx->io_ev[c].create(hipEventDisableTiming);
         if (!ctx->io_pin.p || !ctx->io_ev[kChunks - 1]) {
             fprintf(stderr, "mrgingham_amd: ChESS response failed: no page-locked staging\n");
             return;
@@ -439,7 +436,7 @@ void mrgingham_ChESS_response_5(int16_t* response, const uint8_t* image, int w, 
             std::atomic<int> failed{0};
             const int16_t* pin = (const int16_t*)ctx->io_pin.p;
             const int device = ctx->device;
-            hipEvent_t* evs = ctx->io_ev;
+            const Event* evs = ctx->io_ev;
             constexpr int kBlock = 32;  // rows per work item
             const int nblocks = (h - 2 * kMargin + kBlock - 1) / kBlock;
             auto mover = [&]() {
