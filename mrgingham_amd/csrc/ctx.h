@@ -283,8 +283,7 @@ struct mrgingham_amd_ctx {
     size_t jpeg_coef_budget = (size_t)1 << 30;  // both device buffers together, for either loader
     int jpeg_chunk_frames = 0;
     // the device entropy path of the loader and mrgingham_amd_jpeg_entropy_batch (jpeg_huff.hip): per chunk slot one
-    // staging image (frame records | tables | interval records | compressed bytes | one status byte per interval),
-    // page-locked on the host and mirrored on the device, both grown on demand.  Options "jpeg_entropy" (0: host threads
+    // staging image (jpeg_stage.h has the layout), page-locked on the host and mirrored on the device, both grown on demand.  Options "jpeg_entropy" (0: host threads
     // decode, 1: the device where the file has restart intervals), "jpeg_entropy_max_interval" (MCUs one lane may be
     // handed), "jpeg_entropy_memset" (0: lanes write whole blocks, 1: the area is zeroed in front and lanes store non-zeros)
     mrg::DevBuf jpeg_huff_dev[2];
@@ -293,8 +292,7 @@ struct mrgingham_amd_ctx {
     int jpeg_entropy_max_interval = 1024;
     int jpeg_entropy_memset = 0;
     // files without restart intervals on the device (jpeg_huff_sync.hip): per chunk slot a staging image of their own
-    // (frame records | tables | compressed bytes || the per-file words that come back) and the device-only records of the
-    // subsequences.  Options "jpeg_sync" (0: such files keep the host decoder), "jpeg_sync_subsequence" (bytes per lane),
+    // (jpeg_stage.h) and the device-only records of the subsequences.  Options "jpeg_sync" (0: such files keep the host decoder), "jpeg_sync_subsequence" (bytes per lane),
     // "jpeg_sync_max_rounds" (0: 8192 / jpeg_sync_subsequence), "jpeg_sync_time_phase" (tools: what kernel timing brackets)
     mrg::DevBuf jpeg_sync_dev[2], jpeg_sync_rec[2];
     mrg::PinBuf jpeg_sync_pin[2];
@@ -409,6 +407,20 @@ void launch_one_level_image(const mrgingham_amd_frames* fr, int level, uint8_t* 
 // chain.hip: the scratch-set rotation of a call, its pixel-stream and component-stream work
 // an idle timing event, or a new one (NULL if it cannot be created); it stays the context's (TimingEvents)
 hipEvent_t timing_event(mrgingham_amd_ctx* ctx);
+// Kernel timing around the launches of the JPEG entropy decoders (jpeg_huff.hip): the caller numbers the boundaries
+// between its launches and calls tick at each; with timing on, the pair of events opens at boundary `open` and closes --
+// and is handed to mrgingham_amd_chess_kernel_ms -- at `close`.  An event that cannot be created is an error.
+struct TimingBracket {
+    hipEvent_t mark[2] = {nullptr, nullptr};
+    int open = 0, close = 0;
+    hipError_t begin(mrgingham_amd_ctx* ctx, int open_at, int close_at);
+    hipError_t tick(mrgingham_amd_ctx* ctx, int boundary, hipStream_t s);
+};
+// launch(f0, n) over slabs of at most 65535 frames (a grid's y and z extents)
+template <class F>
+void for_frame_slabs(int nframes, F&& launch) {
+    for (int f0 = 0; f0 < nframes; f0 += 65535) launch(f0, (unsigned)(nframes - f0 < 65535 ? nframes - f0 : 65535));
+}
 void begin_op(mrgingham_amd_ctx* ctx, int max_level);
 void order_after_previous(mrgingham_amd_ctx* ctx, std::initializer_list<mrgingham_amd_ctx::Span> w,
                           std::initializer_list<mrgingham_amd_ctx::Span> r);
@@ -437,6 +449,8 @@ int blob_detect_batch(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, in
 int host_threads(int nthreads);
 
 // jpeg_idct.hip
+// a coefficient area of blocks_w x blocks_h blocks per frame for width x height pixels: 0, or MRGINGHAM_AMD_ERR_ARG
+int check_coef_area(mrgingham_amd_ctx* ctx, const int16_t* d_coef, int64_t coef_pitch, int width, int height, int blocks_w, int blocks_h);
 void launch_jpeg_idct(const int16_t* d_coef, int64_t coef_pitch, const uint16_t* d_quant, int nframes, int width, int height,
                       int blocks_w, uint8_t* d_out, int64_t frame_pitch, int stride, hipStream_t s);
 
@@ -447,6 +461,9 @@ int check_file_batch(mrgingham_amd_ctx* ctx, const char* format, const char* con
                      size_t elem, const void* d_out, int64_t frame_pitch, int stride, const int32_t* h_status);
 // zeroes width x height samples of `elem` bytes of frame `frame` (of a file that failed)
 hipError_t zero_frame(void* d_out, int64_t frame, int64_t frame_pitch, int stride, int width, int height, size_t elem, hipStream_t s);
+// the `after` of a loader whose frames are bytes: zeroes the frames of the chunk's files whose h_status is not 0
+std::function<int(int k, int f0, int n)> zero_failed_frames(mrgingham_amd_ctx* ctx, uint8_t* d_out, int64_t frame_pitch, int stride,
+                                                            int width, int height, const int32_t* h_status);
 // The two-slot chunk ring on ctx->pix: chunks of `chunk` files alternate between the slots (one slot if there is one
 // chunk), whose device buffers are grown to dev_bytes and whose staging to pin_bytes (0: the stage grows it when it
 // needs it).  Per chunk: wait for the event of the slot's previous chunk and, given `finish`, finish(k) behind it; then
@@ -461,36 +478,18 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
                               uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status, int bw, int bh,
                               int chunk);
 
-// jpeg_huff_sync.hip: files without restart intervals (option "jpeg_sync"), for the two callers in jpeg_huff.hip
-struct JpegScan;
-struct JpegSyncFile {
-    const uint8_t* data = nullptr;  // the file
-    const JpegScan* scan = nullptr;
-    uint32_t len = 0;  // of its entropy-coded segment (jpeg_sync_plan)
-    int frame = 0;     // which coefficient area of the chunk it decodes into
-    // laid out by jpeg_sync_lay_out
-    int ntables = 0;
-    uint32_t nsub = 0;
-    size_t table_off = 0, rec_first = 0, stream_off = 0;
-};
-struct JpegSyncChunk {
-    std::vector<JpegSyncFile> files;
-    size_t tables = 0, streams = 0, words = 0, total = 0, nrecords = 0, d_spec = 0;
-    uint32_t most = 0;  // subsequences of the longest file
-};
-// does the sync path take this scanned file (option on, no restart intervals, a stream a 32-bit bit offset spans)?
-bool jpeg_sync_plan(const mrgingham_amd_ctx* ctx, const uint8_t* data, size_t nbytes, const JpegScan& sc, uint32_t* len);
-int jpeg_sync_max_rounds(const mrgingham_amd_ctx* ctx);
-// ch->files (data, scan, len, frame) -> where everything lies; grows slot k's buffers
-int jpeg_sync_lay_out(mrgingham_amd_ctx* ctx, int k, JpegSyncChunk* ch);
-// writes file i of the chunk into slot k's staging image (any thread, one per file)
-void jpeg_sync_fill(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int i, int blocks_h, int pitch_blocks);
-// queues the upload, the zeroing of the files' coefficient areas, round 0, the update rounds, the scan, the write pass and
-// the download of the per-file words
-int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int16_t* d_coef, int64_t coef_pitch, size_t area_elems,
-                     hipStream_t s);
-// after the stream has passed the download: 0 decoded, -1 unreadable, -3 not converged within the cap
-int32_t jpeg_sync_status(const mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int i, int* rounds);
+// jpeg_huff_sync.hip: files without restart intervals (option "jpeg_sync"), for the chunk driver in jpeg_huff.hip; the
+// files of a chunk and the layout of their staging image are jpeg_stage.h
+struct JpegStageFile;
+struct JpegSyncLayout;
+// grows slot k's buffers to what the layout asks for (nothing for a chunk without sync files)
+int jpeg_sync_grow(mrgingham_amd_ctx* ctx, int k, const JpegSyncLayout& l);
+// queues the upload of slot k's filled image, the zeroing of the sync files' coefficient areas (file i of the chunk at
+// d_coef + i * coef_pitch), round 0, the update rounds, the scan, the write pass and the download of the per-file words
+int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncLayout& l, const JpegStageFile* files, int nfiles, int16_t* d_coef,
+                     int64_t coef_pitch, size_t area_elems, hipStream_t s);
+// after the stream has passed the download, sync file i: 0 decoded, -1 unreadable, -3 not converged within the cap
+int32_t jpeg_sync_status(const mrgingham_amd_ctx* ctx, int k, const JpegSyncLayout& l, int i);
 
 // boards.hip
 struct GridScratch { std::vector<PointI> cand; std::vector<PointD> grid; };

@@ -4,15 +4,16 @@
 // decoder, DESIGN.md section 4.10 the method and the measured figures, include/mrgingham_amd.h the options "jpeg_sync",
 // "jpeg_sync_subsequence" and "jpeg_sync_max_rounds".  Four kernels, all plain launches that the stream orders: round 0,
 // R + 1 update rounds (a file that has converged costs its workgroups one load), the scan, the write pass.  No kernel
-// waits for another workgroup.
+// waits for another workgroup.  The staging image the kernels read is built by jpeg_stage.h; here are the kernels and what
+// grows the buffers, queues a filled image and reads the per-file words.
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "ctx.h"
-#include "jpeg.h"
 #include "jpeg_huff_sync.h"
+#include "jpeg_stage.h"
 
 using namespace mrg;
 
@@ -20,25 +21,6 @@ namespace {
 
 constexpr int kLanes = 256;
 constexpr int kTableDwords = (int)(sizeof(JpegHuffTable) / 4);
-
-// One file of a chunk, as the kernels see it (80 bytes).  Offsets are bytes into the chunk's staging image.
-struct SyncFrame {
-    uint64_t stream_off;  // its entropy-coded bytes (a multiple of 4; padded so that whole dwords can be read)
-    uint32_t table_off;   // its ntables tables, JpegHuffTable each
-    uint32_t rec_first;   // index of its first record
-    uint32_t nsub, len, total, ntables;
-    uint32_t frame;       // which coefficient area of the chunk is its own
-    uint32_t unused[3];
-    JpegLaneGeom geom;
-};
-static_assert(sizeof(SyncFrame) == 80, "SyncFrame is laid out by hand in the staging image");
-
-// What the kernels keep per file (zeroed in front of round 0, read back behind the write pass).
-struct SyncWords {
-    uint32_t last_changed;  // the last update round (1 ..) that changed one of its records
-    uint32_t flags;         // kReached / kError from the write pass, kScanReached / kNotConverged from the scan
-};
-constexpr uint32_t kReached = 1, kError = 2, kScanReached = 4, kNotConverged = 8;
 
 __constant__ uint8_t kNaturalSync[64] = {MRG_JPEG_NATURAL_ORDER};
 
@@ -235,135 +217,70 @@ __global__ __launch_bounds__(kLanes) void jpeg_sync_write_kernel(const uint8_t* 
 
 namespace mrg {
 
-bool jpeg_sync_plan(const mrgingham_amd_ctx* ctx, const uint8_t* data, size_t nbytes, const JpegScan& sc, uint32_t* len) {
-    if (!ctx->jpeg_sync || sc.restart_interval) return false;
-    const size_t end = jpeg_segment_end(data, nbytes, sc.entropy_begin);
-    if (end - sc.entropy_begin >= kJpegSyncMaxStream) return false;  // (an empty segment is taken: unreadable, as on the host)
-    *len = (uint32_t)(end - sc.entropy_begin);
-    return true;
-}
-
-int jpeg_sync_max_rounds(const mrgingham_amd_ctx* ctx) {
-    return ctx->jpeg_sync_max_rounds > 0 ? ctx->jpeg_sync_max_rounds : 8192 / ctx->jpeg_sync_subsequence;
-}
-
-int jpeg_sync_lay_out(mrgingham_amd_ctx* ctx, int k, JpegSyncChunk* ch) {
-    const uint32_t S = (uint32_t)ctx->jpeg_sync_subsequence;
-    const size_t n = ch->files.size();
-    ch->tables = n * sizeof(SyncFrame);
-    size_t ntab = 0, nstream = 0;
-    ch->nrecords = 0;
-    ch->most = 0;
-    for (JpegSyncFile& j : ch->files) {
-        const JpegHuffTable* named[kJpegLaneTables] = {};
-        JpegLaneGeom g;
-        jpeg_lane_setup(*j.scan, named, &j.ntables, &g, 1, 1);
-        j.table_off = ch->tables + ntab * sizeof(JpegHuffTable);
-        j.nsub = (j.len + S - 1) / S;
-        j.rec_first = ch->nrecords;
-        j.stream_off = nstream;  // (from ch->streams, added below)
-        ntab += (size_t)j.ntables;
-        ch->nrecords += j.nsub;
-        ch->most = std::max(ch->most, j.nsub);
-        nstream += (((size_t)j.len + 3) & ~(size_t)3) + 4;
-    }
-    ch->streams = ch->tables + ntab * sizeof(JpegHuffTable);
-    for (JpegSyncFile& j : ch->files) j.stream_off += ch->streams;
-    ch->words = ch->streams + nstream;  // (on the host: where the words come back to)
-    ch->total = ch->words + n * sizeof(SyncWords);
-    if (ch->nrecords >= ((size_t)1 << 31)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "too many JPEG subsequences in one chunk");
+int jpeg_sync_grow(mrgingham_amd_ctx* ctx, int k, const JpegSyncLayout& l) {
+    if (l.nfiles == 0) return 0;
+    if (l.nitems >= ((size_t)1 << 31)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "too many JPEG subsequences in one chunk");
     int rc;
-    if ((rc = ensure_pinned(ctx, ctx->jpeg_sync_pin[k], ch->total, 4, false))) return rc;
-    if ((rc = ensure(ctx, ctx->jpeg_sync_dev[k], ch->words))) return rc;
-    // device only: words | spec | two record buffers | starts
-    const size_t recs = ch->nrecords * sizeof(JpegSyncRecord);
-    ch->d_spec = (n * sizeof(SyncWords) + 31) & ~(size_t)31;
-    return ensure(ctx, ctx->jpeg_sync_rec[k], ch->d_spec + 3 * recs + ch->nrecords * sizeof(JpegSyncStart));
+    if ((rc = ensure_pinned(ctx, ctx->jpeg_sync_pin[k], l.total, 4, false))) return rc;
+    if ((rc = ensure(ctx, ctx->jpeg_sync_dev[k], l.back))) return rc;
+    return ensure(ctx, ctx->jpeg_sync_rec[k], l.d_bytes);
 }
 
-void jpeg_sync_fill(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int i, int blocks_h, int pitch_blocks) {
-    char* image = (char*)ctx->jpeg_sync_pin[k].p;
-    const JpegSyncFile& j = ch.files[(size_t)i];
-    const JpegScan& sc = *j.scan;
-    SyncFrame fr;
-    memset(&fr, 0, sizeof(fr));
-    const JpegHuffTable* named[kJpegLaneTables] = {};
-    int ntables = 0;
-    jpeg_lane_setup(sc, named, &ntables, &fr.geom, blocks_h, pitch_blocks);
-    fr.stream_off = j.stream_off;
-    fr.table_off = (uint32_t)j.table_off;
-    fr.rec_first = (uint32_t)j.rec_first;
-    fr.nsub = j.nsub;
-    fr.len = j.len;
-    fr.total = (uint32_t)(sc.mcus_x * sc.mcus_y * sc.blocks_per_mcu);
-    fr.ntables = (uint32_t)ntables;
-    fr.frame = (uint32_t)j.frame;
-    memcpy(image + (size_t)i * sizeof(SyncFrame), &fr, sizeof(fr));
-    for (int s = 0; s < ntables; ++s) memcpy(image + j.table_off + (size_t)s * sizeof(JpegHuffTable), named[s], sizeof(JpegHuffTable));
-    memcpy(image + j.stream_off, j.data + sc.entropy_begin, j.len);
-    memset(image + j.stream_off + j.len, 0, ((((size_t)j.len + 3) & ~(size_t)3) + 4) - j.len);
-}
-
-int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int16_t* d_coef, int64_t coef_pitch, size_t area_elems,
-                     hipStream_t s) {
-    const int n = (int)ch.files.size();
+int jpeg_sync_launch(mrgingham_amd_ctx* ctx, int k, const JpegSyncLayout& l, const JpegStageFile* files, int nfiles, int16_t* d_coef,
+                     int64_t coef_pitch, size_t area_elems, hipStream_t s) {
+    const int n = l.nfiles;
     if (n == 0) return 0;
     char* pin = (char*)ctx->jpeg_sync_pin[k].p;
     char* dev = (char*)ctx->jpeg_sync_dev[k].p;
     char* scratch = (char*)ctx->jpeg_sync_rec[k].p;
-    const uint32_t S = (uint32_t)ctx->jpeg_sync_subsequence, R = (uint32_t)jpeg_sync_max_rounds(ctx);
+    const uint32_t S = (uint32_t)ctx->jpeg_sync_subsequence;
+    const uint32_t R = (uint32_t)(ctx->jpeg_sync_max_rounds > 0 ? ctx->jpeg_sync_max_rounds : 8192 / ctx->jpeg_sync_subsequence);
     SyncWords* words = (SyncWords*)scratch;
-    JpegSyncRecord* spec = (JpegSyncRecord*)(scratch + ch.d_spec);
-    JpegSyncRecord* buf[2] = {spec + ch.nrecords, spec + 2 * ch.nrecords};
-    JpegSyncStart* start = (JpegSyncStart*)(spec + 3 * ch.nrecords);
-    MRG_HIP_CHECK(hipMemcpyAsync(dev, pin, ch.words, hipMemcpyHostToDevice, s));
+    JpegSyncRecord* spec = (JpegSyncRecord*)(scratch + l.d_spec);
+    JpegSyncRecord* buf[2] = {spec + l.nitems, spec + 2 * l.nitems};
+    JpegSyncStart* start = (JpegSyncStart*)(spec + 3 * l.nitems);
+    MRG_HIP_CHECK(hipMemcpyAsync(dev, pin, l.back, hipMemcpyHostToDevice, s));
     MRG_HIP_CHECK(hipMemsetAsync(words, 0, (size_t)n * sizeof(SyncWords), s));
-    for (const JpegSyncFile& j : ch.files)  // the lanes store non-zero coefficients only
-        MRG_HIP_CHECK(hipMemsetAsync(d_coef + (size_t)j.frame * (size_t)coef_pitch, 0, area_elems * sizeof(int16_t), s));
-    // kernel timing on: a pair of events around the launches (option "jpeg_sync_time_phase": around round 0, the update
-    // rounds, the scan or the write pass alone), read by mrgingham_amd_chess_kernel_ms like the response's
-    hipEvent_t mark[2] = {nullptr, nullptr};
-    if (ctx->timing)
-        for (hipEvent_t& e : mark)
-            if (!(e = timing_event(ctx))) MRG_HIP_CHECK(hipGetLastError());  // (what kept it from being created)
+    for (int i = 0; i < nfiles; ++i)  // the lanes store non-zero coefficients only
+        if (files[i].route == JpegRoute::kSync)
+            MRG_HIP_CHECK(hipMemsetAsync(d_coef + (size_t)i * (size_t)coef_pitch, 0, area_elems * sizeof(int16_t), s));
+    // kernel timing: boundary q lies between phase q and phase q + 1 of round 0, the update rounds, the scan, the write
+    // pass; option "jpeg_sync_time_phase" brackets one of them alone
     const int phase = ctx->jpeg_sync_time_phase;
-    auto tick = [&](int boundary) -> hipError_t {  // boundary q lies between phase q and phase q + 1 (1 .. 4)
-        if (!mark[0]) return hipSuccess;
-        if (boundary == (phase ? phase - 1 : 0)) return hipEventRecord(mark[0], s);
-        if (boundary == (phase ? phase : 4)) return hipEventRecord(mark[1], s);
-        return hipSuccess;
-    };
-    MRG_HIP_CHECK(tick(0));
-    const unsigned groups = std::max(1u, (unsigned)((ch.most + kLanes - 1) / kLanes));  // (a file may have no subsequence at all)
+    TimingBracket mark;
+    MRG_HIP_CHECK(mark.begin(ctx, phase ? phase - 1 : 0, phase ? phase : 4));
+    MRG_HIP_CHECK(mark.tick(ctx, 0, s));
+    const unsigned groups = std::max(1u, (unsigned)((l.most_items + kLanes - 1) / kLanes));  // (a file may have no subsequence at all)
     const uint8_t* image = (const uint8_t*)dev;
     const SyncFrame* frames = (const SyncFrame*)dev;
-    for (int f0 = 0; f0 < n; f0 += 65535)
-        hipLaunchKernelGGL(jpeg_sync_spec_kernel, dim3(groups, (unsigned)std::min(n - f0, 65535)), dim3(kLanes), 0, s, image, frames, f0, S,
-                           spec, buf[0]);
-    MRG_HIP_CHECK(tick(1));
+    for_frame_slabs(n, [&](int f0, unsigned nf) {
+        hipLaunchKernelGGL(jpeg_sync_spec_kernel, dim3(groups, nf), dim3(kLanes), 0, s, image, frames, f0, S, spec, buf[0]);
+    });
+    MRG_HIP_CHECK(mark.tick(ctx, 1, s));
     for (uint32_t t = 1; t <= R + 1; ++t)
-        for (int f0 = 0; f0 < n; f0 += 65535)
-            hipLaunchKernelGGL(jpeg_sync_round_kernel, dim3(groups, (unsigned)std::min(n - f0, 65535)), dim3(kLanes), 0, s, image, frames, f0,
-                               S, t, words, (const JpegSyncRecord*)spec, (const JpegSyncRecord*)buf[(t - 1) & 1], buf[t & 1]);
-    MRG_HIP_CHECK(tick(2));
-    for (int f0 = 0; f0 < n; f0 += 65535)
-        hipLaunchKernelGGL(jpeg_sync_scan_kernel, dim3((unsigned)std::min(n - f0, 65535)), dim3(kLanes), 0, s, frames, f0, R, words,
-                           (const JpegSyncRecord*)buf[0], (const JpegSyncRecord*)buf[1], start);
-    MRG_HIP_CHECK(tick(3));
-    for (int f0 = 0; f0 < n; f0 += 65535)
-        hipLaunchKernelGGL(jpeg_sync_write_kernel, dim3(groups, (unsigned)std::min(n - f0, 65535)), dim3(kLanes), 0, s, image, frames, f0, S,
-                           words, (const JpegSyncRecord*)buf[0], (const JpegSyncRecord*)buf[1], (const JpegSyncStart*)start, d_coef,
+        for_frame_slabs(n, [&](int f0, unsigned nf) {
+            hipLaunchKernelGGL(jpeg_sync_round_kernel, dim3(groups, nf), dim3(kLanes), 0, s, image, frames, f0, S, t, words,
+                               (const JpegSyncRecord*)spec, (const JpegSyncRecord*)buf[(t - 1) & 1], buf[t & 1]);
+        });
+    MRG_HIP_CHECK(mark.tick(ctx, 2, s));
+    for_frame_slabs(n, [&](int f0, unsigned nf) {
+        hipLaunchKernelGGL(jpeg_sync_scan_kernel, dim3(nf), dim3(kLanes), 0, s, frames, f0, R, words, (const JpegSyncRecord*)buf[0],
+                           (const JpegSyncRecord*)buf[1], start);
+    });
+    MRG_HIP_CHECK(mark.tick(ctx, 3, s));
+    for_frame_slabs(n, [&](int f0, unsigned nf) {
+        hipLaunchKernelGGL(jpeg_sync_write_kernel, dim3(groups, nf), dim3(kLanes), 0, s, image, frames, f0, S, words,
+                           (const JpegSyncRecord*)buf[0], (const JpegSyncRecord*)buf[1], (const JpegSyncStart*)start, d_coef,
                            (long long)coef_pitch);
+    });
     MRG_HIP_CHECK(hipGetLastError());
-    MRG_HIP_CHECK(tick(4));
-    if (mark[0]) ctx->timing_events.pairs.emplace_back(mark[0], mark[1]);
-    MRG_HIP_CHECK(hipMemcpyAsync(pin + ch.words, words, (size_t)n * sizeof(SyncWords), hipMemcpyDeviceToHost, s));
+    MRG_HIP_CHECK(mark.tick(ctx, 4, s));
+    MRG_HIP_CHECK(hipMemcpyAsync(pin + l.back, words, (size_t)n * sizeof(SyncWords), hipMemcpyDeviceToHost, s));
     return 0;
 }
 
-int32_t jpeg_sync_status(const mrgingham_amd_ctx* ctx, int k, const JpegSyncChunk& ch, int i, int* rounds) {
-    const SyncWords w = ((const SyncWords*)((const char*)ctx->jpeg_sync_pin[k].p + ch.words))[i];
-    if (rounds) *rounds = (int)w.last_changed;
+int32_t jpeg_sync_status(const mrgingham_amd_ctx* ctx, int k, const JpegSyncLayout& l, int i) {
+    const SyncWords w = ((const SyncWords*)((const char*)ctx->jpeg_sync_pin[k].p + l.back))[i];
     if (w.flags & kNotConverged) return -3;
     return (w.flags & kScanReached) && (w.flags & kReached) && !(w.flags & kError) ? 0 : -1;
 }

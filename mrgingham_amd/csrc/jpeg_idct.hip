@@ -93,6 +93,14 @@ int check_idct_args(mrgingham_amd_ctx* ctx, const int16_t* d_coef, int64_t coef_
     if (nframes < 0 || width < 0 || height < 0 || blocks_w < 0 || blocks_h < 0 || stride < width || frame_pitch < 0 || coef_pitch < 0 ||
         (nframes > 0 && (!d_coef || !d_quant || !d_out)))
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad JPEG coefficient batch descriptor");
+    return check_coef_area(ctx, d_coef, coef_pitch, width, height, blocks_w, blocks_h);
+}
+
+}  // namespace
+
+namespace mrg {
+
+int check_coef_area(mrgingham_amd_ctx* ctx, const int16_t* d_coef, int64_t coef_pitch, int width, int height, int blocks_w, int blocks_h) {
     if (width > 32767 || height > 32767)
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "frames larger than 32767 pixels per side are not supported");
     // (an MCU is at most 32 pixels wide and high: 4100 blocks cover the padding of the largest frame)
@@ -103,19 +111,14 @@ int check_idct_args(mrgingham_amd_ctx* ctx, const int16_t* d_coef, int64_t coef_
     return 0;
 }
 
-}  // namespace
-
-namespace mrg {
-
 void launch_jpeg_idct(const int16_t* d_coef, int64_t coef_pitch, const uint16_t* d_quant, int nframes, int width, int height,
                       int blocks_w, uint8_t* d_out, int64_t frame_pitch, int stride, hipStream_t s) {
     const int bw = (width + 7) / 8, bh = (height + 7) / 8;
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {
-        const int n = nframes - f0 < 65535 ? nframes - f0 : 65535;
-        const dim3 grid((unsigned)((bw + kBlocksPerGroup - 1) / kBlocksPerGroup), (unsigned)bh, (unsigned)n);
+    for_frame_slabs(nframes, [&](int f0, unsigned n) {
+        const dim3 grid((unsigned)((bw + kBlocksPerGroup - 1) / kBlocksPerGroup), (unsigned)bh, n);
         hipLaunchKernelGGL(jpeg_idct_kernel, grid, dim3(256), 0, s, d_coef, (long long)coef_pitch, d_quant, f0, width, height,
                            blocks_w, d_out, (long long)frame_pitch, stride);
-    }
+    });
 }
 
 }  // namespace mrg
@@ -206,12 +209,8 @@ int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
         MRG_HIP_CHECK(hipGetLastError());
         return 0;
     };
-    auto zero_failed = [&](int, int f0, int n) -> int {  // failed files: zeros afterwards
-        for (int i = f0; i < f0 + n; ++i)
-            if (h_status[i] != 0) MRG_HIP_CHECK(zero_frame(d_out, i, frame_pitch, stride, width, height, 1, s));
-        return 0;
-    };
-    return loader_ring(ctx, nfiles, chunk, slot_bytes, slot_bytes, stage, zero_failed, nullptr);
+    return loader_ring(ctx, nfiles, chunk, slot_bytes, slot_bytes, stage,
+                       zero_failed_frames(ctx, d_out, frame_pitch, stride, width, height, h_status), nullptr);  // failed files: zeros afterwards
 }
 
 }  // extern "C"

@@ -23,6 +23,15 @@ hipError_t zero_frame(void* d_out, int64_t frame, int64_t frame_pitch, int strid
                             (size_t)height, s);
 }
 
+LoaderStage zero_failed_frames(mrgingham_amd_ctx* ctx, uint8_t* d_out, int64_t frame_pitch, int stride, int width, int height,
+                               const int32_t* h_status) {
+    return [=](int, int f0, int n) -> int {
+        for (int i = f0; i < f0 + n; ++i)
+            if (h_status[i] != 0) MRG_HIP_CHECK(zero_frame(d_out, i, frame_pitch, stride, width, height, 1, ctx->pix));
+        return 0;
+    };
+}
+
 int loader_ring(mrgingham_amd_ctx* ctx, int nfiles, int chunk, size_t dev_bytes, size_t pin_bytes, const LoaderStage& stage,
                 const LoaderStage& after, const std::function<int(int k)>& finish) {
     const int nslots = nfiles > chunk ? 2 : 1;

@@ -158,15 +158,15 @@ def test_scan_c_boundary():
     assert L.mrgingham_amd_jpeg_restart_intervals(bad, len(bad), None, None, 0, None) == -1        # out of sequence
 
 
-def _sanitized_lane_program(tmp_path):
+def _sanitized_lane_program(tmp_path, name="jpeg_lane"):
     probe = tmp_path / "probe.cpp"
     probe.write_text("int main() { return 0; }\n")
     flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
     r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
     if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
         pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "jpeg_lane")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "jpeg_lane_main.cpp"),
+    exe = str(tmp_path / name)
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", name + "_main.cpp"),
                         os.path.join(CSRC, "jpeg.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     return exe
@@ -217,3 +217,27 @@ def test_corrupted_intervals_are_accepted_exactly_when_the_host_accepts_under_sa
     assert 0.30 <= pooled.mean() <= 0.80
     assert not host[kinds == "rst_removed"].any() and not host[kinds == "rst_exchanged"].any()
     assert (kinds == "rst_removed").sum() >= 12 and (kinds == "eoi_planted").sum() >= 12
+
+
+def test_staging_images_of_the_device_decoders_under_sanitizers(tmp_path):
+    """csrc/jpeg_stage.h (plan, lay out, fill) over all 16 restart fixtures and every fixture without restart intervals,
+    chunked by size, and one mixed chunk: tests/boundary/jpeg_stage_main.cpp lists what it requires of every chunk."""
+    from test_jpeg_sync import nodri_cases
+    exe = _sanitized_lane_program(tmp_path, "jpeg_stage")
+    nodri = nodri_cases()
+    assert len(rst_cases()) == 16 and len(nodri) >= 30
+    mixed = [rst_case("rows_48x64_420"), rst_case("nodri_48x64"), test_jpeg_io.case("progressive_48x64"), test_jpeg_io.case("noise_16x16_444")]
+    items = [c.data for c in rst_cases() + nodri + mixed]
+    blob = tmp_path / "corpus.bin"
+    with open(blob, "wb") as f:
+        f.write(struct.pack("<I", len(items)))
+        for data in items:
+            f.write(struct.pack("<I", len(data)) + data)
+    r = subprocess.run([exe, str(blob)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout, r.stderr[-4000:])
+    lines = r.stdout.splitlines()
+    assert lines[0] == "mixed 0 -3 -1 -2" and lines[1] == "mixed_off -3 -3 -1 -2", r.stdout
+    with_dri = sum(not c.name.endswith("_dri0") for c in rst_cases())
+    words = lines[2].split()
+    assert words[:2] == ["cases", str(16 + len(nodri) + 4)] and words[2] == "chunks" and int(words[3]) >= 10, r.stdout
+    assert words[4:] == ["intervals", str(with_dri), "sync", str(16 - with_dri + len(nodri))], r.stdout
