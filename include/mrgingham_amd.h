@@ -54,7 +54,10 @@ extern "C" {
  *      and what it hands to the component search).
  *      Later, additive: mrgingham_amd_png_scanlines, _png_reconstruct_batch, _png_reconstruct_geometry, _read_pngs_batch (PNG:
  *      inflate on the host, row filters and grey on the device); option "png_chunk_frames"; mrgingham_amd_find_boards_files_ex
- *      (loader flags: MRGINGHAM_AMD_FILES_PNG_DEVICE).  Off unless asked for: every earlier call behaves as before. */
+ *      (loader flags: MRGINGHAM_AMD_FILES_PNG_DEVICE).  Off unless asked for: every earlier call behaves as before.
+ *      Later, additive (the version stays 4: new symbols and a new flag value break no caller): mrgingham_amd_pgm_header,
+ *      _pgm_unpack_batch, _read_pgms_batch (binary PGM payloads to frames on the device); option "pgm_chunk_frames"; loader
+ *      flag MRGINGHAM_AMD_FILES_DEEP_CHUNKS (16-bit PGM / PNG files in chunks).  Off unless asked for. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -492,6 +495,40 @@ int mrgingham_amd_read_pngs_batch(mrgingham_amd_ctx* ctx, const char* const* fil
                                   int bits, void* d_out, int64_t frame_pitch, int stride, int nthreads,
                                   int32_t* h_status);
 
+/* Binary PGM (P5).  The header of a file held in memory, whole or only its first nbytes (host only): the one parser behind
+ * mrgingham_amd_read_image, _probe_image and _read_pgms_batch.  0: "P5", three decimal numbers separated by white space
+ * and # comments, one byte after the last; sides 1 .. 32767, maxval 1 .. 65535; *bits 8 (maxval < 256) or 16,
+ * *payload_offset the byte the samples begin at.  -1: not such a file, or a rule broken.  -2: the bytes end inside the
+ * header (of a whole file: unreadable; of a file's first bytes: more are needed).  A file is readable when it holds
+ * width*height*bits/8 bytes from *payload_offset on.  Any output pointer may be NULL. */
+int mrgingham_amd_pgm_header(const uint8_t* data, size_t nbytes, int* width, int* height, int* bits, size_t* payload_offset);
+
+/* PGM payloads to frames on the device: frame f's payload as it lies in the file -- width*height bytes for bits 8,
+ * width*height BIG-ENDIAN pairs for bits 16 -- at d_payload + f*payload_pitch (BYTES; d_payload 16-byte aligned,
+ * payload_pitch a multiple of 16 and >= width*height*bits/8).  d_out as for mrgingham_amd_png_reconstruct_batch: uint8_t
+ * or native-endian uint16_t frames, frame f row y at d_out + f*frame_pitch + y*stride, ELEMENTS; only the width x height
+ * samples are written, what lies between width and stride stays untouched.  d_out may be d_payload itself where the two
+ * layouts coincide (stride == width, frame_pitch*bits/8 == payload_pitch): every sample is then read and written by the
+ * same lane.  A streaming kernel, 16-byte loads, one byte permute per dword, 16-byte stores between a row's head and
+ * tail; the launch is sized to the device.  Asynchronous on `stream` (NULL = default); allocates nothing.  Arguments are
+ * checked like mrgingham_amd_png_reconstruct_batch's (MRGINGHAM_AMD_ERR_ARG, nothing written). */
+int mrgingham_amd_pgm_unpack_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_payload, int64_t payload_pitch, int nframes,
+                                   int width, int height, int bits, void* d_out, int64_t frame_pitch, int stride,
+                                   void* stream);
+
+/* nfiles binary PGM files of ONE size and depth straight into device frames (layout and element type as d_out above):
+ * per file a host thread (nthreads of them; <= 0: all cores, at most 32) parses the header and reads the payload from the
+ * file straight into page-locked staging, at a 16-byte aligned offset -- no byte is swapped or copied a second time on the
+ * host --; a chunk of files goes up in one copy and through one launch of mrgingham_amd_pgm_unpack_batch while the host
+ * threads read the next.  h_status[f]: 0 loaded, -1 unreadable or not a PGM by mrgingham_amd_read_image's rules (a file
+ * shorter than its header promises included), -2 a PGM of another size or depth; the frame of a failed file is
+ * zero-filled.  SYNCHRONOUS: d_out is complete on return.  Returns MRGINGHAM_AMD_OK also when files failed.  Completes the
+ * find_boards jobs in flight first and restores the caller's HIP device.  The chunk buffers are those of
+ * mrgingham_amd_read_jpegs_batch, within the same 1 GiB (12 MP at 16 bit: ~20 files each; option "pgm_chunk_frames"). */
+int mrgingham_amd_read_pgms_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
+                                  int bits, void* d_out, int64_t frame_pitch, int stride, int nthreads,
+                                  int32_t* h_status);
+
 /* The same preprocessing for one HOST image (out: dense width x height bytes, host): what the Python
  * recipe of find_board.docstring:8-10 does with cv2 before find_board.  Uses the calling thread's
  * context.  Returns 0, or -2 on an argument or device error. */
@@ -600,7 +637,8 @@ int mrgingham_amd_files_plan(const int32_t* key, int nfiles, int batch_frames, i
  * collected; nothing synchronises the device in the steady state.  Restores the caller's current HIP device.
  * Routing by mrgingham_amd_probe_image: 8-bit files of one size share chunks (mrgingham_amd_files_plan, key = size) --
  * JPEG files through mrgingham_amd_read_jpegs_batch straight into the chunk's frames, PGM / PNG files decoded by the
- * loader's host threads into page-locked staging and uploaded; 16-bit files, and sizes the batch entry points refuse
+ * loader's host threads into page-locked staging and uploaded; 16-bit files (unless mrgingham_amd_find_boards_files_ex is
+ * given MRGINGHAM_AMD_FILES_DEEP_CHUNKS), and sizes the batch entry points refuse
  * while the one-image path takes them (CLAHE below 8 x 8 pixels), go one at a time through the one-image path on the
  * CALLING THREAD's context (mrgingham_amd_thread_device), when the prefix of final files reaches them.  A file the
  * probe rejects, or accepts and the decoder then rejects, has status -1.
@@ -623,8 +661,8 @@ typedef struct mrgingham_amd_files_options {
     int device;       /* -1: the device of the calling thread's context (mrgingham_amd_thread_device) */
 } mrgingham_amd_files_options;
 #define MRGINGHAM_AMD_FILES_CHUNKS 0           /* chunks that went through the ring */
-#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch */
-#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (PGM / PNG) */
+#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch (PNG_DEVICE) / _read_pgms_batch (DEEP_CHUNKS: 16-bit PGM) */
+#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (8-bit PGM / PNG; 16-bit PNG with DEEP_CHUNKS alone) */
 #define MRGINGHAM_AMD_FILES_ONE_IMAGE 3        /* files through the one-image path */
 #define MRGINGHAM_AMD_FILES_UNREADABLE 4       /* files with status -1 ([1] + [2] + [3] + [4] = nfiles) */
 #define MRGINGHAM_AMD_FILES_DETECTOR_WAIT_MS 5 /* wall ms the calling thread waited for a loaded chunk: the loader bounds the run */
@@ -637,8 +675,18 @@ int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, co
 /* mrgingham_amd_find_boards_files with loader flags (0: exactly that call).  MRGINGHAM_AMD_FILES_PNG_DEVICE: runs of
  * consecutive 8-bit PNG slots of a chunk go through mrgingham_amd_read_pngs_batch on the loader context, like the JPEG
  * runs -- the host threads only inflate -- and are counted under MRGINGHAM_AMD_FILES_DEVICE_LOADED; palette files keep
- * the host decoder (and MRGINGHAM_AMD_FILES_HOST_DECODED), 16-bit files the one-image path.  Same outputs. */
+ * the host decoder (and MRGINGHAM_AMD_FILES_HOST_DECODED), 16-bit files the one-image path.  Same outputs.
+ * MRGINGHAM_AMD_FILES_DEEP_CHUNKS: 16-bit PGM and PNG files of one size share chunks of their own (key = size and depth: a
+ * chunk holds one size AND one depth; CLAHE below 8 x 8 pixels keeps the one-image path) instead of going one at a time
+ * through the calling thread.  PGM slots go through mrgingham_amd_read_pgms_batch (MRGINGHAM_AMD_FILES_DEVICE_LOADED); PNG
+ * slots through mrgingham_amd_read_pngs_batch if PNG_DEVICE is set as well (DEVICE_LOADED), else through the host decoder
+ * on the loader's host threads and an upload of native uint16 samples (HOST_DECODED).  The calling thread runs
+ * mrgingham_amd_preprocess16_batch on every such chunk (always: it is what makes the 8-bit frames), then
+ * mrgingham_amd_find_boards_submit_ex.  The ring buffers are sized in BYTES of the largest batched frame: a 16-bit chunk
+ * holds half the frames of an 8-bit one under the same 1 GiB.  Same outputs.  The flags may be combined; any other bit
+ * is MRGINGHAM_AMD_ERR_ARG. */
 #define MRGINGHAM_AMD_FILES_PNG_DEVICE 1
+#define MRGINGHAM_AMD_FILES_DEEP_CHUNKS 2
 int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
                                        double* h_boards, signed char* h_levels, signed char* h_found_level,
                                        int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
@@ -794,6 +842,7 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *   "jpeg_chunk_frames"   test hook: 0 (default) = mrgingham_amd_read_jpegs_batch cuts its files into chunks by its scratch
  *                         budget; n > 0 = at most n files per chunk.  Results never depend on it.
  *   "png_chunk_frames"    test hook: the same for mrgingham_amd_read_pngs_batch.
+ *   "pgm_chunk_frames"    test hook: the same for mrgingham_amd_read_pgms_batch.
  *   "jpeg_entropy"        0 (default): mrgingham_amd_read_jpegs_batch entropy-decodes on its host threads; 1: files with
  *                         restart intervals are Huffman-decoded on the device, one lane per interval.  Same frames and statuses.
  *   "jpeg_entropy_max_interval"  MCUs per restart interval the device accepts (default 1024, at least 1; files above it go

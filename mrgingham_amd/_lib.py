@@ -55,6 +55,7 @@ EXPORTS = [
     "mrgingham_amd_find_boards_files", "mrgingham_amd_debug_pixel_stage", "mrgingham_amd_debug_pixel_products",
     "mrgingham_amd_png_scanlines", "mrgingham_amd_png_reconstruct_batch", "mrgingham_amd_png_reconstruct_geometry",
     "mrgingham_amd_read_pngs_batch", "mrgingham_amd_find_boards_files_ex",
+    "mrgingham_amd_pgm_header", "mrgingham_amd_pgm_unpack_batch", "mrgingham_amd_read_pgms_batch",
 ]
 
 
@@ -159,6 +160,12 @@ def lib():
                                                     ctypes.c_int64, c_int, c_int, c_vp]
         L.mrgingham_amd_find_boards_files_ex.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
                                                          c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
+    if hasattr(L, "mrgingham_amd_pgm_unpack_batch"):
+        L.mrgingham_amd_pgm_header.argtypes = [c_vp, ctypes.c_size_t] + [ctypes.POINTER(c_int)] * 3 + [ctypes.POINTER(ctypes.c_size_t)]
+        L.mrgingham_amd_pgm_unpack_batch.argtypes = [c_vp, c_vp, ctypes.c_int64, c_int, c_int, c_int, c_int, c_vp, ctypes.c_int64, c_int,
+                                                     c_vp]
+        L.mrgingham_amd_read_pgms_batch.argtypes = [c_vp, ctypes.POINTER(ctypes.c_char_p), c_int, c_int, c_int, c_int, c_vp,
+                                                    ctypes.c_int64, c_int, c_int, c_vp]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]
     L.mrgingham_amd_host_alloc.argtypes = [ctypes.c_size_t]

@@ -216,6 +216,24 @@ def png_scanlines_size(data):
     return h.value, w.value, b.value, ct.value
 
 
+PGM_HEADER_CUT = -2   # pgm_header: the bytes end inside the header
+
+
+def pgm_header(data):
+    """The header of a binary PGM held in memory, whole or only its first bytes (mrgingham_amd_pgm_header; host only):
+    (height, width, bits, payload_offset) -- the file is readable when it holds height*width*bits/8 bytes from
+    payload_offset on --, None for what is not a PGM or breaks a rule, PGM_HEADER_CUT where the bytes end inside the
+    header (of a whole file: unreadable; of a file's first bytes: more are needed)."""
+    buf = bytes(data)
+    w, h, b, off = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    rc = _lib.lib().mrgingham_amd_pgm_header(buf, len(buf), ctypes.byref(w), ctypes.byref(h), ctypes.byref(b), ctypes.byref(off))
+    if rc == PGM_HEADER_CUT:
+        return PGM_HEADER_CUT
+    if rc != 0:
+        return None
+    return h.value, w.value, b.value, off.value
+
+
 def png_reconstruct_geometry():
     """(rows_in_flight, segment_pixels) of the PNG reconstruction kernel's schedule (mrgingham_amd_png_reconstruct_geometry)."""
     r, s = ctypes.c_int(), ctypes.c_int()
@@ -270,7 +288,7 @@ FILES_STATS = ("chunks", "files_device_loader", "files_host_decoded", "files_one
 
 
 def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_radius=1, refine=True, batch=64, nthreads=0,
-                      entropy="host", device=None, progress=None, png="host"):
+                      entropy="host", device=None, progress=None, png="host", deep="one"):
     """A list of image files (binary PGM, PNG, baseline JPEG; any sizes) to boards (mrgingham_amd_find_boards_files): a
     loader thread fills chunks of `batch` equally-sized frames on the device -- JPEG through the batch loader,
     entropy="device": Huffman-decoded on the device as well -- while the calling thread preprocesses and searches the
@@ -281,11 +299,16 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
     with non-decreasing values of nfinal and the arrays the call is going to return: their entries [0, nfinal) are final,
     the last call passes n.  device None: the calling thread's device.  png="device": the runs of 8-bit PNG files of a chunk
     go through the PNG batch loader (Detector.read_pngs: the host threads only inflate) and count as files_device_loader;
-    same numbers."""
+    same numbers.  deep="one": 16-bit files go one at a time through the one-image path on this thread; deep="chunks":
+    16-bit PGM and PNG files of one size share chunks of their own -- PGM through Detector.read_pgms (files_device_loader),
+    PNG through the PNG batch loader with png="device", else decoded on the loader's host threads (files_host_decoded) --
+    and are preprocessed at 16 bit a chunk at a time; same numbers."""
     if entropy not in ("host", "device"):
         raise ValueError('find_boards_files: entropy is "host" or "device"')
     if png not in ("host", "device"):
         raise ValueError('find_boards_files: png is "host" or "device"')
+    if deep not in ("one", "chunks"):
+        raise ValueError('find_boards_files: deep is "one" or "chunks"')
     _require_device()
     L = _lib.lib()
     names = [os.fsencode(p) for p in paths]
@@ -308,7 +331,8 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
     cb = _lib.PROGRESS_F(on_progress)
     arr = (ctypes.c_char_p * max(n, 1))(*names)
     rc = L.mrgingham_amd_find_boards_files_ex(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
-                                              status.ctypes.data, cb, None, stats.ctypes.data, len(stats), int(png == "device"))
+                                              status.ctypes.data, cb, None, stats.ctypes.data, len(stats),
+                                              int(png == "device") | 2 * int(deep == "chunks"))
     if raised:
         raise raised[0]
     if rc == -1:
@@ -966,6 +990,67 @@ class Detector:
         arr = (ctypes.c_char_p * B)(*names)
         t.cuda.current_stream(self.device).synchronize()
         self._check(self.L.mrgingham_amd_read_pngs_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
+                                                         status.ctypes.data))
+        return frames, status
+
+    def pgm_unpack(self, payload, height, width, bits, out=None):
+        """The payloads of binary PGM files to frames on the device (mrgingham_amd_pgm_unpack_batch), on torch's current
+        stream: payload uint8 [B, P] device tensor, contiguous and 16-byte aligned, P a multiple of 16 and at least
+        height*width*bits/8 -- row f holds file f's samples as they lie behind its header, bytes (bits 8) or big-endian
+        pairs (bits 16) -> uint8 or uint16 [B, height, width].  `out`: a [B, height, >= width] device tensor of that type
+        (unit column stride) to write into; what lies beyond `width` is not touched.  It may be a view of `payload` itself
+        where the layouts coincide (a dense [B, height, width] view of a payload with P == height*width*bits/8)."""
+        t = self.torch
+        if bits not in (8, 16):
+            raise ValueError("pgm_unpack: bits 8 or 16")
+        es = bits // 8
+        if not (payload.is_cuda and payload.dtype == t.uint8 and payload.dim() == 2 and payload.is_contiguous()
+                and payload.shape[1] % 16 == 0 and payload.shape[1] >= height * width * es and payload.data_ptr() % 16 == 0):
+            raise ValueError("pgm_unpack: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least height*width*bits/8")
+        B = payload.shape[0]
+        dtype = t.uint8 if bits == 8 else t.uint16
+        if out is None:
+            out = t.empty((B, height, width), dtype=dtype, device=payload.device)
+        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
+                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
+            raise ValueError("pgm_unpack: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
+        stream = t.cuda.current_stream(payload.device).cuda_stream
+        self._check(self.L.mrgingham_amd_pgm_unpack_batch(
+            self.ctx, payload.data_ptr(), payload.shape[1], B, int(width), int(height), int(bits), out.data_ptr(),
+            out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+        return out[:, :, :width]
+
+    def read_pgms(self, paths, nthreads=0):
+        """Binary PGM files of one size and depth straight into device frames (mrgingham_amd_read_pgms_batch): `nthreads`
+        host threads (0: all cores, at most 32) read the payloads from the files into page-locked staging, the device
+        swaps the bytes of 16-bit samples and lays out the frames.  -> (frames uint8 or uint16 [B,H,W] on the device,
+        status int32 [B] numpy: 0 loaded, -1 unreadable or not a PGM (a file shorter than its header promises included),
+        -2 a PGM of another size or depth; failed frames are zero).  Size and depth are those of the first file whose
+        header parses (none does: uint8 frames [B,0,0]).  Synchronous."""
+        t = self.torch
+        names = [os.fsencode(p) for p in paths]
+        B = len(names)
+        status = np.full((B,), -1, dtype=np.int32)
+        H = W = 0
+        bits = 8
+        for name in names:
+            try:
+                with open(name, "rb") as f:
+                    data = f.read(4096)
+                    head = pgm_header(data)
+                    if head == PGM_HEADER_CUT:
+                        head = pgm_header(data + f.read())
+            except OSError:
+                head = None
+            if head is not None and head != PGM_HEADER_CUT:
+                H, W, bits, _ = head
+                break
+        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
+        if B == 0 or H == 0:
+            return frames, status
+        arr = (ctypes.c_char_p * B)(*names)
+        t.cuda.current_stream(self.device).synchronize()
+        self._check(self.L.mrgingham_amd_read_pgms_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
                                                          status.ctypes.data))
         return frames, status
 

@@ -46,11 +46,13 @@ struct Options {
     int batch = 0;                // --batch N: frames per chunk of mrgingham_amd_find_boards_files; 0 = not given
     bool entropy_device = false;  // --jpeg-entropy device
     bool png_device = false;      // --png-reconstruct device
+    bool deep_chunks = false;     // --deep-batch chunks
 } opt;
 
 const char* kUsage =
     "Usage: %s [--gridn N] [--noclahe] [--blur radius] [--level l] [--no-refine] [--jobs N]\n"
-    "          [--gpus N|all] [--batch N [--jpeg-entropy host|device] [--png-reconstruct host|device]]\n"
+    "          [--gpus N|all] [--batch N [--jpeg-entropy host|device] [--png-reconstruct host|device]\n"
+    "          [--deep-batch one|chunks]]\n"
     "          [--debug] [--debug-sequence x,y]\n"
     "          imageglobs...\n"
     "\n"
@@ -79,6 +81,8 @@ const char* kUsage =
     "  --jpeg-entropy host|device   with --batch: where JPEG files are Huffman-decoded (default host: --jobs threads)\n"
     "  --png-reconstruct host|device   with --batch: where the row filters of PNG files are undone and colour is reduced\n"
     "                  to grey (default host; device: the --jobs threads only inflate)\n"
+    "  --deep-batch one|chunks   with --batch: how 16-bit PGM / PNG files are processed (default one: one at a time; chunks:\n"
+    "                  in chunks of their own, the byte swap and the 16-bit preprocessing a chunk at a time on the device)\n"
     "  --blobs         find a grid of dark circles instead of a chessboard (no --level, no refinement)\n"
     "  --debug         one image only: write the preprocessed image, the level images, the ChESS\n"
     "                  responses and the corner vnlogs to /tmp like the reference does\n"
@@ -275,7 +279,8 @@ int run_batch() {
     double stats[MRGINGHAM_AMD_FILES_STATS] = {};
     const int rc = mrgingham_amd_find_boards_files_ex(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
                                                       B.status.data(), batch_progress, &B, stats, MRGINGHAM_AMD_FILES_STATS,
-                                                      opt.png_device ? MRGINGHAM_AMD_FILES_PNG_DEVICE : 0);
+                                                      (opt.png_device ? MRGINGHAM_AMD_FILES_PNG_DEVICE : 0) |
+                                                          (opt.deep_chunks ? MRGINGHAM_AMD_FILES_DEEP_CHUNKS : 0));
     fflush(stdout);
     if (getenv("MRGINGHAM_AMD_CLI_TIMING"))
         fprintf(stderr, "batch: %.0f chunks; files: %.0f device loader, %.0f host-decoded, %.0f one at a time, %.0f unreadable; "
@@ -300,8 +305,9 @@ int main(int argc, char* argv[]) {
         {"gpus", required_argument, nullptr, 'G'},     {"batch", required_argument, nullptr, 'T'},
         {"jpeg-entropy", required_argument, nullptr, 'E'},
         {"png-reconstruct", required_argument, nullptr, 'P'},
+        {"deep-batch", required_argument, nullptr, 'Q'},
         {nullptr, 0, nullptr, 0}};
-    bool doblobs = false, entropy_given = false, png_given = false;
+    bool doblobs = false, entropy_given = false, png_given = false, deep_given = false;
     int c;
     while ((c = getopt_long(argc, argv, "hj:b:l:", longopts, nullptr)) != -1) {
         switch (c) {
@@ -355,6 +361,15 @@ int main(int argc, char* argv[]) {
                 png_given = true;
                 opt.png_device = !strcmp(optarg, "device");
                 break;
+            case 'Q':
+                if (strcmp(optarg, "one") && strcmp(optarg, "chunks")) {
+                    fprintf(stderr, "--deep-batch takes 'one' or 'chunks', got '%s'\n", optarg);
+                    fprintf(stderr, kUsage, argv[0]);
+                    return 1;
+                }
+                deep_given = true;
+                opt.deep_chunks = !strcmp(optarg, "chunks");
+                break;
             default:
                 fprintf(stderr, "Unknown option\n");
                 fprintf(stderr, kUsage, argv[0]);
@@ -367,6 +382,10 @@ int main(int argc, char* argv[]) {
     }
     if (png_given && !opt.batch) {
         fprintf(stderr, "--png-reconstruct is only accepted with --batch\n");
+        return 1;
+    }
+    if (deep_given && !opt.batch) {
+        fprintf(stderr, "--deep-batch is only accepted with --batch\n");
         return 1;
     }
     if (opt.batch && (opt.debug || doblobs || opt.gpus > 1 || opt.gpus == -1)) {

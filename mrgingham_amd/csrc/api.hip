@@ -603,6 +603,11 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
         ctx->png_chunk_frames = value;
         return 0;
     }
+    if (!strcmp(name, "pgm_chunk_frames")) {
+        if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "pgm_chunk_frames: 0 (by the scratch budget) or a file count");
+        ctx->pgm_chunk_frames = value;
+        return 0;
+    }
     if (!strcmp(name, "jpeg_entropy")) {
         if (value != 0 && value != 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_entropy: 0 (host threads) or 1 (the device, for files with restart intervals)");
         ctx->jpeg_entropy = value;

@@ -305,6 +305,9 @@ struct mrgingham_amd_ctx {
     // option "png_chunk_frames" (test hook): at most that many files per chunk, 0 = by the budget
     mrg::DevBuf png_row;
     int png_chunk_frames = 0;
+    // mrgingham_amd_read_pgms_batch (pgm_unpack.hip): on loader_slot within jpeg_coef_budget as well (staging: the files'
+    // payloads); option "pgm_chunk_frames" (test hook): at most that many files per chunk, 0 = by the budget
+    int pgm_chunk_frames = 0;
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
     // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
     // context of THIS context's device, created on first use -- not on the calling thread's default context, which

@@ -1,5 +1,6 @@
 // Host side of libmrgingham_amd.so, a list of image files to boards (mrgingham_amd_find_boards_files): the schedule that
-// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip, png_recon.hip), of the preprocessing (preprocess.hip) and of the board
+// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip, png_recon.hip, pgm_unpack.hip), of the preprocessing (preprocess.hip,
+// preprocess16_batch.hip) and of the board
 // detector (boards.hip) fed from a list of several sizes and formats.  No kernel of its own.
 //
 //   loader thread, LOADER context            calling thread, DETECTOR context
@@ -9,6 +10,8 @@
 //     (host threads), upload, event          preprocess_batch on the pix stream, find_boards_submit_ex
 //   JPEG runs -> read_jpegs_batch            collect chunk c - k, scatter its results, advance the final prefix
 //   (PNG runs -> read_pngs_batch where the caller set MRGINGHAM_AMD_FILES_PNG_DEVICE)
+//   (16-bit files, where the caller set MRGINGHAM_AMD_FILES_DEEP_CHUNKS, in chunks of their own: PGM runs ->
+//    read_pgms_batch, PNG as above, as uint16 frames; the detector side runs preprocess16_batch on such a chunk)
 //   chunk c loaded                           (one-image files are processed when the prefix reaches them)
 //
 // The ring has three slots; slot c % 3 holds chunk c from its load to its collect.  What orders the two contexts:
@@ -37,12 +40,13 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 struct FileInfo {
     int w = 0, h = 0, bits = 0, kind = 0;  // kind 0: the probe rejected the file
     bool png_device = false;               // a PNG that goes through read_pngs_batch (MRGINGHAM_AMD_FILES_PNG_DEVICE)
-    bool batch_loader() const { return kind == 3 || png_device; }
+    bool pgm_device = false;               // a 16-bit PGM that goes through read_pgms_batch (MRGINGHAM_AMD_FILES_DEEP_CHUNKS)
+    bool batch_loader() const { return kind == 3 || png_device || pgm_device; }
 };
 
 struct Chunk {
     std::vector<int> files;  // list indices, in slot order
-    int w = 0, h = 0;
+    int w = 0, h = 0, bits = 8;  // one size and one depth
 };
 
 struct Slot {
@@ -87,7 +91,7 @@ struct Run {
     mrgingham_amd_ctx *loader = nullptr, *detector = nullptr;
 };
 
-// frames lie dense in a ring buffer, like the one frame of the one-image path
+// frames lie dense in a ring buffer, like the one frame of the one-image path (the pitch in samples)
 size_t frame_pitch_of(int w, int h) { return (size_t)w * h; }
 
 // One chunk into its slot (loader thread, loader context).  0, or the error that stops the pipeline.
@@ -96,21 +100,22 @@ int load_chunk(Run& R, int c) {
     Slot& S = R.slots[c % kRing];
     mrgingham_amd_ctx* ctx = R.loader;
     const int n = (int)ch.files.size();
-    const size_t pitch = frame_pitch_of(ch.w, ch.h), npx = (size_t)ch.w * ch.h;
+    const size_t es = (size_t)ch.bits / 8, pitch = frame_pitch_of(ch.w, ch.h) * es, npx = (size_t)ch.w * ch.h * es;  // (bytes)
     hipStream_t s = ctx->pix;
     uint8_t *const d_raw = (uint8_t*)S.d_raw.p, *const pin = (uint8_t*)S.pin.p;
     S.load_status.assign((size_t)n, -1);
     if (S.uploaded) MRG_HIP_CHECK(hipEventSynchronize(S.ev_up));  // (long done: the chunk that recorded it has been collected)
     S.uploaded = false;
-    // PGM / PNG: the host threads decode into the staging of the slot, consecutive slots go up in one copy
+    // PGM / PNG: the host threads decode into the staging of the slot (a 16-bit chunk: native uint16 samples), consecutive
+    // slots go up in one copy
     std::vector<int> host;
     for (int k = 0; k < n; ++k)
         if (!R.info[(size_t)ch.files[(size_t)k]].batch_loader()) host.push_back(k);
     if (!host.empty()) {
         for_files<Image>(ctx->pool, R.nthreads, (int)host.size(), [&](int i, Image& im) {
             const int k = host[(size_t)i];
-            if (read_image(R.names[ch.files[(size_t)k]], im) && im.depth == 8 && im.w == ch.w && im.h == ch.h) {
-                memcpy(pin + (size_t)k * pitch, im.px8.data(), npx);
+            if (read_image(R.names[ch.files[(size_t)k]], im) && im.depth == ch.bits && im.w == ch.w && im.h == ch.h) {
+                memcpy(pin + (size_t)k * pitch, ch.bits == 8 ? (const void*)im.px8.data() : (const void*)im.px16.data(), npx);
                 S.load_status[(size_t)k] = 0;
             } else {
                 memset(pin + (size_t)k * pitch, 0, npx);  // (the frame is detected on with its chunk; its result is dropped)
@@ -126,12 +131,12 @@ int load_chunk(Run& R, int c) {
         MRG_HIP_CHECK(hipEventRecord(S.ev_up, s));
         S.uploaded = true;
     }
-    // JPEG, and PNG where the caller asked for it: every run of consecutive slots of one of them is one call of its batch
-    // loader, straight into the chunk's frames
+    // JPEG, and PNG / 16-bit PGM where the caller asked for it: every run of consecutive slots of one of them is one call of
+    // its batch loader, straight into the chunk's frames
     long nbatch_ok = 0;
     auto route = [&](int k) {
         const FileInfo& f = R.info[(size_t)ch.files[(size_t)k]];
-        return f.kind == 3 ? 1 : f.png_device ? 2 : 0;
+        return f.kind == 3 ? 1 : f.png_device ? 2 : f.pgm_device ? 3 : 0;
     };
     for (int k = 0; k < n;) {
         const int via = route(k);
@@ -140,10 +145,12 @@ int load_chunk(Run& R, int c) {
         while (j < n && route(j) == via) ++j;
         std::vector<const char*> run;
         for (int i = k; i < j; ++i) run.push_back(R.names[ch.files[(size_t)i]]);
-        const int rc = via == 1 ? mrgingham_amd_read_jpegs_batch(ctx, run.data(), j - k, ch.w, ch.h, d_raw + (size_t)k * pitch, (int64_t)pitch,
-                                                                 ch.w, R.nthreads, S.load_status.data() + k)
-                                : mrgingham_amd_read_pngs_batch(ctx, run.data(), j - k, ch.w, ch.h, 8, d_raw + (size_t)k * pitch, (int64_t)pitch,
-                                                                ch.w, R.nthreads, S.load_status.data() + k);
+        uint8_t* const frames = d_raw + (size_t)k * pitch;
+        const int64_t fpitch = (int64_t)frame_pitch_of(ch.w, ch.h);
+        int32_t* const st = S.load_status.data() + k;
+        const int rc = via == 1   ? mrgingham_amd_read_jpegs_batch(ctx, run.data(), j - k, ch.w, ch.h, frames, fpitch, ch.w, R.nthreads, st)
+                       : via == 2 ? mrgingham_amd_read_pngs_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
+                                  : mrgingham_amd_read_pgms_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st);
         if (rc) return rc;
         for (int i = k; i < j; ++i) {
             if (S.load_status[(size_t)i] == 0) ++nbatch_ok;
@@ -219,7 +226,7 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
                                        int loader_flags) {
-    if (nfiles < 0 || (loader_flags & ~MRGINGHAM_AMD_FILES_PNG_DEVICE) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
+    if (nfiles < 0 || (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS)) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
         o->blur_radius > 64 || o->device < -1 || nstats < 0 || (nstats > 0 && !stats) ||
         (nfiles > 0 && (!filenames || !h_boards || !h_levels || !h_found_level || !h_status)))
         return MRGINGHAM_AMD_ERR_ARG;
@@ -247,6 +254,8 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
     R.nthreads = host_threads(o->nthreads);
     // ---- routing: what every file is, which size bucket it belongs to
     R.info.resize((size_t)nfiles);
+    const bool deep_chunks = (loader_flags & MRGINGHAM_AMD_FILES_DEEP_CHUNKS) != 0;
+    bool any_deep = false;
     std::vector<int32_t> key((size_t)nfiles, -1);
     {
         HostPool probe_pool;
@@ -254,8 +263,9 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
             FileInfo& f = R.info[(size_t)i];
             if (!probe_image(filenames[i], &f.w, &f.h, &f.bits, &f.kind)) f = FileInfo{};
             // (palette files keep the host decoder: read_pngs_batch would hand them to it anyway, one by one)
-            if ((loader_flags & MRGINGHAM_AMD_FILES_PNG_DEVICE) && f.kind == 2 && f.bits == 8)
+            if ((loader_flags & MRGINGHAM_AMD_FILES_PNG_DEVICE) && f.kind == 2 && (f.bits == 8 || deep_chunks))
                 f.png_device = png_header(filenames[i], nullptr, nullptr, nullptr) != 3;
+            f.pgm_device = deep_chunks && f.kind == 1 && f.bits == 16;
         });
     }
     size_t max_frame = 0, max_host_frame = 0;
@@ -263,11 +273,14 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
         const FileInfo& f = R.info[(size_t)i];
         h_status[i] = f.kind ? 0 : -1;
         h_found_level[i] = -1;
-        // the batch preprocessing refuses CLAHE below 8 x 8 pixels, the one-image path of 16-bit files does not exist in
-        // chunks: such files take the one-image path (key -1), like the ones the probe rejected take none
-        if (!f.kind || f.bits != 8 || (o->do_clahe && (f.w < 8 || f.h < 8))) continue;
-        key[(size_t)i] = (int32_t)(((uint32_t)f.h << 15) | (uint32_t)f.w);  // (sides are at most 32767)
-        const size_t fp = frame_pitch_of(f.w, f.h);
+        // the batch preprocessing refuses CLAHE below 8 x 8 pixels, 16-bit files are in chunks only where the caller asked
+        // for it: such files take the one-image path (key -1), like the ones the probe rejected take none
+        const bool deep = f.bits == 16;
+        if (!f.kind || (deep ? !deep_chunks : f.bits != 8) || (o->do_clahe && (f.w < 8 || f.h < 8))) continue;
+        // (sides are at most 32767: 30 bits; bit 30 is the depth, so a chunk holds one size and one depth)
+        key[(size_t)i] = (int32_t)(((uint32_t)deep << 30) | ((uint32_t)f.h << 15) | (uint32_t)f.w);
+        any_deep = any_deep || deep;
+        const size_t fp = frame_pitch_of(f.w, f.h) * (size_t)(f.bits / 8);  // bytes
         if (fp > max_frame) max_frame = fp;
         if (!f.batch_loader() && fp > max_host_frame) max_host_frame = fp;
     }
@@ -284,6 +297,7 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
             ch.files.push_back(i);  // (ascending i = ascending slot: files keep list order inside a key)
             ch.w = R.info[(size_t)i].w;
             ch.h = R.info[(size_t)i].h;
+            ch.bits = R.info[(size_t)i].bits;
         }
 
     // ---- the two contexts, the ring
@@ -310,7 +324,8 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
         for (int k = 0; k < nslots; ++k) {
             Slot& S = R.slots[k];
             if (hipMalloc(&S.d_raw.p, bytes) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
-            if (preprocess && hipMalloc(&S.d_pre.p, bytes) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
+            // (a 16-bit chunk always has preprocessed frames: the conversion to 8 bit is part of its preprocessing)
+            if ((preprocess || any_deep) && hipMalloc(&S.d_pre.p, bytes) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
             if (max_host_frame && hipHostMalloc(&S.pin.p, (size_t)R.batch * max_host_frame, hipHostMallocDefault) != hipSuccess)
                 return MRGINGHAM_AMD_ERR_DEVICE;
             if (S.ev_up.create(hipEventDisableTiming) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
@@ -422,7 +437,12 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
         if (S.uploaded) MRG_HIP_CHECK(hipStreamWaitEvent(ctx->pix, S.ev_up, 0));
         mrgingham_amd_frames fr{(uint8_t*)S.d_raw.p, (int64_t)pitch, n, ch.w, ch.h, ch.w};
         int r = 0;
-        if (preprocess) {
+        if (ch.bits == 16) {
+            // what the one-image path does with a 16-bit image: normalize + CLAHE at 16 bit, convertTo 8 bit, the blur
+            r = mrgingham_amd_preprocess16_batch(ctx, (const uint16_t*)S.d_raw.p, (int64_t)pitch, n, ch.w, ch.h, ch.w, o->do_clahe,
+                                                 o->blur_radius, (uint8_t*)S.d_pre.p, ctx->pix);
+            fr.frames = (uint8_t*)S.d_pre.p;
+        } else if (preprocess) {
             // on the pixel stream, like the one-image path: the detector's pixel kernels follow it there
             r = mrgingham_amd_preprocess_batch(ctx, &fr, o->do_clahe, o->blur_radius, (uint8_t*)S.d_pre.p, ctx->pix);
             fr.frames = (uint8_t*)S.d_pre.p;

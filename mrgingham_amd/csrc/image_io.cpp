@@ -34,35 +34,44 @@ static void about_to_hold(Image& im, size_t n8, size_t n16) {
     if (im.before_grow && (n8 > im.px8.capacity() || n16 > im.px16.capacity())) im.before_grow(n8, n16);
 }
 
-static bool decode_pgm(const std::vector<uint8_t>& b, Image& im) {
+// The one parser of a binary PGM's header (image_io.h).
+int pgm_header(const uint8_t* b, size_t nbytes, int* width, int* height, int* bits, size_t* payload_offset) {
+    if (!b || nbytes < 2 || b[0] != 'P' || b[1] != '5') return -1;
     size_t p = 2;
-    auto next_int = [&](int& v) {
+    int v[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {
         for (;;) {
-            while (p < b.size() && (b[p] == ' ' || b[p] == '\t' || b[p] == '\n' || b[p] == '\r')) ++p;
-            if (p < b.size() && b[p] == '#') { while (p < b.size() && b[p] != '\n') ++p; continue; }
+            while (p < nbytes && (b[p] == ' ' || b[p] == '\t' || b[p] == '\n' || b[p] == '\r')) ++p;
+            if (p < nbytes && b[p] == '#') { while (p < nbytes && b[p] != '\n') ++p; continue; }
             break;
         }
-        if (p >= b.size() || b[p] < '0' || b[p] > '9') return false;
+        if (p >= nbytes) return kPgmHeaderCut;
+        if (b[p] < '0' || b[p] > '9') return -1;
         long x = 0;
-        while (p < b.size() && b[p] >= '0' && b[p] <= '9') { x = x * 10 + (b[p] - '0'); if (x > 1 << 30) return false; ++p; }
-        v = (int)x;
-        return true;
-    };
-    int w, h, maxval;
-    if (!next_int(w) || !next_int(h) || !next_int(maxval)) return false;
-    if (p >= b.size()) return false;
-    ++p;  // the single whitespace after maxval
-    if (w <= 0 || h <= 0 || w > kMaxSide || h > kMaxSide || maxval <= 0 || maxval > 65535) return false;
+        while (p < nbytes && b[p] >= '0' && b[p] <= '9') { x = x * 10 + (b[p] - '0'); if (x > 1 << 30) return -1; ++p; }
+        v[k] = (int)x;
+    }
+    if (p >= nbytes) return kPgmHeaderCut;  // (the last number may go on, and the single whitespace after it is part of the header)
+    ++p;
+    if (v[0] <= 0 || v[1] <= 0 || v[0] > kMaxSide || v[1] > kMaxSide || v[2] <= 0 || v[2] > 65535) return -1;
+    if (width) *width = v[0];
+    if (height) *height = v[1];
+    if (bits) *bits = v[2] < 256 ? 8 : 16;
+    if (payload_offset) *payload_offset = p;
+    return 0;
+}
+
+static bool decode_pgm(const std::vector<uint8_t>& b, Image& im) {
+    int w = 0, h = 0, bits = 0;
+    size_t p = 0;
+    if (pgm_header(b.data(), b.size(), &w, &h, &bits, &p) != 0) return false;
     const size_t n = (size_t)w * h;
-    im.w = w; im.h = h;
-    if (maxval < 256) {
-        if (b.size() - p < n) return false;
-        im.depth = 8;
+    if (b.size() - p < n * (size_t)(bits / 8)) return false;
+    im.w = w; im.h = h; im.depth = bits;
+    if (bits == 8) {
         about_to_hold(im, n, 0);
         im.px8.assign(b.begin() + p, b.begin() + p + n);
     } else {
-        if (b.size() - p < 2 * n) return false;
-        im.depth = 16;
         about_to_hold(im, 0, n);
         im.px16.resize(n);
         for (size_t i = 0; i < n; ++i) im.px16[i] = (uint16_t)((b[p + 2 * i] << 8) | b[p + 2 * i + 1]);
@@ -224,33 +233,17 @@ static int read_pgm8_direct(const char* path, Image& im) {
     if (!f) return -1;
     uint8_t head[128];
     const size_t got = fread(head, 1, sizeof(head), f);
-    int rc = 0;
-    if (got >= 8 && head[0] == 'P' && head[1] == '5') {
-        size_t p = 2;
-        int v[3] = {0, 0, 0};
-        bool ok = true;
-        for (int k = 0; k < 3 && ok; ++k) {
-            for (;;) {
-                while (p < got && (head[p] == ' ' || head[p] == '\t' || head[p] == '\n' || head[p] == '\r')) ++p;
-                if (p < got && head[p] == '#') { while (p < got && head[p] != '\n') ++p; continue; }
-                break;
-            }
-            if (p >= got || head[p] < '0' || head[p] > '9') { ok = false; break; }
-            long x = 0;
-            while (p < got && head[p] >= '0' && head[p] <= '9') { x = x * 10 + (head[p] - '0'); if (x > 1 << 30) { ok = false; break; } ++p; }
-            v[k] = (int)x;
-        }
-        // (a header with a long comment does not fit the 128 bytes: the general path takes it)
-        if (ok && p < got && v[2] > 0 && v[2] < 256 && v[0] > 0 && v[1] > 0 && v[0] <= kMaxSide && v[1] <= kMaxSide) {
-            ++p;  // the single whitespace after maxval
-            const size_t n = (size_t)v[0] * v[1];
-            im.w = v[0]; im.h = v[1]; im.depth = 8;
-            about_to_hold(im, n, 0);
-            im.px8.resize(n);
-            const size_t have = got - p < n ? got - p : n;
-            memcpy(im.px8.data(), head + p, have);
-            rc = fread(im.px8.data() + have, 1, n - have, f) == n - have ? 1 : -1;
-        }
+    int rc = 0, w = 0, h = 0, bits = 0;
+    size_t p = 0;
+    // (a header with a long comment does not fit the 128 bytes, a 16-bit file is not this function's: the general path takes them)
+    if (got >= 8 && pgm_header(head, got, &w, &h, &bits, &p) == 0 && bits == 8) {
+        const size_t n = (size_t)w * h;
+        im.w = w; im.h = h; im.depth = 8;
+        about_to_hold(im, n, 0);
+        im.px8.resize(n);
+        const size_t have = got - p < n ? got - p : n;
+        memcpy(im.px8.data(), head + p, have);
+        rc = fread(im.px8.data() + have, 1, n - have, f) == n - have ? 1 : -1;
     }
     fclose(f);
     return rc;
@@ -296,33 +289,13 @@ bool probe_image(const char* path, int* width, int* height, int* bits, int* kind
         int w = 0, h = 0, d = 0, k = 0;
         if (ok && b[0] == 'P' && b[1] == '5') {
             k = 1;
-            for (int pass = 0; pass < 2 && ok; ++pass) {
-                size_t p = 2;
-                int v[3] = {0, 0, 0};
-                bool parsed = true;
-                for (int i = 0; i < 3 && parsed; ++i) {
-                    for (;;) {
-                        while (p < b.size() && (b[p] == ' ' || b[p] == '\t' || b[p] == '\n' || b[p] == '\r')) ++p;
-                        if (p < b.size() && b[p] == '#') { while (p < b.size() && b[p] != '\n') ++p; continue; }
-                        break;
-                    }
-                    if (p >= b.size() || b[p] < '0' || b[p] > '9') { parsed = false; break; }
-                    long x = 0;
-                    while (p < b.size() && b[p] >= '0' && b[p] <= '9') { x = x * 10 + (b[p] - '0'); if (x > 1 << 30) { parsed = false; break; } ++p; }
-                    v[i] = (int)x;
-                }
-                if ((!parsed || p >= b.size()) && pass == 0 && b.size() < (size_t)size) {  // the header may go on
-                    ok = rest();
-                    continue;
-                }
-                ok = parsed && p < b.size();
-                if (!ok) break;
-                ++p;  // the single whitespace after maxval
-                if (v[0] <= 0 || v[1] <= 0 || v[0] > kMaxSide || v[1] > kMaxSide || v[2] <= 0 || v[2] > 65535) { ok = false; break; }
-                w = v[0]; h = v[1]; d = v[2] < 256 ? 8 : 16;
-                ok = (size_t)size - p >= (size_t)w * h * (d / 8);
-                break;
+            size_t p = 0;
+            int rc = pgm_header(b.data(), b.size(), &w, &h, &d, &p);
+            if (rc == kPgmHeaderCut && b.size() < (size_t)size) {  // the header may go on
+                ok = rest();
+                if (ok) rc = pgm_header(b.data(), b.size(), &w, &h, &d, &p);
             }
+            ok = ok && rc == 0 && (size_t)size - p >= (size_t)w * h * (d / 8);
         } else if (ok && b[0] == 0x89 && b[1] == 'P') {
             k = 2;
             static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
@@ -408,6 +381,10 @@ void to_8bit(const Image& im, std::vector<uint8_t>& out) {
 }
 
 }  // namespace mrg
+
+extern "C" int mrgingham_amd_pgm_header(const uint8_t* data, size_t nbytes, int* width, int* height, int* bits, size_t* payload_offset) {
+    return mrg::pgm_header(data, nbytes, width, height, bits, payload_offset);
+}
 
 extern "C" int mrgingham_amd_png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan_capacity, int* width,
                                            int* height, int* bits, int* color_type) {

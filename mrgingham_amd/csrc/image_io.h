@@ -31,6 +31,15 @@ bool read_image(const char* path, Image& im);
 // short or breaks a rule (sides above 32767 included), a PGM shorter than its header promises.  A file that passes may
 // still fail to decode.  Never throws, never sizes anything from an unchecked field.
 bool probe_image(const char* path, int* width, int* height, int* bits, int* kind);
+// The header of a binary PGM (P5) held in memory, whole or only its first nbytes: the one parser behind read_image's two
+// PGM readers, probe_image and the batch loader (mrgingham_amd_read_pgms_batch).  0: a header that keeps the rules --
+// "P5", three decimal numbers separated by white space and # comments, ONE byte after the last; sides 1 .. 32767, maxval
+// 1 .. 65535 -- with *bits 8 (maxval < 256) or 16 and *payload_offset the byte the samples begin at (16-bit samples are
+// big-endian pairs).  -1: not such a file, or a rule is broken.  kPgmHeaderCut: the bytes end inside the header -- of a
+// whole file that is unreadable, of a file's first bytes it asks for more.  The payload is the caller's to check:
+// a file is readable when it holds width * height * bits / 8 bytes from *payload_offset on.  Any output may be NULL.
+constexpr int kPgmHeaderCut = -2;
+int pgm_header(const uint8_t* data, size_t nbytes, int* width, int* height, int* bits, size_t* payload_offset);
 // The host half of the PNG device route (mrgingham_amd_png_scanlines): decode_png's header and chunk rules, then the
 // inflated, still filtered scanlines -- row y is scan[(rowbytes + 1) * y]: its filter byte, then rowbytes bytes -- into
 // `scan` (NULL: sizes only).  0 taken; kPngNotTaken readable, but a palette file (the host decoder's alone: sizes are
