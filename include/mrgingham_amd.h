@@ -57,7 +57,12 @@ extern "C" {
  *      (loader flags: MRGINGHAM_AMD_FILES_PNG_DEVICE).  Off unless asked for: every earlier call behaves as before.
  *      Later, additive (the version stays 4: new symbols and a new flag value break no caller): mrgingham_amd_pgm_header,
  *      _pgm_unpack_batch, _read_pgms_batch (binary PGM payloads to frames on the device); option "pgm_chunk_frames"; loader
- *      flag MRGINGHAM_AMD_FILES_DEEP_CHUNKS (16-bit PGM / PNG files in chunks).  Off unless asked for. */
+ *      flag MRGINGHAM_AMD_FILES_DEEP_CHUNKS (16-bit PGM / PNG files in chunks).  Off unless asked for.
+ *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (kind 4) read strip TIFF;
+ *      mrgingham_amd_tiff_layout, _tiff_decode_batch, _tiff_geometry, _read_tiffs_batch (TIFF: LZW strips, predictor and
+ *      grey on the device); options "tiff_chunk_frames", "tiff_lzw_max_strip", "tiff_lzw_lanes";
+ *      mrgingham_amd_find_boards_files_ex2 (loader flag MRGINGHAM_AMD_FILES_TIFF_DEVICE).  The device route is off unless
+ *      asked for. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -348,8 +353,9 @@ bool find_chessboard_from_image_file_C(const char* filename, const int gridn, in
                                        bool (*add_points)(double* xy, int N, void* cookie), void* cookie);
 
 /* The image decoder behind the two functions above and the command-line tool, on its own (host only, no
- * device needed): binary PGM (8 / 16 bit), non-interlaced PNG and baseline JPEG (see
- * mrgingham_amd_jpeg_coefficients for what is accepted).  `out` (may be NULL: sizes only)
+ * device needed): binary PGM (8 / 16 bit), non-interlaced PNG, baseline JPEG (see
+ * mrgingham_amd_jpeg_coefficients for what is accepted) and strip TIFF (see mrgingham_amd_tiff_layout for
+ * what is accepted).  `out` (may be NULL: sizes only)
  * receives width*height grey bytes.  16-bit samples: cli_scaling = 0 keeps the high byte, what
  * cv::imread(IMREAD_GRAYSCALE) gives the file entry points; 1 rescales by 255/65535 with rounding, what
  * the CLI's convertTo does (mrgingham-from-image.cc:85-92).  Returns 0; -1 unreadable, unsupported or
@@ -529,6 +535,89 @@ int mrgingham_amd_read_pgms_batch(mrgingham_amd_ctx* ctx, const char* const* fil
                                   int bits, void* d_out, int64_t frame_pitch, int stride, int nthreads,
                                   int32_t* h_status);
 
+/* TIFF, host half (host only, no device needed): the one parser of a TIFF's first image file directory, behind
+ * mrgingham_amd_read_image, _probe_image and _read_tiffs_batch.  `data` is a whole file held in memory.  The subset is
+ * closed, and everything outside it is unreadable; every field is checked before anything is sized from it:
+ *   classic TIFF (magic 42; BigTIFF is unreadable), byte orders II and MM, the first IFD only; the entries looked at have
+ *   type BYTE, SHORT or LONG, inline or at an offset, offsets and counts checked against nbytes in 64 bits; a tag twice is
+ *   unreadable; ImageWidth, ImageLength, BitsPerSample, PhotometricInterpretation, StripOffsets and StripByteCounts are
+ *   required;
+ *   BitsPerSample 8 or 16, one value per sample, all equal; SampleFormat absent or 1; SamplesPerPixel 1 .. 4 (samples
+ *   behind the first -- grey -- or the third -- RGB -- are extra samples and ignored); PlanarConfiguration, FillOrder and
+ *   Orientation absent or 1; Photometric 0 (WhiteIsZero: read as maxval - v), 1, or 2 (RGB, at least 3 samples: grey is
+ *   (R*4899 + G*9617 + B*1868 + 8192) >> 14); strips only (any tile tag: unreadable), RowsPerStrip absent or above the
+ *   height = one strip, the last strip may be short, strips lie anywhere in the file in any order; sides 1 .. 32767;
+ *   Compression 1 (none), 5 (LZW: MSB-first codes of 9 .. 12 bits, ClearCode 256, EOI 257, the width growing one code
+ *   early), 32773 (PackBits, a run never crossing its row), 8 and 32946 (Deflate); Predictor absent, 1 or 2 (horizontal
+ *   differences per sample, mod 2^bits, on 16-bit samples in value order).
+ * A strip whose byte count cannot give its rows -- uncompressed: fewer bytes than rows x rowbytes; compressed: fewer than
+ * the best ratio of the scheme allows -- makes the file unreadable here; whether a compressed strip gives EXACTLY its
+ * rows x rowbytes is the decoder's to find out (LZW: a code above the next free one, a non-clear code after code 4095 has
+ * been assigned, EOI or the end of the strip's bytes before its bytes are out; what follows the last needed code is
+ * ignored; the decoder starts cleared whether or not the stream opens with ClearCode).
+ * Outputs: *info (may be NULL); strips (may be NULL: counts only) receives up to `capacity` records, strip i covering
+ * rows [first_row, first_row + rows) from `nbytes` bytes at `offset` of the file; *nstrips (may be NULL) the number of
+ * strips.  lzw_max_strip: the decoded bytes of an LZW strip above which the file is left to the host decoder (<= 0 or
+ * above 2^20: 2^20, the limit of the kernel's table entries; option "tiff_lzw_max_strip" of a context).
+ * Returns 0: mrgingham_amd_tiff_decode_batch takes the file (compression 1 or 5); MRGINGHAM_AMD_TIFF_NOT_TAKEN: readable,
+ * but mrgingham_amd_read_image's decoder alone reads it (PackBits, Deflate, an LZW strip above lzw_max_strip), outputs as
+ * for 0; -1: unreadable; -2: capacity below the strip count (*info and *nstrips are still reported).  Never throws,
+ * allocates nothing, never reads out of bounds on a crafted file. */
+#define MRGINGHAM_AMD_TIFF_NOT_TAKEN -3
+typedef struct mrgingham_amd_tiff_info {
+    int32_t width, height, bits, samples, photometric, compression, predictor, big_endian;
+} mrgingham_amd_tiff_info;
+typedef struct mrgingham_amd_tiff_strip {
+    int64_t offset, nbytes;   /* in the file */
+    int32_t first_row, rows;  /* of the image */
+} mrgingham_amd_tiff_strip;
+int mrgingham_amd_tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info,
+                              mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips);
+
+/* TIFF, device half: nframes files of ONE size, depth, sample count, photometric, compression (1 or 5), predictor and byte
+ * order (`info`, HOST; what mrgingham_amd_tiff_layout reported for every one of them) from their bytes to grey frames,
+ * byte for byte what mrgingham_amd_read_image computes.  d_files: file f's bytes at d_files + f*file_pitch (BYTES; d_files
+ * 16-byte aligned, file_pitch a multiple of 16).  d_strips (DEVICE): file f's strip records, as mrgingham_amd_tiff_layout
+ * wrote them, at d_strips + f*strips_pitch, d_nstrips[f] (DEVICE) of them, at most strips_pitch.  d_out: uint8_t frames
+ * for bits 8, native-endian uint16_t frames for bits 16; frame f row y at d_out + f*frame_pitch + y*stride, ELEMENTS; only
+ * the width x height samples are written, what lies between width and stride stays untouched.  d_status (DEVICE, nframes
+ * words, written): 0 decoded; -1 an LZW strip broke a rule of the decoder, or a strip record does not fit its file or
+ * frame (offset + nbytes above file_pitch, rows outside the frame or not in strip order, a decoded size above 1 MiB) --
+ * that frame is zero-filled, the others are not affected.  d_strip_status (DEVICE, may be NULL; nframes*strips_pitch
+ * words): per LZW strip 0, or what stopped its lane (tiff_lzw.h).
+ * Compression 5 first runs tiff_lzw_kernel, one lane per strip: a fixed number of lanes loops over the strips, each with
+ * a table of 4096 dwords in context scratch (interleaved by lane: at most 16384 lanes x 16 KiB = 256 MiB, whatever the
+ * batch), decoding into context scratch of nframes x rowbytes x height; a lane reads nothing beyond its strip's byte
+ * count and writes nothing beyond its strip's rows.  Then tiff_finish_kernel, one wave per row: value order, predictor 2
+ * undone by a prefix sum mod 2^bits, WhiteIsZero inverted, grey.  Asynchronous on `stream` (NULL = default); allocates
+ * nothing beyond context scratch.  Arguments are checked like mrgingham_amd_png_reconstruct_batch's (MRGINGHAM_AMD_ERR_ARG,
+ * nothing written). */
+int mrgingham_amd_tiff_decode_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch,
+                                    const mrgingham_amd_tiff_strip* d_strips, int strips_pitch, const int32_t* d_nstrips,
+                                    int nframes, const mrgingham_amd_tiff_info* info, void* d_out, int64_t frame_pitch,
+                                    int stride, int32_t* d_status, int32_t* d_strip_status, void* stream);
+
+/* The constants of those kernels' schedules, for tests that place their shapes on the seams: the lanes in flight of the
+ * LZW launch (strip s is decoded by lane s modulo that many; option "tiff_lzw_lanes" lowers it), the pixels of a row a
+ * lane of the finish kernel takes, and the pixels of a row a wave takes per step (the prefix sum of predictor 2 is carried
+ * from lane to lane inside a step and from step to step). */
+void mrgingham_amd_tiff_geometry(int* lzw_lanes, int* segment_pixels, int* step_pixels);
+
+/* nfiles TIFF files of ONE size and depth straight into device frames (layout and element type as d_out above): per file
+ * a host thread (nthreads of them; <= 0: all cores, at most 32) reads the file straight into page-locked staging and runs
+ * mrgingham_amd_tiff_layout -- no sample is touched on the host --; a chunk of files goes up in three copies (the files, their strip tables packed
+ * to the chunk's largest strip count, their strip counts) and through one
+ * mrgingham_amd_tiff_decode_batch per run of files of equal (samples, photometric, compression, predictor, byte order)
+ * while the host threads read the next.  A file the device route does not take (MRGINGHAM_AMD_TIFF_NOT_TAKEN, or a file
+ * much larger than its samples) is decoded by the host thread with mrgingham_amd_read_image's decoder and uploaded: same
+ * bytes.  h_status[f]: 0 decoded, -1 unreadable / unsupported / malformed (or not a TIFF), -2 a TIFF of another size or
+ * depth; the frame of a failed file is zero-filled.  SYNCHRONOUS: d_out is complete on return.  Returns MRGINGHAM_AMD_OK
+ * also when files failed.  Completes the find_boards jobs in flight first and restores the caller's HIP device.  The
+ * chunk buffers are those of mrgingham_amd_read_jpegs_batch, within the same 1 GiB (option "tiff_chunk_frames"). */
+int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
+                                   int bits, void* d_out, int64_t frame_pitch, int stride, int nthreads,
+                                   int32_t* h_status);
+
 /* The same preprocessing for one HOST image (out: dense width x height bytes, host): what the Python
  * recipe of find_board.docstring:8-10 does with cv2 before find_board.  Uses the calling thread's
  * context.  Returns 0, or -2 on an argument or device error. */
@@ -611,7 +700,8 @@ int mrgingham_amd_find_boards_submit_ex(mrgingham_amd_ctx* ctx, const mrgingham_
 /* ---- a list of image files to boards ---------------------------------------------------------------------------
  * What mrgingham_amd_read_image would produce for a file, from its header alone (host only, no device needed, nothing
  * is decoded): *width, *height, *bits (8 or 16), *kind (1 binary PGM, 2 PNG, 3 baseline JPEG: the header parse of
- * mrgingham_amd_jpeg_coefficients, up to and including SOS).  Any output pointer may be NULL.  Returns 0; -1 for what
+ * mrgingham_amd_jpeg_coefficients, up to and including SOS; 4 TIFF: mrgingham_amd_tiff_layout's parse of the directory
+ * and the strip table).  Any output pointer may be NULL.  Returns 0; -1 for what
  * read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut short or
  * breaks a rule (sides above 32767, interlaced PNG, progressive JPEG, ...), a PGM shorter than its header promises.  A
  * file that passes may still fail to decode.  Never sizes anything from an unchecked field. */
@@ -636,7 +726,7 @@ int mrgingham_amd_files_plan(const int32_t* key, int nfiles, int batch_frames, i
  * that context has scratch sets and collects them in chunk order.  The two are ordered by events and by what has been
  * collected; nothing synchronises the device in the steady state.  Restores the caller's current HIP device.
  * Routing by mrgingham_amd_probe_image: 8-bit files of one size share chunks (mrgingham_amd_files_plan, key = size) --
- * JPEG files through mrgingham_amd_read_jpegs_batch straight into the chunk's frames, PGM / PNG files decoded by the
+ * JPEG files through mrgingham_amd_read_jpegs_batch straight into the chunk's frames, PGM / PNG / TIFF files decoded by the
  * loader's host threads into page-locked staging and uploaded; 16-bit files (unless mrgingham_amd_find_boards_files_ex is
  * given MRGINGHAM_AMD_FILES_DEEP_CHUNKS), and sizes the batch entry points refuse
  * while the one-image path takes them (CLAHE below 8 x 8 pixels), go one at a time through the one-image path on the
@@ -661,8 +751,8 @@ typedef struct mrgingham_amd_files_options {
     int device;       /* -1: the device of the calling thread's context (mrgingham_amd_thread_device) */
 } mrgingham_amd_files_options;
 #define MRGINGHAM_AMD_FILES_CHUNKS 0           /* chunks that went through the ring */
-#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch (PNG_DEVICE) / _read_pgms_batch (DEEP_CHUNKS: 16-bit PGM) */
-#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (8-bit PGM / PNG; 16-bit PNG with DEEP_CHUNKS alone) */
+#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch (PNG_DEVICE) / _read_pgms_batch (DEEP_CHUNKS: 16-bit PGM) / _read_tiffs_batch (TIFF_DEVICE) */
+#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (8-bit PGM / PNG / TIFF; 16-bit PNG / TIFF with DEEP_CHUNKS alone) */
 #define MRGINGHAM_AMD_FILES_ONE_IMAGE 3        /* files through the one-image path */
 #define MRGINGHAM_AMD_FILES_UNREADABLE 4       /* files with status -1 ([1] + [2] + [3] + [4] = nfiles) */
 #define MRGINGHAM_AMD_FILES_DETECTOR_WAIT_MS 5 /* wall ms the calling thread waited for a loaded chunk: the loader bounds the run */
@@ -691,6 +781,18 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
                                        double* h_boards, signed char* h_levels, signed char* h_found_level,
                                        int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
                                        double* stats, int nstats, int loader_flags);
+
+/* mrgingham_amd_find_boards_files_ex with one more loader flag (the older entry point goes on refusing it).  Without it
+ * TIFF files behave as PGM and PNG files do: 8-bit files of one size share chunks and are decoded by the loader's host
+ * threads (MRGINGHAM_AMD_FILES_HOST_DECODED), 16-bit files take the one-image path or, with DEEP_CHUNKS, chunks of their own.
+ * MRGINGHAM_AMD_FILES_TIFF_DEVICE: runs of consecutive TIFF slots of a chunk (8-bit; 16-bit under DEEP_CHUNKS) go through
+ * mrgingham_amd_read_tiffs_batch on the loader context and are counted under MRGINGHAM_AMD_FILES_DEVICE_LOADED.  Same
+ * outputs.  Any bit above the three flags is MRGINGHAM_AMD_ERR_ARG. */
+#define MRGINGHAM_AMD_FILES_TIFF_DEVICE 4
+int mrgingham_amd_find_boards_files_ex2(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
+                                        double* h_boards, signed char* h_levels, signed char* h_found_level,
+                                        int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
+                                        double* stats, int nstats, int loader_flags);
 
 /* Where the find_boards calls of this context spent their HOST time since the last reset, and what their grid-finder
  * threads did (the reference's find_grid_from_points, mrgingham.cc:51, is the host part of the product call; on a busy
@@ -843,6 +945,14 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         budget; n > 0 = at most n files per chunk.  Results never depend on it.
  *   "png_chunk_frames"    test hook: the same for mrgingham_amd_read_pngs_batch.
  *   "pgm_chunk_frames"    test hook: the same for mrgingham_amd_read_pgms_batch.
+ *   "tiff_chunk_frames"   test hook: the same for mrgingham_amd_read_tiffs_batch.
+ *   "tiff_lzw_max_strip"  decoded bytes of an LZW strip, 1 .. 1048576 (the limit of the kernel's table entries; default
+ *                         65536): a file with a larger strip keeps the host threads in mrgingham_amd_read_tiffs_batch.  It
+ *                         bounds the serial work of one lane: on 64 12 MP files mrgingham_amd_read_tiffs_batch was measured
+ *                         faster through the device than on 16 host threads at 8 KiB and 64 KiB strips and slower at 1 MiB
+ *                         (the sizes between were not measured).
+ *   "tiff_lzw_lanes"      test hook: lanes in flight of the LZW launch, a multiple of 64 up to 16384; 0 (default) = 16384.
+ *                         Results never depend on it.
  *   "jpeg_entropy"        0 (default): mrgingham_amd_read_jpegs_batch entropy-decodes on its host threads; 1: files with
  *                         restart intervals are Huffman-decoded on the device, one lane per interval.  Same frames and statuses.
  *   "jpeg_entropy_max_interval"  MCUs per restart interval the device accepts (default 1024, at least 1; files above it go

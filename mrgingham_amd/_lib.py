@@ -25,6 +25,17 @@ class FilesOptions(ctypes.Structure):
                                             "batch_frames", "nthreads", "jpeg_entropy", "device")]
 
 
+class TiffInfo(ctypes.Structure):
+    """mrgingham_amd_tiff_info"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "bits", "samples", "photometric", "compression", "predictor",
+                                              "big_endian")]
+
+
+class TiffStrip(ctypes.Structure):
+    """mrgingham_amd_tiff_strip"""
+    _fields_ = [("offset", ctypes.c_int64), ("nbytes", ctypes.c_int64), ("first_row", ctypes.c_int32), ("rows", ctypes.c_int32)]
+
+
 class Frames(ctypes.Structure):
     """mrgingham_amd_frames"""
     _fields_ = [("frames", ctypes.c_void_p), ("frame_pitch", ctypes.c_int64), ("nframes", ctypes.c_int),
@@ -56,6 +67,8 @@ EXPORTS = [
     "mrgingham_amd_png_scanlines", "mrgingham_amd_png_reconstruct_batch", "mrgingham_amd_png_reconstruct_geometry",
     "mrgingham_amd_read_pngs_batch", "mrgingham_amd_find_boards_files_ex",
     "mrgingham_amd_pgm_header", "mrgingham_amd_pgm_unpack_batch", "mrgingham_amd_read_pgms_batch",
+    "mrgingham_amd_tiff_layout", "mrgingham_amd_tiff_decode_batch", "mrgingham_amd_tiff_geometry",
+    "mrgingham_amd_read_tiffs_batch", "mrgingham_amd_find_boards_files_ex2",
 ]
 
 
@@ -166,6 +179,17 @@ def lib():
                                                      c_vp]
         L.mrgingham_amd_read_pgms_batch.argtypes = [c_vp, ctypes.POINTER(ctypes.c_char_p), c_int, c_int, c_int, c_int, c_vp,
                                                     ctypes.c_int64, c_int, c_int, c_vp]
+    if hasattr(L, "mrgingham_amd_tiff_decode_batch"):
+        L.mrgingham_amd_tiff_layout.argtypes = [c_vp, ctypes.c_size_t, ctypes.c_int64, ctypes.POINTER(TiffInfo), c_vp, ctypes.c_size_t,
+                                                ctypes.POINTER(ctypes.c_size_t)]
+        L.mrgingham_amd_tiff_decode_batch.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp, c_int, c_vp, c_int, ctypes.POINTER(TiffInfo), c_vp,
+                                                      ctypes.c_int64, c_int, c_vp, c_vp, c_vp]
+        L.mrgingham_amd_tiff_geometry.argtypes = [ctypes.POINTER(c_int)] * 3
+        L.mrgingham_amd_tiff_geometry.restype = None
+        L.mrgingham_amd_read_tiffs_batch.argtypes = [c_vp, ctypes.POINTER(ctypes.c_char_p), c_int, c_int, c_int, c_int, c_vp,
+                                                     ctypes.c_int64, c_int, c_int, c_vp]
+        L.mrgingham_amd_find_boards_files_ex2.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
+                                                          c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]
     L.mrgingham_amd_host_alloc.argtypes = [ctypes.c_size_t]

@@ -241,8 +241,62 @@ def png_reconstruct_geometry():
     return r.value, s.value
 
 
+class TiffLayout:
+    """What tiff_layout found in a TIFF file: height, width, bits, samples, photometric, compression, predictor, big_endian;
+    nstrips and strips, a structured array (offset, nbytes, first_row, rows) of the records that fitted the capacity;
+    taken: the device route (Detector.tiff_decode) takes the file, False: read_image's decoder alone reads it; rc: the
+    C call's return value (0, TIFF_NOT_TAKEN, or -2 where a given capacity was too small)."""
+    FIELDS = ("width", "height", "bits", "samples", "photometric", "compression", "predictor", "big_endian")
+
+    def __init__(self, info, strips, nstrips, rc):
+        for n in self.FIELDS:
+            setattr(self, n, int(getattr(info, n)))
+        self.strips, self.nstrips, self.rc, self.taken = strips, int(nstrips), int(rc), rc == 0
+
+    def key(self):
+        return tuple(getattr(self, n) for n in self.FIELDS)
+
+    def __repr__(self):
+        return "TiffLayout(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.FIELDS) + f", nstrips={self.nstrips}, rc={self.rc})"
+
+
+TIFF_NOT_TAKEN = -3
+TIFF_STRIP = np.dtype([("offset", "<i8"), ("nbytes", "<i8"), ("first_row", "<i4"), ("rows", "<i4")])
+
+
+def tiff_layout(data, lzw_max_strip=0, capacity=None):
+    """The first image file directory of a TIFF held in memory (host only; mrgingham_amd_tiff_layout, which has the subset
+    this library reads): -> TiffLayout, or None when the data is not a TIFF this library reads.  lzw_max_strip: the decoded
+    bytes of an LZW strip above which the file is left to the host decoder (0: 1 MiB).  capacity: room for that many
+    strip records (default: all of them); with fewer than the file has, rc is -2 and the counts are still reported."""
+    L = _lib.lib()
+    buf = bytes(data)
+    info, n = _lib.TiffInfo(), ctypes.c_size_t()
+    rc = L.mrgingham_amd_tiff_layout(buf, len(buf), int(lzw_max_strip), ctypes.byref(info), None, 0, ctypes.byref(n))
+    if rc not in (0, TIFF_NOT_TAKEN):
+        return None
+    cap = n.value if capacity is None else int(capacity)
+    strips = np.zeros(cap, dtype=TIFF_STRIP)
+    rc = L.mrgingham_amd_tiff_layout(buf, len(buf), int(lzw_max_strip), ctypes.byref(info), strips.ctypes.data if cap else None, cap,
+                                     ctypes.byref(n))
+    if cap == 0 and n.value > 0 and capacity is not None:
+        rc = -2   # (no array to write into is "counts only" at the C boundary)
+    if rc not in (0, TIFF_NOT_TAKEN, -2):
+        return None
+    return TiffLayout(info, strips[:min(cap, n.value)], n.value, rc)
+
+
+def tiff_geometry():
+    """(lzw_lanes, segment_pixels, step_pixels) of the TIFF kernels' schedules (mrgingham_amd_tiff_geometry): the lanes in
+    flight of the LZW launch, the pixels of a row a lane of the finish kernel takes and the pixels a wave takes per step."""
+    a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.lib().mrgingham_amd_tiff_geometry(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+    return a.value, b.value, c.value
+
+
 def read_image(filename, cli_scaling=False):
-    """Decode a binary PGM, non-interlaced PNG or baseline JPEG to uint8 [H, W] with the library's own decoder (host only).
+    """Decode a binary PGM, non-interlaced PNG, baseline JPEG or strip TIFF (uncompressed, LZW, PackBits, Deflate; grey or
+    RGB, 8 or 16 bit) to uint8 [H, W] with the library's own decoder (host only).
     16-bit files: the high byte (cv::imread(IMREAD_GRAYSCALE)) or, with cli_scaling, the CLI's
     convertTo(255/65535).  None when the file is unreadable, unsupported or malformed."""
     L = _lib.lib()
@@ -260,7 +314,7 @@ def read_image(filename, cli_scaling=False):
 
 def probe_image(filename):
     """What read_image would produce for the file, from its header alone (mrgingham_amd_probe_image; host only, nothing is
-    decoded): (height, width, bits, kind) with kind 1 binary PGM, 2 PNG, 3 baseline JPEG; None for a file that is
+    decoded): (height, width, bits, kind) with kind 1 binary PGM, 2 PNG, 3 baseline JPEG, 4 TIFF; None for a file that is
     unreadable at header level."""
     w, h, b, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     if _lib.lib().mrgingham_amd_probe_image(os.fsencode(filename), ctypes.byref(w), ctypes.byref(h), ctypes.byref(b),
@@ -288,8 +342,8 @@ FILES_STATS = ("chunks", "files_device_loader", "files_host_decoded", "files_one
 
 
 def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_radius=1, refine=True, batch=64, nthreads=0,
-                      entropy="host", device=None, progress=None, png="host", deep="one"):
-    """A list of image files (binary PGM, PNG, baseline JPEG; any sizes) to boards (mrgingham_amd_find_boards_files): a
+                      entropy="host", device=None, progress=None, png="host", deep="one", tiff="host"):
+    """A list of image files (binary PGM, PNG, baseline JPEG, TIFF; any sizes) to boards (mrgingham_amd_find_boards_files): a
     loader thread fills chunks of `batch` equally-sized frames on the device -- JPEG through the batch loader,
     entropy="device": Huffman-decoded on the device as well -- while the calling thread preprocesses and searches the
     chunks before them.  Per file the same numbers as read_image + the one-image path with the same options.
@@ -302,7 +356,12 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
     same numbers.  deep="one": 16-bit files go one at a time through the one-image path on this thread; deep="chunks":
     16-bit PGM and PNG files of one size share chunks of their own -- PGM through Detector.read_pgms (files_device_loader),
     PNG through the PNG batch loader with png="device", else decoded on the loader's host threads (files_host_decoded) --
-    and are preprocessed at 16 bit a chunk at a time; same numbers."""
+    and are preprocessed at 16 bit a chunk at a time; same numbers.  TIFF files behave as PNG files do: 8-bit files share
+    chunks and are decoded on the loader's host threads, 16-bit files follow `deep`; tiff="device": the runs of TIFF files
+    of a chunk go through the TIFF batch loader (Detector.read_tiffs: the host threads only read the files, LZW strips are
+    decoded one lane each) and count as files_device_loader; same numbers."""
+    if tiff not in ("host", "device"):
+        raise ValueError('find_boards_files: tiff is "host" or "device"')
     if entropy not in ("host", "device"):
         raise ValueError('find_boards_files: entropy is "host" or "device"')
     if png not in ("host", "device"):
@@ -330,9 +389,9 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
                 raised.append(e)
     cb = _lib.PROGRESS_F(on_progress)
     arr = (ctypes.c_char_p * max(n, 1))(*names)
-    rc = L.mrgingham_amd_find_boards_files_ex(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
-                                              status.ctypes.data, cb, None, stats.ctypes.data, len(stats),
-                                              int(png == "device") | 2 * int(deep == "chunks"))
+    rc = L.mrgingham_amd_find_boards_files_ex2(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
+                                               status.ctypes.data, cb, None, stats.ctypes.data, len(stats),
+                                               int(png == "device") | 2 * int(deep == "chunks") | 4 * int(tiff == "device"))
     if raised:
         raise raised[0]
     if rc == -1:
@@ -1052,6 +1111,76 @@ class Detector:
         t.cuda.current_stream(self.device).synchronize()
         self._check(self.L.mrgingham_amd_read_pgms_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
                                                          status.ctypes.data))
+        return frames, status
+
+    def tiff_decode(self, datas, layouts=None, out=None):
+        """TIFF files held in memory to grey frames on the device (mrgingham_amd_tiff_decode_batch), on torch's current
+        stream: datas, a list of bytes; layouts, their tiff_layout results (default: computed here), which must all be
+        taken by the device route and agree in every field -> (frames uint8 or uint16 [B, height, width], the samples
+        read_image's decoder gives; status int32 [B] numpy: 0, or -1 for a file whose LZW strips broke a rule -- its frame
+        is zero; strip_status int32 [B, P] numpy: per strip what stopped its lane, 0 for none).  `out`: a [B, height,
+        >= width] device tensor of that type (unit column stride) to write into; what lies beyond `width` is not touched.
+        Synchronises (the status words come back)."""
+        t = self.torch
+        datas = [bytes(d) for d in datas]
+        if layouts is None:
+            layouts = [tiff_layout(d) for d in datas]
+        B = len(datas)
+        if B == 0 or len(layouts) != B or any(l is None or not l.taken for l in layouts) or len({l.key() for l in layouts}) != 1:
+            raise ValueError("tiff_decode: at least one file, all taken by the device route (tiff_layout) and equal in every field")
+        lay = layouts[0]
+        W, H, P = lay.width, lay.height, max(l.nstrips for l in layouts)
+        pitch = (max(len(d) for d in datas) + 15) // 16 * 16
+        h_files = np.zeros((B, pitch), dtype=np.uint8)
+        h_strips = np.zeros((B, P), dtype=TIFF_STRIP)
+        for i, (d, l) in enumerate(zip(datas, layouts)):
+            h_files[i, :len(d)] = np.frombuffer(d, dtype=np.uint8)
+            h_strips[i, :l.nstrips] = l.strips
+        d_files = t.from_numpy(h_files).to(self.device)
+        d_strips = t.from_numpy(h_strips.view(np.uint8).reshape(B, -1)).to(self.device)
+        d_ns = t.tensor([l.nstrips for l in layouts], dtype=t.int32, device=self.device)
+        d_status = t.full((B,), -7, dtype=t.int32, device=self.device)
+        d_sstatus = t.zeros((B, P), dtype=t.int32, device=self.device)
+        dtype = t.uint8 if lay.bits == 8 else t.uint16
+        if out is None:
+            out = t.empty((B, H, W), dtype=dtype, device=self.device)
+        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == H
+                and out.shape[2] >= W and (out.shape[2] <= 1 or out.stride(2) == 1)):
+            raise ValueError("tiff_decode: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
+        info = _lib.TiffInfo(*lay.key())
+        stream = t.cuda.current_stream(self.device).cuda_stream
+        self._check(self.L.mrgingham_amd_tiff_decode_batch(
+            self.ctx, d_files.data_ptr(), pitch, d_strips.data_ptr(), P, d_ns.data_ptr(), B, ctypes.byref(info), out.data_ptr(),
+            out.stride(0) if B > 1 else H * out.stride(1), out.stride(1) if H > 1 else out.shape[2], d_status.data_ptr(),
+            d_sstatus.data_ptr(), stream))
+        return out[:, :, :W], d_status.cpu().numpy(), d_sstatus.cpu().numpy()
+
+    def read_tiffs(self, paths, nthreads=0):
+        """TIFF files of one size and depth straight into device frames (mrgingham_amd_read_tiffs_batch): `nthreads` host
+        threads (0: all cores, at most 32) read the files into page-locked staging and parse their directories, the device
+        decodes the LZW strips one lane each, undoes the predictor and reduces colour to grey.  -> (frames uint8 or uint16
+        [B,H,W] on the device, status int32 [B] numpy: 0 decoded, -1 unreadable / unsupported / malformed, -2 a TIFF of
+        another size or depth; failed frames are zero).  Size and depth are those of the first file whose directory
+        parses (none does: uint8 frames [B,0,0]).  PackBits and Deflate files, and LZW files with a strip above option
+        "tiff_lzw_max_strip", are decoded by the host threads: same bytes.  Synchronous."""
+        t = self.torch
+        names = [os.fsencode(p) for p in paths]
+        B = len(names)
+        status = np.full((B,), -1, dtype=np.int32)
+        H = W = 0
+        bits = 8
+        for p in paths:
+            head = probe_image(p)
+            if head is not None and head[3] == 4:
+                H, W, bits, _ = head
+                break
+        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
+        if B == 0 or H == 0:
+            return frames, status
+        arr = (ctypes.c_char_p * B)(*names)
+        t.cuda.current_stream(self.device).synchronize()
+        self._check(self.L.mrgingham_amd_read_tiffs_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
+                                                          status.ctypes.data))
         return frames, status
 
     BLOBS_STATS = ("calls", "chunks", "nodes", "contours", "points", "device_ms", "host_ms", "frames")

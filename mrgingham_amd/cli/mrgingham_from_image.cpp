@@ -47,16 +47,17 @@ struct Options {
     bool entropy_device = false;  // --jpeg-entropy device
     bool png_device = false;      // --png-reconstruct device
     bool deep_chunks = false;     // --deep-batch chunks
+    bool tiff_device = false;     // --tiff-lzw device
 } opt;
 
 const char* kUsage =
     "Usage: %s [--gridn N] [--noclahe] [--blur radius] [--level l] [--no-refine] [--jobs N]\n"
     "          [--gpus N|all] [--batch N [--jpeg-entropy host|device] [--png-reconstruct host|device]\n"
-    "          [--deep-batch one|chunks]]\n"
+    "          [--deep-batch one|chunks] [--tiff-lzw host|device]]\n"
     "          [--debug] [--debug-sequence x,y]\n"
     "          imageglobs...\n"
     "\n"
-    "Finds the chessboard in every image (binary PGM, PNG or baseline JPEG) and writes a vnlog table\n"
+    "Finds the chessboard in every image (binary PGM, PNG, baseline JPEG or strip TIFF) and writes a vnlog table\n"
     "\n"
     "  # filename x y level\n"
     "\n"
@@ -83,6 +84,8 @@ const char* kUsage =
     "                  to grey (default host; device: the --jobs threads only inflate)\n"
     "  --deep-batch one|chunks   with --batch: how 16-bit PGM / PNG files are processed (default one: one at a time; chunks:\n"
     "                  in chunks of their own, the byte swap and the 16-bit preprocessing a chunk at a time on the device)\n"
+    "  --tiff-lzw host|device   with --batch: where the strips of TIFF files are decoded and their rows reduced to grey\n"
+    "                  (default host; device: the --jobs threads only read the files, LZW strips are decoded one lane each)\n"
     "  --blobs         find a grid of dark circles instead of a chessboard (no --level, no refinement)\n"
     "  --debug         one image only: write the preprocessed image, the level images, the ChESS\n"
     "                  responses and the corner vnlogs to /tmp like the reference does\n"
@@ -277,10 +280,11 @@ int run_batch() {
     o.jpeg_entropy = opt.entropy_device;
     o.device = -1;
     double stats[MRGINGHAM_AMD_FILES_STATS] = {};
-    const int rc = mrgingham_amd_find_boards_files_ex(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
-                                                      B.status.data(), batch_progress, &B, stats, MRGINGHAM_AMD_FILES_STATS,
-                                                      (opt.png_device ? MRGINGHAM_AMD_FILES_PNG_DEVICE : 0) |
-                                                          (opt.deep_chunks ? MRGINGHAM_AMD_FILES_DEEP_CHUNKS : 0));
+    const int rc = mrgingham_amd_find_boards_files_ex2(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
+                                                       B.status.data(), batch_progress, &B, stats, MRGINGHAM_AMD_FILES_STATS,
+                                                       (opt.png_device ? MRGINGHAM_AMD_FILES_PNG_DEVICE : 0) |
+                                                           (opt.deep_chunks ? MRGINGHAM_AMD_FILES_DEEP_CHUNKS : 0) |
+                                                           (opt.tiff_device ? MRGINGHAM_AMD_FILES_TIFF_DEVICE : 0));
     fflush(stdout);
     if (getenv("MRGINGHAM_AMD_CLI_TIMING"))
         fprintf(stderr, "batch: %.0f chunks; files: %.0f device loader, %.0f host-decoded, %.0f one at a time, %.0f unreadable; "
@@ -306,8 +310,9 @@ int main(int argc, char* argv[]) {
         {"jpeg-entropy", required_argument, nullptr, 'E'},
         {"png-reconstruct", required_argument, nullptr, 'P'},
         {"deep-batch", required_argument, nullptr, 'Q'},
+        {"tiff-lzw", required_argument, nullptr, 'Z'},
         {nullptr, 0, nullptr, 0}};
-    bool doblobs = false, entropy_given = false, png_given = false, deep_given = false;
+    bool doblobs = false, entropy_given = false, png_given = false, deep_given = false, tiff_given = false;
     int c;
     while ((c = getopt_long(argc, argv, "hj:b:l:", longopts, nullptr)) != -1) {
         switch (c) {
@@ -370,6 +375,15 @@ int main(int argc, char* argv[]) {
                 deep_given = true;
                 opt.deep_chunks = !strcmp(optarg, "chunks");
                 break;
+            case 'Z':
+                if (strcmp(optarg, "host") && strcmp(optarg, "device")) {
+                    fprintf(stderr, "--tiff-lzw takes 'host' or 'device', got '%s'\n", optarg);
+                    fprintf(stderr, kUsage, argv[0]);
+                    return 1;
+                }
+                tiff_given = true;
+                opt.tiff_device = !strcmp(optarg, "device");
+                break;
             default:
                 fprintf(stderr, "Unknown option\n");
                 fprintf(stderr, kUsage, argv[0]);
@@ -386,6 +400,10 @@ int main(int argc, char* argv[]) {
     }
     if (deep_given && !opt.batch) {
         fprintf(stderr, "--deep-batch is only accepted with --batch\n");
+        return 1;
+    }
+    if (tiff_given && !opt.batch) {
+        fprintf(stderr, "--tiff-lzw is only accepted with --batch\n");
         return 1;
     }
     if (opt.batch && (opt.debug || doblobs || opt.gpus > 1 || opt.gpus == -1)) {

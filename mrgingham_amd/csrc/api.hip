@@ -608,6 +608,21 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
         ctx->pgm_chunk_frames = value;
         return 0;
     }
+    if (!strcmp(name, "tiff_chunk_frames")) {
+        if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "tiff_chunk_frames: 0 (by the scratch budget) or a file count");
+        ctx->tiff_chunk_frames = value;
+        return 0;
+    }
+    if (!strcmp(name, "tiff_lzw_max_strip")) {
+        if (value < 1 || value > (1 << 20)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "tiff_lzw_max_strip: decoded bytes per strip, 1 .. 1048576");
+        ctx->tiff_lzw_max_strip = value;
+        return 0;
+    }
+    if (!strcmp(name, "tiff_lzw_lanes")) {
+        if (value < 0 || value > 16384 || (value & 63)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "tiff_lzw_lanes: 0 (16384) or a multiple of 64 up to 16384");
+        ctx->tiff_lzw_lanes = value;
+        return 0;
+    }
     if (!strcmp(name, "jpeg_entropy")) {
         if (value != 0 && value != 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_entropy: 0 (host threads) or 1 (the device, for files with restart intervals)");
         ctx->jpeg_entropy = value;

@@ -308,6 +308,16 @@ struct mrgingham_amd_ctx {
     // mrgingham_amd_read_pgms_batch (pgm_unpack.hip): on loader_slot within jpeg_coef_budget as well (staging: the files'
     // payloads); option "pgm_chunk_frames" (test hook): at most that many files per chunk, 0 = by the budget
     int pgm_chunk_frames = 0;
+    // mrgingham_amd_read_tiffs_batch / _tiff_decode_batch (tiff_decode.hip): the loader runs on loader_slot within
+    // jpeg_coef_budget too (staging: the files as they lie on disk, their strip tables); tiff_raw: the decoded strips of an
+    // LZW launch, rowbytes x height per frame; tiff_table: 4096 dwords per lane in flight, interleaved by lane;
+    // tiff_broken: per frame, set by a lane whose strip broke a rule.  Options "tiff_chunk_frames" (test hook: at most
+    // that many files per chunk, 0 = by the budget), "tiff_lzw_max_strip" (decoded bytes of an LZW strip above which a
+    // file keeps the host decoder) and "tiff_lzw_lanes" (test hook: lanes in flight of the LZW launch, 0 = 16384)
+    mrg::DevBuf tiff_raw, tiff_table, tiff_broken;
+    int tiff_chunk_frames = 0;
+    int tiff_lzw_max_strip = 64 << 10;  // (measured: DESIGN.md section 4.14)
+    int tiff_lzw_lanes = 0;
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
     // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
     // context of THIS context's device, created on first use -- not on the calling thread's default context, which

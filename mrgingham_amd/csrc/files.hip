@@ -1,5 +1,5 @@
 // Host side of libmrgingham_amd.so, a list of image files to boards (mrgingham_amd_find_boards_files): the schedule that
-// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip, png_recon.hip, pgm_unpack.hip), of the preprocessing (preprocess.hip,
+// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip, png_recon.hip, pgm_unpack.hip, tiff_decode.hip), of the preprocessing (preprocess.hip,
 // preprocess16_batch.hip) and of the board
 // detector (boards.hip) fed from a list of several sizes and formats.  No kernel of its own.
 //
@@ -9,7 +9,8 @@
 //   PGM / PNG -> page-locked staging         pix stream waits for the slot's upload event
 //     (host threads), upload, event          preprocess_batch on the pix stream, find_boards_submit_ex
 //   JPEG runs -> read_jpegs_batch            collect chunk c - k, scatter its results, advance the final prefix
-//   (PNG runs -> read_pngs_batch where the caller set MRGINGHAM_AMD_FILES_PNG_DEVICE)
+//   (PNG runs -> read_pngs_batch where the caller set MRGINGHAM_AMD_FILES_PNG_DEVICE,
+//    TIFF runs -> read_tiffs_batch where the caller set MRGINGHAM_AMD_FILES_TIFF_DEVICE)
 //   (16-bit files, where the caller set MRGINGHAM_AMD_FILES_DEEP_CHUNKS, in chunks of their own: PGM runs ->
 //    read_pgms_batch, PNG as above, as uint16 frames; the detector side runs preprocess16_batch on such a chunk)
 //   chunk c loaded                           (one-image files are processed when the prefix reaches them)
@@ -41,7 +42,8 @@ struct FileInfo {
     int w = 0, h = 0, bits = 0, kind = 0;  // kind 0: the probe rejected the file
     bool png_device = false;               // a PNG that goes through read_pngs_batch (MRGINGHAM_AMD_FILES_PNG_DEVICE)
     bool pgm_device = false;               // a 16-bit PGM that goes through read_pgms_batch (MRGINGHAM_AMD_FILES_DEEP_CHUNKS)
-    bool batch_loader() const { return kind == 3 || png_device || pgm_device; }
+    bool tiff_device = false;              // a TIFF that goes through read_tiffs_batch (MRGINGHAM_AMD_FILES_TIFF_DEVICE)
+    bool batch_loader() const { return kind == 3 || png_device || pgm_device || tiff_device; }
 };
 
 struct Chunk {
@@ -136,7 +138,7 @@ int load_chunk(Run& R, int c) {
     long nbatch_ok = 0;
     auto route = [&](int k) {
         const FileInfo& f = R.info[(size_t)ch.files[(size_t)k]];
-        return f.kind == 3 ? 1 : f.png_device ? 2 : f.pgm_device ? 3 : 0;
+        return f.kind == 3 ? 1 : f.png_device ? 2 : f.pgm_device ? 3 : f.tiff_device ? 4 : 0;
     };
     for (int k = 0; k < n;) {
         const int via = route(k);
@@ -150,7 +152,8 @@ int load_chunk(Run& R, int c) {
         int32_t* const st = S.load_status.data() + k;
         const int rc = via == 1   ? mrgingham_amd_read_jpegs_batch(ctx, run.data(), j - k, ch.w, ch.h, frames, fpitch, ch.w, R.nthreads, st)
                        : via == 2 ? mrgingham_amd_read_pngs_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
-                                  : mrgingham_amd_read_pgms_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st);
+                       : via == 3 ? mrgingham_amd_read_pgms_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
+                                  : mrgingham_amd_read_tiffs_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st);
         if (rc) return rc;
         for (int i = k; i < j; ++i) {
             if (S.load_status[(size_t)i] == 0) ++nbatch_ok;
@@ -218,15 +221,24 @@ int mrgingham_amd_files_plan(const int32_t* key, int nfiles, int batch_frames, i
 int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
                                     double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
                                     void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats) {
-    return mrgingham_amd_find_boards_files_ex(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
-                                              nstats, 0);
+    return mrgingham_amd_find_boards_files_ex2(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
+                                               nstats, 0);
 }
 
 int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
                                        int loader_flags) {
-    if (nfiles < 0 || (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS)) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
+    if (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS)) return MRGINGHAM_AMD_ERR_ARG;
+    return mrgingham_amd_find_boards_files_ex2(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
+                                               nstats, loader_flags);
+}
+
+int mrgingham_amd_find_boards_files_ex2(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
+                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
+                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
+                                        int loader_flags) {
+    if (nfiles < 0 || (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE)) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
         o->blur_radius > 64 || o->device < -1 || nstats < 0 || (nstats > 0 && !stats) ||
         (nfiles > 0 && (!filenames || !h_boards || !h_levels || !h_found_level || !h_status)))
         return MRGINGHAM_AMD_ERR_ARG;
@@ -266,6 +278,7 @@ int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles,
             if ((loader_flags & MRGINGHAM_AMD_FILES_PNG_DEVICE) && f.kind == 2 && (f.bits == 8 || deep_chunks))
                 f.png_device = png_header(filenames[i], nullptr, nullptr, nullptr) != 3;
             f.pgm_device = deep_chunks && f.kind == 1 && f.bits == 16;
+            f.tiff_device = (loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEVICE) && f.kind == 4 && (f.bits == 8 || deep_chunks);
         });
     }
     size_t max_frame = 0, max_host_frame = 0;

@@ -2,6 +2,7 @@
 #include "image_io.h"
 #include "jpeg.h"
 #include "png_filter.h"
+#include "tiff_lzw.h"
 #include "../../include/mrgingham_amd.h"
 
 #include <stdio.h>
@@ -10,6 +11,7 @@
 #include <zlib.h>
 
 #include <cmath>
+#include <memory>
 
 namespace mrg {
 
@@ -225,6 +227,217 @@ static bool decode_jpeg(const std::vector<uint8_t>& b, Image& im) {
     return true;
 }
 
+// ---- TIFF (image_io.h: tiff_layout has the subset)
+
+namespace {
+
+struct TiffEntry {
+    bool present = false;
+    uint32_t type = 0, count = 0;
+    size_t at = 0;  // where the values lie in the file (checked: at + count * size <= nbytes)
+};
+
+struct TiffReader {
+    const uint8_t* b;
+    size_t n;
+    bool be;
+    uint32_t u16(size_t p) const { return be ? (uint32_t)(b[p] << 8 | b[p + 1]) : (uint32_t)(b[p + 1] << 8 | b[p]); }
+    uint32_t u32(size_t p) const {
+        return be ? ((uint32_t)b[p] << 24 | (uint32_t)b[p + 1] << 16 | (uint32_t)b[p + 2] << 8 | b[p + 3])
+                  : ((uint32_t)b[p + 3] << 24 | (uint32_t)b[p + 2] << 16 | (uint32_t)b[p + 1] << 8 | b[p]);
+    }
+    // value i (< count) of an entry of type BYTE, SHORT or LONG
+    uint32_t value(const TiffEntry& e, uint32_t i) const {
+        return e.type == 1 ? b[e.at + i] : e.type == 3 ? u16(e.at + 2 * (size_t)i) : u32(e.at + 4 * (size_t)i);
+    }
+};
+
+// the tags the reader looks at; every other tag of the IFD is passed over, whatever its type
+enum { kTagWidth, kTagHeight, kTagBits, kTagCompression, kTagPhotometric, kTagFillOrder, kTagStripOffsets, kTagOrientation,
+       kTagSamples, kTagRowsPerStrip, kTagStripByteCounts, kTagPlanar, kTagPredictor, kTagTileWidth, kTagTileLength,
+       kTagTileOffsets, kTagTileByteCounts, kTagSampleFormat, kTags };
+const uint16_t kTiffTagIds[kTags] = {256, 257, 258, 259, 262, 266, 273, 274, 277, 278, 279, 284, 317, 322, 323, 324, 325, 339};
+
+}  // namespace
+
+int tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info_out,
+                mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips_out) {
+    if (nstrips_out) *nstrips_out = 0;
+    if (!data || nbytes < 8) return -1;
+    TiffReader r{data, nbytes, false};
+    if (data[0] == 'I' && data[1] == 'I') r.be = false;
+    else if (data[0] == 'M' && data[1] == 'M') r.be = true;
+    else return -1;
+    if (r.u16(2) != 42) return -1;  // (43: BigTIFF)
+    const uint64_t ifd = r.u32(4);
+    if (ifd < 8 || ifd + 2 > nbytes) return -1;
+    const uint64_t nent = r.u16((size_t)ifd);
+    if (ifd + 2 + 12 * nent > nbytes) return -1;
+    TiffEntry e[kTags];
+    for (uint64_t k = 0; k < nent; ++k) {
+        const size_t p = (size_t)(ifd + 2 + 12 * k);
+        const uint32_t tag = r.u16(p);
+        int t = -1;
+        for (int i = 0; i < kTags; ++i)
+            if (kTiffTagIds[i] == tag) t = i;
+        if (t < 0) continue;
+        TiffEntry& x = e[t];
+        if (x.present) return -1;  // a tag twice
+        x.present = true;
+        x.type = r.u16(p + 2);
+        x.count = r.u32(p + 4);
+        if ((x.type != 1 && x.type != 3 && x.type != 4) || x.count == 0) return -1;
+        // count * size in 64 bits: at most 2^34
+        const uint64_t bytes = (uint64_t)x.count * (x.type == 1 ? 1u : x.type == 3 ? 2u : 4u);
+        if (bytes <= 4) x.at = p + 8;
+        else {
+            const uint64_t off = r.u32(p + 8);
+            if (off > nbytes || bytes > nbytes - off) return -1;
+            x.at = (size_t)off;
+        }
+    }
+    auto one = [&](int t, uint32_t dflt, bool* ok) -> uint32_t {  // a tag that holds one value
+        if (!e[t].present) return dflt;
+        if (e[t].count != 1) { *ok = false; return dflt; }
+        return r.value(e[t], 0);
+    };
+    bool ok = true;
+    if (e[kTagTileWidth].present || e[kTagTileLength].present || e[kTagTileOffsets].present || e[kTagTileByteCounts].present) return -1;
+    if (!e[kTagWidth].present || !e[kTagHeight].present || !e[kTagBits].present || !e[kTagPhotometric].present ||
+        !e[kTagStripOffsets].present || !e[kTagStripByteCounts].present)
+        return -1;
+    const uint32_t w = one(kTagWidth, 0, &ok), h = one(kTagHeight, 0, &ok), spp = one(kTagSamples, 1, &ok);
+    const uint32_t comp = one(kTagCompression, 1, &ok), photo = one(kTagPhotometric, 0, &ok), pred = one(kTagPredictor, 1, &ok);
+    uint32_t rps = one(kTagRowsPerStrip, 0xFFFFFFFFu, &ok);
+    if (!ok || one(kTagFillOrder, 1, &ok) != 1 || one(kTagOrientation, 1, &ok) != 1 || one(kTagPlanar, 1, &ok) != 1 || !ok) return -1;
+    if (w == 0 || h == 0 || w > (uint32_t)kMaxSide || h > (uint32_t)kMaxSide || spp < 1 || spp > 4) return -1;
+    if (e[kTagBits].count != spp) return -1;
+    const uint32_t bits = r.value(e[kTagBits], 0);
+    for (uint32_t i = 1; i < spp; ++i)
+        if (r.value(e[kTagBits], i) != bits) return -1;
+    if (bits != 8 && bits != 16) return -1;
+    if (e[kTagSampleFormat].present) {
+        if (e[kTagSampleFormat].count > spp) return -1;
+        for (uint32_t i = 0; i < e[kTagSampleFormat].count; ++i)
+            if (r.value(e[kTagSampleFormat], i) != 1) return -1;
+    }
+    if (photo > 2 || (photo == 2 && spp < 3)) return -1;
+    if (comp != 1 && comp != 5 && comp != 32773 && comp != 8 && comp != 32946) return -1;
+    if (pred != 1 && pred != 2) return -1;
+    if (rps == 0) return -1;
+    if (rps > h) rps = h;
+    const uint32_t ns = (h + rps - 1) / rps;
+    if (e[kTagStripOffsets].count != ns || e[kTagStripByteCounts].count != ns) return -1;
+    const uint64_t rowb = (uint64_t)w * spp * (bits / 8);
+    bool taken = comp == 1 || comp == 5;
+    if (lzw_max_strip <= 0 || lzw_max_strip > (int64_t)kTiffLzwMaxStrip20) lzw_max_strip = (int64_t)kTiffLzwMaxStrip20;
+    for (uint32_t i = 0; i < ns; ++i) {
+        const uint64_t off = r.value(e[kTagStripOffsets], i), cnt = r.value(e[kTagStripByteCounts], i);
+        const uint32_t first = i * rps, rows = h - first < rps ? h - first : rps;
+        if (off > nbytes || cnt > nbytes - off) return -1;
+        if (comp == 1 && cnt < rows * rowb) return -1;
+        // (a code is at least 9 bits and gives fewer than 4096 bytes: a strip that cannot hold its rows is refused before
+        // anything is sized for them)
+        if (comp == 5 && (cnt * 8 / 9 + 1) * 4096 < rows * rowb) return -1;
+        if (comp == 32773 && cnt * 64 < rows * rowb) return -1;                       // (two bytes give at most 128)
+        if ((comp == 8 || comp == 32946) && (cnt + 1) * 1040 < rows * rowb) return -1;  // (Deflate: below 1032 to 1)
+        if (comp == 5 && rows * rowb > (uint64_t)lzw_max_strip) taken = false;
+        if (strips && i < capacity) strips[i] = mrgingham_amd_tiff_strip{(int64_t)off, (int64_t)cnt, (int32_t)first, (int32_t)rows};
+    }
+    if (info_out)
+        *info_out = mrgingham_amd_tiff_info{(int32_t)w, (int32_t)h, (int32_t)bits, (int32_t)spp, (int32_t)photo, (int32_t)comp,
+                                            (int32_t)pred, r.be ? 1 : 0};
+    if (nstrips_out) *nstrips_out = ns;
+    if (strips && capacity < ns) return -2;
+    return taken ? 0 : kTiffNotTaken;
+}
+
+// one decoded row (file bytes, rowb of them) to grey samples: value order, predictor 2 undone, WhiteIsZero inverted, the
+// first sample or png_grey of the first three -- the steps of tiff_finish_kernel (tiff_decode.hip)
+template <class T>
+static void tiff_finish_row(const uint8_t* s, const mrgingham_amd_tiff_info& ti, T* o) {
+    constexpr uint32_t mask = sizeof(T) == 1 ? 255u : 65535u;
+    const int spp = ti.samples, nc = ti.photometric == 2 ? 3 : 1;
+    uint32_t acc[3] = {0, 0, 0};
+    for (int x = 0; x < ti.width; ++x) {
+        uint32_t v[3] = {0, 0, 0};
+        for (int c = 0; c < nc; ++c) {
+            const uint8_t* q = s + ((size_t)x * spp + c) * sizeof(T);
+            uint32_t raw = sizeof(T) == 1 ? q[0] : ti.big_endian ? (uint32_t)(q[0] << 8 | q[1]) : (uint32_t)(q[1] << 8 | q[0]);
+            if (ti.predictor == 2) raw = acc[c] = (acc[c] + raw) & mask;
+            v[c] = ti.photometric == 0 ? mask - raw : raw;
+        }
+        o[x] = (T)(nc == 3 ? png_grey(v[0], v[1], v[2]) : v[0]);
+    }
+}
+
+// PackBits, row by row (a run never crosses the end of its row): exactly rows * rowb bytes, or false
+static bool tiff_unpackbits(const uint8_t* s, size_t ns, uint8_t* o, size_t rowb, size_t rows) {
+    size_t p = 0;
+    for (size_t y = 0; y < rows; ++y) {
+        size_t x = 0;
+        while (x < rowb) {
+            if (p >= ns) return false;
+            const int c = (int8_t)s[p++];
+            if (c == -128) continue;
+            const size_t run = c >= 0 ? (size_t)c + 1 : (size_t)(1 - c);
+            if (run > rowb - x) return false;
+            if (c >= 0) {
+                if (run > ns - p) return false;
+                memcpy(o + y * rowb + x, s + p, run);
+                p += run;
+            } else {
+                if (p >= ns) return false;
+                memset(o + y * rowb + x, s[p++], run);
+            }
+            x += run;
+        }
+    }
+    return true;
+}
+
+static bool decode_tiff(const std::vector<uint8_t>& b, Image& im) {
+    mrgingham_amd_tiff_info ti;
+    size_t ns = 0;
+    int rc = tiff_layout(b.data(), b.size(), 0, &ti, nullptr, 0, &ns);
+    if (rc != 0 && rc != kTiffNotTaken) return false;
+    std::vector<mrgingham_amd_tiff_strip> strips(ns);
+    rc = tiff_layout(b.data(), b.size(), 0, &ti, strips.data(), ns, &ns);
+    if (rc != 0 && rc != kTiffNotTaken) return false;
+    const size_t rowb = (size_t)ti.width * ti.samples * (ti.bits / 8), n = (size_t)ti.width * ti.height;
+    im.w = ti.width; im.h = ti.height; im.depth = ti.bits;
+    if (ti.bits == 8) { about_to_hold(im, n, 0); im.px8.resize(n); }
+    else { about_to_hold(im, 0, n); im.px16.resize(n); }
+    std::vector<uint8_t> raw;
+    std::unique_ptr<TiffLzwHostTable> tab;
+    for (const mrgingham_amd_tiff_strip& st : strips) {
+        const uint8_t* src = b.data() + st.offset;
+        const size_t need = rowb * (size_t)st.rows;
+        const uint8_t* rows = src;
+        if (ti.compression != 1) {
+            // (the decoders count in 32 bits: a strip of 4 GiB or more is refused before anything is sized for it)
+            if (need > 0xFFFFFFFFull || (uint64_t)st.nbytes > 0xFFFFFFFFull) return false;
+            raw.resize(need);
+            rows = raw.data();
+            if (ti.compression == 5) {
+                if (!tab) tab.reset(new TiffLzwHostTable);
+                if (tiff_lzw_decode(src, (uint32_t)st.nbytes, raw.data(), (uint32_t)need, *tab) != kTiffLzwOk) return false;
+            } else if (ti.compression == 32773) {
+                if (!tiff_unpackbits(src, (size_t)st.nbytes, raw.data(), rowb, (size_t)st.rows)) return false;
+            } else {
+                uLongf got = (uLongf)need;
+                if (uncompress(raw.data(), &got, src, (uLong)st.nbytes) != Z_OK || got != need) return false;
+            }
+        }
+        for (int y = 0; y < st.rows; ++y) {
+            const size_t row = (size_t)st.first_row + y;
+            if (ti.bits == 8) tiff_finish_row<uint8_t>(rows + rowb * y, ti, &im.px8[row * ti.width]);
+            else tiff_finish_row<uint16_t>(rows + rowb * y, ti, &im.px16[row * ti.width]);
+        }
+    }
+    return true;
+}
+
 // 8-bit binary PGM, the format a calibration run usually feeds the tool: the pixels go from the file straight into
 // px8 -- no copy of the whole file in between (a 12 MB image: one pass over memory less per image).  Returns 1 = done,
 // 0 = not such a file (the general path decides), -1 = such a file, but broken.
@@ -259,15 +472,16 @@ bool read_image(const char* path, Image& im) {
         if (b[0] == 'P' && b[1] == '5') return decode_pgm(b, im);
         if (b[0] == 0x89 && b[1] == 'P') return decode_png(b, im);
         if (b[0] == 0xFF && b[1] == 0xD8) return decode_jpeg(b, im);
+        if ((b[0] == 'I' && b[1] == 'I') || (b[0] == 'M' && b[1] == 'M')) return decode_tiff(b, im);
         return false;
     } catch (...) {  // std::bad_alloc / length_error on a file that claims more than can be held
         return false;
     }
 }
 
-// The header checks of decode_pgm / read_pgm8_direct, decode_png and decode_jpeg without the decoding.  PGM and PNG keep
-// what they need in front: only the first kProbeBytes of such a file are read (a PGM whose comments push the header
-// beyond them is read whole); a JPEG is read whole, its tables may lie anywhere before SOS.
+// The header checks of decode_pgm / read_pgm8_direct, decode_png, decode_jpeg and decode_tiff without the decoding.  PGM
+// and PNG keep what they need in front: only the first kProbeBytes of such a file are read (a PGM whose comments push the
+// header beyond them is read whole); a JPEG is read whole, its tables may lie anywhere before SOS, and so is a TIFF.
 bool probe_image(const char* path, int* width, int* height, int* bits, int* kind) {
     constexpr size_t kProbeBytes = 4096;
     if (!path) return false;
@@ -315,6 +529,15 @@ bool probe_image(const char* path, int* width, int* height, int* bits, int* kind
             JpegInfo info;
             ok = ok && jpeg_coefficients(b.data(), b.size(), nullptr, 0, 0, &info) == 0;
             w = info.width; h = info.height; d = 8;
+        } else if (ok && ((b[0] == 'I' && b[1] == 'I') || (b[0] == 'M' && b[1] == 'M'))) {
+            k = 4;
+            ok = b.size() == (size_t)size || rest();  // (the IFD may lie anywhere, behind the strips as well)
+            mrgingham_amd_tiff_info ti{};
+            if (ok) {
+                const int rc = tiff_layout(b.data(), b.size(), 0, &ti, nullptr, 0, nullptr);
+                ok = rc == 0 || rc == kTiffNotTaken;
+            }
+            w = ti.width; h = ti.height; d = ti.bits;
         } else {
             ok = false;
         }
@@ -384,6 +607,11 @@ void to_8bit(const Image& im, std::vector<uint8_t>& out) {
 
 extern "C" int mrgingham_amd_pgm_header(const uint8_t* data, size_t nbytes, int* width, int* height, int* bits, size_t* payload_offset) {
     return mrg::pgm_header(data, nbytes, width, height, bits, payload_offset);
+}
+
+extern "C" int mrgingham_amd_tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info,
+                                         mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips) {
+    return mrg::tiff_layout(data, nbytes, lzw_max_strip, info, strips, capacity, nstrips);
 }
 
 extern "C" int mrgingham_amd_png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan_capacity, int* width,

@@ -1,5 +1,6 @@
 // What the file-list loaders share (mrgingham_amd_read_jpegs_batch in jpeg_idct.hip, its device-entropy route in
-// jpeg_huff.hip, mrgingham_amd_read_pngs_batch in png_recon.hip): the check of their descriptor, the zeroing of a failed
+// jpeg_huff.hip, mrgingham_amd_read_pngs_batch in png_recon.hip, _read_pgms_batch in pgm_unpack.hip, _read_tiffs_batch in
+// tiff_decode.hip): the check of their descriptor, the zeroing of a failed
 // file's frame and the two-slot chunk ring, of which each loader is a stage.  Host code only; the chunk size is loader.h.
 #include "ctx.h"
 

@@ -1,0 +1,467 @@
+// TIFF on the device: the LZW strips of a batch of files decoded one lane per strip (tiff_lzw.h, the host decoder's text),
+// the rows put into value order, predictor 2 undone and the samples reduced to grey, and the batch loader that reads the
+// files straight into page-locked staging.  See include/mrgingham_amd.h for the contract of the entry points and
+// DESIGN.md section 4.14 for the schedule and the numbers.
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "ctx.h"
+#include "image_io.h"
+#include "loader.h"
+#include "png_filter.h"
+#include "tiff_lzw.h"
+
+using namespace mrg;
+
+namespace {
+
+// ---- the schedule (mrgingham_amd_tiff_geometry)
+// LZW: at most kLzwLanes lanes in flight, whatever the batch: strip s is lane s % lanes' k-th.  Every lane has a table of
+// 4096 dwords in context scratch, interleaved by lane: kLzwLanes x 16 KiB = 256 MiB bounds the table scratch.
+constexpr int kLzwLanes = 16384;
+constexpr int kLzwBlock = 64;      // one wave per workgroup: a wave runs as long as its longest strip, a workgroup no longer
+static_assert((size_t)kLzwLanes * kTiffLzwCodes * sizeof(uint32_t) == (size_t)256 << 20, "the table scratch bound stated in the header");
+// finish: a wave per row, a lane per kSegPx pixels of it, kStepPx pixels per step of the wave
+constexpr int kSegPx = 16;
+constexpr int kWave = 64;
+constexpr int kStepPx = kSegPx * kWave;
+constexpr int kFinishBlock = 256;
+
+// One lane per strip slot (frame * strips_pitch + index), behind a memset of `status`: the strip table of every frame against
+// what the two kernels below rely on -- strips in row order, rps = the first strip's rows each (the last one the rest),
+// every strip inside its file's area, an uncompressed strip long enough for its rows, an LZW strip decoding to at most
+// 1 MiB.  A lane that finds a fault in its frame's counts or in its own strip stores -1 into status[f] (every such lane
+// the same value): the frame is zero-filled.
+__global__ void tiff_check_kernel(const mrgingham_amd_tiff_strip* strips, int strips_pitch, const int32_t* nstrips, int nframes,
+                                  int height, uint32_t rowb, long long file_pitch, int lzw, int32_t* status) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= (long long)nframes * strips_pitch) return;
+    const int f = (int)(s / strips_pitch), i = (int)(s - (long long)f * strips_pitch);
+    const mrgingham_amd_tiff_strip* t = strips + (long long)f * strips_pitch;
+    const int ns = nstrips[f];
+    bool ok = ns >= 1 && ns <= strips_pitch;
+    if (ok) {
+        const int rps = t[0].rows;
+        ok = rps >= 1 && rps <= height && (long long)(ns - 1) * rps < height && (long long)ns * rps >= height;
+        if (ok && i < ns) {
+            const int first = i * rps, rows = height - first < rps ? height - first : rps;
+            const unsigned long long need = (unsigned long long)rows * rowb;
+            ok = t[i].first_row == first && t[i].rows == rows && t[i].offset >= 0 && t[i].nbytes >= 0 && t[i].offset <= file_pitch &&
+                 t[i].nbytes <= file_pitch - t[i].offset && t[i].nbytes <= 0xFFFFFFFFll &&
+                 (lzw ? need <= kTiffLzwMaxStrip20 : (unsigned long long)t[i].nbytes >= need);
+        }
+    }
+    if (!ok) status[f] = -1;
+}
+
+// One lane per strip, lanes looping over the strips of the batch (strip slot s = frame * strips_pitch + index).  A lane
+// reads src[0, nbytes) of its strip and writes the rows x rowb bytes of its strip in `raw` (frame f at raw + f*raw_pitch,
+// rows dense): both bounds are arguments of tiff_lzw_decode and were checked against the file's area and the frame by
+// tiff_check_kernel.  A rule broken: the lane stops, leaves the reason in strip_status and -1 in status[f].
+__global__ __launch_bounds__(kLzwBlock) void tiff_lzw_kernel(const uint8_t* files, long long file_pitch,
+                                                             const mrgingham_amd_tiff_strip* strips, int strips_pitch,
+                                                             const int32_t* nstrips, int nframes, uint32_t rowb, uint8_t* raw,
+                                                             long long raw_pitch, uint32_t* table, int32_t* status,
+                                                             int32_t* strip_status, int32_t* broken) {
+    const uint32_t lanes = gridDim.x * blockDim.x, lane = blockIdx.x * blockDim.x + threadIdx.x;
+    TiffLzwPackedTable tab{table + lane, lanes};
+    const long long total = (long long)nframes * strips_pitch;
+    for (long long s = lane; s < total; s += lanes) {
+        const int f = (int)(s / strips_pitch), i = (int)(s - (long long)f * strips_pitch);
+        int rc = 0;
+        if (status[f] == 0 && i < nstrips[f]) {  // (status: only tiff_check_kernel's verdict is read here; lanes write `broken`)
+            const mrgingham_amd_tiff_strip st = strips[s];
+            rc = tiff_lzw_decode(files + f * file_pitch + st.offset, (uint32_t)st.nbytes, raw + f * raw_pitch + (long long)st.first_row * rowb,
+                                 (uint32_t)st.rows * rowb, tab);
+            if (rc) broken[f] = 1;
+        }
+        if (strip_status) strip_status[s] = rc;
+    }
+}
+
+// behind the LZW launch: a frame with a broken strip gets status -1
+__global__ void tiff_verdict_kernel(const int32_t* broken, int nframes, int32_t* status) {
+    const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (f < nframes && broken[f]) status[f] = -1;
+}
+
+__device__ inline uint32_t load_dword(const uint8_t* __restrict__ src, long long off, long long limit) {
+    if (off + 4 <= limit) return *(const uint32_t*)(src + off);
+    uint32_t v = 0;  // the last dword of the last frame may end behind the buffer: its bytes one by one
+    for (int i = 0; i < 4; ++i)
+        if (off + i < limit) v |= (uint32_t)src[off + i] << (8 * i);
+    return v;
+}
+
+__device__ inline uint32_t byte_of(const uint32_t* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 255u; }
+
+// A grid-stride loop of waves over the rows of all frames.  The bytes of row y of frame f lie at `src` + f*src_pitch +
+// y*rowb (from_raw: the LZW launch's output) or inside the strip that holds the row (the file's own bytes, at any byte
+// address).  Lane l of the wave takes pixels [x0 + 16 l, x0 + 16 l + 16) of the step that begins at x0: it loads the
+// aligned dwords that cover them (guarded by `limit`, the end of the buffer), puts 16-bit samples into value order and,
+// for predictor 2, sums them up per channel; the sums of the lanes to its left come from a shuffle scan over the wave, the
+// sums of the steps before from `carry` -- a prefix sum modulo 2^BITS, exact in any order.  Then WhiteIsZero is inverted,
+// and the first sample or png_grey of the first three is stored: 16 samples in one or two 16-byte stores where the
+// address allows it, sample by sample at a row's unaligned head and tail.  A frame whose status is not 0 is zero-filled.
+template <int BITS, int SPP>
+__global__ __launch_bounds__(kFinishBlock) void tiff_finish_kernel(const uint8_t* __restrict__ src, long long src_pitch, long long limit,
+                                                                   const mrgingham_amd_tiff_strip* __restrict__ strips, int strips_pitch,
+                                                                   int from_raw, int width, int height, long long nrows, int rgb,
+                                                                   int invert, int predictor2, int big_endian, void* __restrict__ out,
+                                                                   long long frame_pitch, int stride, const int32_t* __restrict__ status) {
+    constexpr int ES = BITS / 8, BPP = SPP * ES, NC = SPP >= 3 ? 3 : 1, SEGB = kSegPx * BPP, ND = SEGB / 4;
+    constexpr uint32_t MASK = BITS == 8 ? 255u : 65535u;
+    const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x / kWave;
+    const long long nwaves = (long long)gridDim.x * (kFinishBlock / kWave), rowb = (long long)width * BPP;
+    for (long long row = (long long)blockIdx.x * (kFinishBlock / kWave) + wave; row < nrows; row += nwaves) {
+        const long long f = row / height;
+        const int y = (int)(row - f * height);
+        const bool dead = status[f] != 0;
+        long long row_off = f * src_pitch + (long long)y * rowb;
+        if (!from_raw && !dead) {  // (tiff_check_kernel: strip i holds rows [i*rps, i*rps + rows), all of them inside the file's area)
+            const mrgingham_amd_tiff_strip* t = strips + f * strips_pitch;
+            const int i = y / t[0].rows;
+            row_off = f * src_pitch + t[i].offset + (long long)(y - t[i].first_row) * rowb;
+        }
+        uint32_t carry[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) carry[c] = 0;
+        for (int x0 = 0; x0 < width; x0 += kStepPx) {
+            const int xs = x0 + lane * kSegPx, nx = width - xs;
+            uint32_t v[kSegPx][NC], acc[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) acc[c] = 0;
+            if (!dead && nx > 0) {
+                const long long first = row_off + (long long)xs * BPP, first4 = first & ~3ll;
+                const int shift = 8 * (int)(first & 3);
+                uint32_t w[ND + 1], in[ND];
+#pragma unroll
+                for (int i = 0; i <= ND; ++i) w[i] = load_dword(src, first4 + 4 * i, limit);
+#pragma unroll
+                for (int i = 0; i < ND; ++i) in[i] = (uint32_t)(((((unsigned long long)w[i + 1]) << 32) | w[i]) >> shift);
+#pragma unroll
+                for (int p = 0; p < kSegPx; ++p) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        const int b = (p * SPP + c) * ES;
+                        uint32_t s;
+                        if constexpr (BITS == 8) s = byte_of(in, b);
+                        else s = big_endian ? byte_of(in, b) << 8 | byte_of(in, b + 1) : byte_of(in, b + 1) << 8 | byte_of(in, b);
+                        // (pixels behind the row's end are computed from whatever follows and never stored: they sit in the
+                        // row's last lane, to the right of everything their sums could reach)
+                        if (predictor2) s = acc[c] += s;
+                        v[p][c] = s;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < kSegPx; ++p)
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) v[p][c] = 0;
+            }
+            if (predictor2) {  // (uniform over the wave)
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    uint32_t t = nx > 0 ? acc[c] : 0;
+                    const uint32_t own = t;
+#pragma unroll
+                    for (int d = 1; d < kWave; d <<= 1) {
+                        const uint32_t u = __shfl_up(t, d, kWave);
+                        if (lane >= d) t += u;
+                    }
+                    const uint32_t before = t - own + carry[c];
+                    carry[c] += __shfl(t, kWave - 1, kWave);
+#pragma unroll
+                    for (int p = 0; p < kSegPx; ++p) v[p][c] += before;
+                }
+            }
+            if (nx <= 0) continue;
+            uint32_t grey[kSegPx];
+#pragma unroll
+            for (int p = 0; p < kSegPx; ++p) {
+                uint32_t q[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    q[c] = v[p][c] & MASK;
+                    if (invert) q[c] = MASK - q[c];
+                }
+                uint32_t g = q[0];
+                if constexpr (NC == 3) {
+                    if (rgb) g = png_grey(q[0], q[1], q[2]);
+                }
+                grey[p] = dead ? 0u : g;
+            }
+            if (BITS == 8) {
+                uint8_t* o = (uint8_t*)out + f * frame_pitch + (long long)y * stride + xs;
+                if (nx >= kSegPx && ((uintptr_t)o & 15) == 0) {
+                    uint32_t d[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) d[i] = grey[4 * i] | grey[4 * i + 1] << 8 | grey[4 * i + 2] << 16 | grey[4 * i + 3] << 24;
+                    *(uint4*)o = make_uint4(d[0], d[1], d[2], d[3]);
+                } else {
+#pragma unroll
+                    for (int p = 0; p < kSegPx; ++p)
+                        if (p < nx) o[p] = (uint8_t)grey[p];
+                }
+            } else {
+                uint16_t* o = (uint16_t*)out + f * frame_pitch + (long long)y * stride + xs;
+                if (nx >= kSegPx && ((uintptr_t)o & 15) == 0) {
+                    uint32_t d[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) d[i] = (grey[2 * i] & 0xFFFFu) | grey[2 * i + 1] << 16;
+                    *(uint4*)o = make_uint4(d[0], d[1], d[2], d[3]);
+                    *(uint4*)(o + 8) = make_uint4(d[4], d[5], d[6], d[7]);
+                } else {
+#pragma unroll
+                    for (int p = 0; p < kSegPx; ++p)
+                        if (p < nx) o[p] = (uint16_t)grey[p];
+                }
+            }
+        }
+    }
+}
+
+bool tiff_info_ok(const mrgingham_amd_tiff_info& t) {
+    return t.width >= 1 && t.height >= 1 && t.width <= 32767 && t.height <= 32767 && (t.bits == 8 || t.bits == 16) && t.samples >= 1 &&
+           t.samples <= 4 && t.photometric >= 0 && t.photometric <= 2 && (t.photometric != 2 || t.samples >= 3) &&
+           (t.compression == 1 || t.compression == 5) && (t.predictor == 1 || t.predictor == 2) && (t.big_endian == 0 || t.big_endian == 1);
+}
+
+int lzw_lanes_of(const mrgingham_amd_ctx* ctx) { return ctx->tiff_lzw_lanes > 0 ? ctx->tiff_lzw_lanes : kLzwLanes; }
+
+// checked arguments -> the launches; grows the LZW scratch
+int launch_tiff_decode(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch, const mrgingham_amd_tiff_strip* d_strips,
+                       int strips_pitch, const int32_t* d_nstrips, int nframes, const mrgingham_amd_tiff_info& ti, void* d_out,
+                       int64_t frame_pitch, int stride, int32_t* d_status, int32_t* d_strip_status, hipStream_t s) {
+    const int width = ti.width, height = ti.height, bpp = ti.samples * ti.bits / 8;
+    const uint32_t rowb = (uint32_t)width * bpp;
+    const bool lzw = ti.compression == 5;
+    const unsigned frame_blocks = (unsigned)((nframes + 63) / 64);
+    const long long slots = (long long)nframes * strips_pitch;
+    MRG_HIP_CHECK(hipMemsetAsync(d_status, 0, (size_t)nframes * sizeof(int32_t), s));
+    hipLaunchKernelGGL(tiff_check_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, d_strips, strips_pitch, d_nstrips, nframes, height,
+                       rowb, (long long)file_pitch, lzw ? 1 : 0, d_status);
+    const uint8_t* src = d_files;
+    long long src_pitch = file_pitch;
+    if (lzw) {
+        const long long raw_pitch = ((long long)rowb * height + 15) & ~15ll;
+        long long lanes = (slots + kLzwBlock - 1) / kLzwBlock * kLzwBlock;
+        if (lanes > lzw_lanes_of(ctx)) lanes = lzw_lanes_of(ctx);
+        int rc;
+        if ((rc = ensure(ctx, ctx->tiff_raw, (size_t)nframes * (size_t)raw_pitch))) return rc;
+        if ((rc = ensure(ctx, ctx->tiff_table, (size_t)lanes * kTiffLzwCodes * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure(ctx, ctx->tiff_broken, (size_t)nframes * sizeof(int32_t)))) return rc;
+        MRG_HIP_CHECK(hipMemsetAsync(ctx->tiff_broken.p, 0, (size_t)nframes * sizeof(int32_t), s));
+        hipLaunchKernelGGL(tiff_lzw_kernel, dim3((unsigned)(lanes / kLzwBlock)), dim3(kLzwBlock), 0, s, d_files, (long long)file_pitch, d_strips,
+                           strips_pitch, d_nstrips, nframes, rowb, (uint8_t*)ctx->tiff_raw.p, raw_pitch, (uint32_t*)ctx->tiff_table.p, d_status,
+                           d_strip_status, (int32_t*)ctx->tiff_broken.p);
+        hipLaunchKernelGGL(tiff_verdict_kernel, dim3(frame_blocks), dim3(64), 0, s, (const int32_t*)ctx->tiff_broken.p, nframes, d_status);
+        src = (const uint8_t*)ctx->tiff_raw.p;
+        src_pitch = raw_pitch;
+    }
+    const long long nrows = (long long)nframes * height, limit = (long long)nframes * src_pitch;
+    int cus = 0;
+    MRG_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    // sized to the device: eight workgroups of 256 lanes fill a CU
+    long long blocks = (nrows + kFinishBlock / kWave - 1) / (kFinishBlock / kWave);
+    if (blocks > (long long)cus * 8) blocks = (long long)cus * 8;
+#define MRG_TIFF_CASE(B, C)                                                                                                              \
+    hipLaunchKernelGGL((tiff_finish_kernel<B, C>), dim3((unsigned)blocks), dim3(kFinishBlock), 0, s, src, src_pitch, limit, d_strips,      \
+                       strips_pitch, lzw ? 1 : 0, width, height, nrows, ti.photometric == 2 ? 1 : 0, ti.photometric == 0 ? 1 : 0,           \
+                       ti.predictor == 2 ? 1 : 0, ti.big_endian, d_out, (long long)frame_pitch, stride, (const int32_t*)d_status)
+    const int ch = ti.samples;
+    if (ti.bits == 8) {
+        if (ch == 1) MRG_TIFF_CASE(8, 1); else if (ch == 2) MRG_TIFF_CASE(8, 2); else if (ch == 3) MRG_TIFF_CASE(8, 3); else MRG_TIFF_CASE(8, 4);
+    } else {
+        if (ch == 1) MRG_TIFF_CASE(16, 1); else if (ch == 2) MRG_TIFF_CASE(16, 2); else if (ch == 3) MRG_TIFF_CASE(16, 3); else MRG_TIFF_CASE(16, 4);
+    }
+#undef MRG_TIFF_CASE
+    MRG_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// what makes two files of a chunk share a launch
+uint32_t launch_key(const mrgingham_amd_tiff_info& t) {
+    return (uint32_t)t.samples | (uint32_t)t.photometric << 4 | (uint32_t)(t.compression == 5) << 8 | (uint32_t)t.predictor << 12 |
+           (uint32_t)t.big_endian << 16;
+}
+
+}  // namespace
+
+extern "C" {
+
+void mrgingham_amd_tiff_geometry(int* lzw_lanes, int* segment_pixels, int* step_pixels) {
+    if (lzw_lanes) *lzw_lanes = kLzwLanes;
+    if (segment_pixels) *segment_pixels = kSegPx;
+    if (step_pixels) *step_pixels = kStepPx;
+}
+
+int mrgingham_amd_tiff_decode_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch,
+                                    const mrgingham_amd_tiff_strip* d_strips, int strips_pitch, const int32_t* d_nstrips, int nframes,
+                                    const mrgingham_amd_tiff_info* info, void* d_out, int64_t frame_pitch, int stride, int32_t* d_status,
+                                    int32_t* d_strip_status, void* stream) {
+    if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
+    if (!info || nframes < 0 || strips_pitch < 1 || frame_pitch < 0 || file_pitch < 0 ||
+        (nframes > 0 && (!d_files || !d_strips || !d_nstrips || !d_out || !d_status)))
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad TIFF batch descriptor");
+    if (!tiff_info_ok(*info) || stride < info->width)
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "TIFF batch: sides 1..32767, 8 or 16 bits, 1..4 samples, photometric 0..2, compression 1 or 5, predictor 1 or 2, stride >= width");
+    if ((file_pitch & 15) || ((uintptr_t)d_files & 15) || ((uintptr_t)d_strips & 7) || ((uintptr_t)d_nstrips & 3) || ((uintptr_t)d_status & 3) ||
+        ((uintptr_t)d_strip_status & 3) || (info->bits == 16 && ((uintptr_t)d_out & 1)))
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "TIFF batch: files 16-byte aligned, file_pitch a multiple of 16; 16-bit frames 2-byte aligned");
+    if (nframes == 0) return 0;
+    MRG_HIP_CHECK(hipSetDevice(ctx->device));
+    return launch_tiff_decode(ctx, d_files, file_pitch, d_strips, strips_pitch, d_nstrips, nframes, *info, d_out, frame_pitch, stride, d_status,
+                              d_strip_status, (hipStream_t)stream);  // (the stream used as given: NULL is HIP's default stream)
+}
+
+int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height, int bits,
+                                   void* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status) {
+    const size_t es = bits == 8 ? 1 : bits == 16 ? 2 : 0;
+    int rc = check_file_batch(ctx, "TIFF", filenames, nfiles, width, height, es, d_out, frame_pitch, stride, h_status);
+    if (rc) return rc;
+    if (nfiles == 0) return 0;
+    fb_drain(ctx);
+    const CallerDevice caller_device_;
+    MRG_HIP_CHECK(hipSetDevice(ctx->device));
+    nthreads = host_threads(nthreads);
+    uint8_t* const out = (uint8_t*)d_out;
+
+    // Every file of a chunk gets ONE area of the staging: the largest file of the list, or the decoded samples where those
+    // are more (a file the host decodes leaves them there).  A file much larger than the samples of a frame of four
+    // channels -- hardly a TIFF of this size -- does not size the areas: it keeps the host decoder.
+    const size_t px_bytes = (size_t)width * height * es;
+    const size_t file_limit = 4 * px_bytes + 16 * (size_t)height + 65536;
+    std::vector<size_t> fsize((size_t)nfiles, 0);
+    for_files(ctx->pool, nthreads, nfiles, [&](int i) {
+        FILE* f = fopen(filenames[i], "rb");
+        if (!f) return;
+        if (fseek(f, 0, SEEK_END) == 0) {
+            const long n = ftell(f);
+            if (n > 0) fsize[(size_t)i] = (size_t)n;
+        }
+        fclose(f);
+    });
+    size_t largest = px_bytes;
+    for (size_t n : fsize)
+        if (n <= file_limit && n > largest) largest = n;
+    const size_t area = (largest + 15) & ~(size_t)15;
+    const size_t per_file = area + (size_t)height * sizeof(mrgingham_amd_tiff_strip) + 2 * sizeof(int32_t);
+    const int chunk = loader_chunk_frames(ctx->jpeg_coef_budget, per_file, nfiles, nthreads, ctx->tiff_chunk_frames);
+    // a slot, page-locked and on the device alike: the files' areas | their strip tables, `height` records each | their
+    // strip counts | (device -> host) their status words
+    const size_t off_strips = (size_t)chunk * area, off_ns = off_strips + (size_t)chunk * height * sizeof(mrgingham_amd_tiff_strip),
+                 off_status = off_ns + (size_t)chunk * sizeof(int32_t), slot_bytes = off_status + (size_t)chunk * sizeof(int32_t);
+    hipStream_t s = ctx->pix;
+    const int64_t max_strip = ctx->tiff_lzw_max_strip;
+    // per slot and file of its chunk: -1 failed, 0 decoded on the host (its samples lie in its area), 1 the device's
+    struct InSlot { int f0 = 0, n = 0; std::vector<int> kind; std::vector<mrgingham_amd_tiff_info> info; } in_slot[2];
+    struct Buffers { std::vector<uint8_t> file; Image im; };
+    auto stage = [&](int k, int f0, int n) -> int {
+        uint8_t* const pin = (uint8_t*)ctx->loader_slot[k].pin.p;
+        mrgingham_amd_tiff_strip* const h_strips = (mrgingham_amd_tiff_strip*)(pin + off_strips);
+        int32_t* const h_ns = (int32_t*)(pin + off_ns);
+        InSlot& S = in_slot[k];
+        S.f0 = f0; S.n = n;
+        S.kind.assign((size_t)n, -1);
+        S.info.assign((size_t)n, mrgingham_amd_tiff_info{});
+        for_files<Buffers>(ctx->pool, nthreads, n, [&](int i, Buffers& t) {
+            int32_t st = -1;
+            int kind = -1;
+            uint8_t* dst = pin + (size_t)i * area;
+            mrgingham_amd_tiff_info ti{};
+            size_t ns = 0;
+            h_ns[i] = 0;
+            try {
+                int head = -1;
+                bool staged = false;
+                FILE* f = fopen(filenames[f0 + i], "rb");
+                if (f) {
+                    // the file straight into its area (one that has grown since it was measured, or is too large: the host's)
+                    const size_t got = fread(dst, 1, area, f);
+                    const bool whole = got < area || fgetc(f) == EOF;
+                    fclose(f);
+                    if (whole) {
+                        staged = true;
+                        head = tiff_layout(dst, got, max_strip, &ti, h_strips + (size_t)i * height, (size_t)height, &ns);
+                    } else if (read_file(filenames[f0 + i], t.file)) {
+                        head = tiff_layout(t.file.data(), t.file.size(), max_strip, &ti, nullptr, 0, &ns);
+                        if (head == 0) head = kTiffNotTaken;
+                    }
+                }
+                // (-2: more strips than rows of THIS batch's frames -- a file of another height)
+                if (head == 0 || head == kTiffNotTaken || head == -2) {
+                    if (ti.width != width || ti.height != height || ti.bits != bits) st = -2;
+                    else if (head == 0 && staged) {
+                        h_ns[i] = (int32_t)ns;
+                        kind = 1;
+                        st = 0;  // (an LZW strip may still break a rule: known when the chunk has passed the stream)
+                    } else if (head != -2 && read_image(filenames[f0 + i], t.im) && t.im.depth == bits && t.im.w == width && t.im.h == height) {
+                        // the device route does not take it: the host decoder's samples
+                        memcpy(dst, bits == 8 ? (const void*)t.im.px8.data() : (const void*)t.im.px16.data(), px_bytes);
+                        kind = 0;
+                        st = 0;
+                    }
+                }
+            } catch (...) {  // std::bad_alloc on a file too large to hold
+                st = -1;
+                kind = -1;
+            }
+            S.kind[(size_t)i] = kind;
+            S.info[(size_t)i] = ti;
+            h_status[f0 + i] = st;
+        });
+        // The host threads wrote file i's records at a pitch of `height`, the most a file can have.  The launches get a dense
+        // table: the records moved down to a pitch of the chunk's largest strip count (i * P <= i * height: ascending i never
+        // overwrites what is still to move), so that the lanes of the LZW launch, which take slot after slot, meet no runs of
+        // empty slots -- a pitch of `height` would leave most lanes idle and stack the strips on the others.
+        int P = 1;
+        for (int i = 0; i < n; ++i)
+            if (h_ns[i] > P) P = h_ns[i];
+        for (int i = 1; i < n && P < height; ++i)
+            if (h_ns[i] > 0) memmove(h_strips + (size_t)i * P, h_strips + (size_t)i * height, (size_t)h_ns[i] * sizeof(mrgingham_amd_tiff_strip));
+        // three uploads (areas; tables; counts), one launch sequence per run of files of one kind and one set of fields
+        uint8_t* const dev = (uint8_t*)ctx->loader_slot[k].dev.p;
+        MRG_HIP_CHECK(hipMemcpyAsync(dev, pin, (size_t)n * area, hipMemcpyHostToDevice, s));
+        MRG_HIP_CHECK(hipMemcpyAsync(dev + off_strips, pin + off_strips, (size_t)n * P * sizeof(mrgingham_amd_tiff_strip), hipMemcpyHostToDevice, s));
+        MRG_HIP_CHECK(hipMemcpyAsync(dev + off_ns, pin + off_ns, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        MRG_HIP_CHECK(hipMemsetAsync(dev + off_status, 0, (size_t)n * sizeof(int32_t), s));
+        auto same = [&](int a, int b) {
+            return S.kind[(size_t)a] == S.kind[(size_t)b] && (S.kind[(size_t)a] != 1 || launch_key(S.info[(size_t)a]) == launch_key(S.info[(size_t)b]));
+        };
+        for (int i = 0; i < n;) {
+            int e = i + 1;
+            while (e < n && same(i, e)) ++e;
+            if (S.kind[(size_t)i] == 1) {
+                int lrc;
+                if ((lrc = launch_tiff_decode(ctx, dev + (size_t)i * area, (int64_t)area, (const mrgingham_amd_tiff_strip*)(dev + off_strips) + (size_t)i * P,
+                                              P, (const int32_t*)(dev + off_ns) + i, e - i, S.info[(size_t)i],
+                                              out + (size_t)(f0 + i) * frame_pitch * es, frame_pitch, stride, (int32_t*)(dev + off_status) + i, nullptr, s)))
+                    return lrc;
+            } else if (S.kind[(size_t)i] == 0) {
+                for (int q = i; q < e; ++q)
+                    MRG_HIP_CHECK(hipMemcpy2DAsync(out + (size_t)(f0 + q) * frame_pitch * es, (size_t)stride * es, dev + (size_t)q * area,
+                                                   (size_t)width * es, (size_t)width * es, (size_t)height, hipMemcpyDeviceToDevice, s));
+            } else {
+                for (int q = i; q < e; ++q) MRG_HIP_CHECK(zero_frame(d_out, f0 + q, frame_pitch, stride, width, height, es, s));
+            }
+            i = e;
+        }
+        MRG_HIP_CHECK(hipMemcpyAsync(pin + off_status, dev + off_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        return 0;
+    };
+    // the chunk has passed the stream: the verdicts of the device's files (their frames are zero-filled already)
+    auto finish = [&](int k) -> int {
+        const InSlot& S = in_slot[k];
+        const int32_t* st = (const int32_t*)((const uint8_t*)ctx->loader_slot[k].pin.p + off_status);
+        for (int i = 0; i < S.n; ++i)
+            if (S.kind[(size_t)i] == 1 && st[i] != 0) h_status[S.f0 + i] = -1;
+        return 0;
+    };
+    // the chunk slots are shared with the JPEG, PNG and PGM loaders (ctx.h: loader_slot)
+    return loader_ring(ctx, nfiles, chunk, slot_bytes, slot_bytes, stage, nullptr, finish);
+}
+
+}  // extern "C"

@@ -1,0 +1,170 @@
+"""What the TIFF device route (tiff_decode.hip, mrgingham_amd_read_tiffs_batch) costs and buys at 12 MP:
+
+    python tools/tiff_bench.py [--rounds 3] [--jobs 16] [--frames 64] [--out profiles/tiff_bench.json]
+
+Files: two 4096x3072 frames (synth.board_frame plus noise), 8 bit and 16 bit, written by Pillow's libtiff into a RAM-backed
+directory -- LZW with predictor 2 at 2, 16 and 256 rows per strip (8 KiB, 64 KiB and 1 MiB decoded per strip at 8 bit) and
+uncompressed.
+1. The launches alone: `--frames` files uploaded once, mrgingham_amd_tiff_decode_batch between two device events (two
+   warm-up calls, the median of ten), its output checked against the source array.  On an LZW file that is the check
+   kernel, the LZW kernel (one lane per strip) and the finish kernel; on the same pixels uncompressed it is the check and
+   the finish kernel alone, so the difference prices the LZW launch.  For the finish kernel the bytes its algorithm moves
+   -- one read of rowbytes x height and one write of width x height x bits / 8 per frame -- and the fraction of the HBM
+   peak (8.0 TB/s) that is.  The three strip sizes are the sweep behind option "tiff_lzw_max_strip".
+2. The loader: `--frames` names over the two files through Detector.read_tiffs with `--jobs` host threads, at every strip
+   size of the sweep: the device route (option "tiff_lzw_max_strip" at its limit, 1 MiB, so that every file is taken)
+   against the same call with every file forced to the host decoder (the option at 1), alternating, `--rounds` times in
+   one process; frames per second of wall time.  These pairs are what the option's default is read from.
+One JSON document."""
+import ctypes
+import json
+import os
+import shutil
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK = 8.0e12
+W, H = 4096, 3072
+
+
+def opts(args, name, default=None):
+    return args[args.index(name) + 1] if name in args else default
+
+
+def board(seed, bits):
+    from mrgingham_amd import synth
+    rng = np.random.default_rng(seed)
+    grey = synth.board_frame(W, H, 10, seed=seed).numpy().astype(np.int32)
+    img = np.clip(grey + rng.integers(-3, 4, grey.shape), 0, 255)
+    return img.astype(np.uint8) if bits == 8 else (img * 257 + rng.integers(0, 64, grey.shape)).astype(np.uint16)
+
+
+def write_files(scratch):
+    from PIL import Image
+    files, source = {}, {}
+    for bits in (8, 16):
+        for seed in (1, 2):
+            img = board(seed, bits)
+            source[bits, seed] = img
+            for name, kw in (("lzw_rows2", dict(compression="tiff_lzw", tiffinfo={317: 2, 278: 2})),
+                             ("lzw_rows16", dict(compression="tiff_lzw", tiffinfo={317: 2, 278: 16})),
+                             ("lzw_rows256", dict(compression="tiff_lzw", tiffinfo={317: 2, 278: 256})),
+                             ("none", dict(tiffinfo={278: 2}))):
+                if bits == 16 and name in ("lzw_rows16", "lzw_rows256"):
+                    continue
+                if bits == 16 and name == "lzw_rows2":
+                    kw = dict(compression="tiff_lzw", tiffinfo={317: 2, 278: 1})     # 8 KiB decoded per strip at 16 bit
+                p = os.path.join(scratch, f"b{bits}_{name}_{seed}.tif")
+                Image.fromarray(img).save(p, "TIFF", **kw)
+                files[bits, name, seed] = p
+    return files, source
+
+
+def launch_ms(det, datas, want, frames):
+    """decode_batch over `frames` copies of the files, uploaded once: median ms of ten calls."""
+    import torch
+    import mrgingham_amd
+    from mrgingham_amd import _lib, api
+    lays = [mrgingham_amd.tiff_layout(d) for d in datas]
+    assert all(l is not None and l.taken for l in lays) and len({l.key() for l in lays}) == 1
+    lay, P = lays[0], max(l.nstrips for l in lays)
+    pitch = (max(len(d) for d in datas) + 15) // 16 * 16
+    h_files = np.zeros((frames, pitch), np.uint8)
+    h_strips = np.zeros((frames, P), api.TIFF_STRIP)
+    for i in range(frames):
+        d, l = datas[i % len(datas)], lays[i % len(datas)]
+        h_files[i, :len(d)] = np.frombuffer(d, np.uint8)
+        h_strips[i, :l.nstrips] = l.strips
+    d_files = torch.from_numpy(h_files).cuda()
+    d_strips = torch.from_numpy(h_strips.view(np.uint8).reshape(frames, -1)).cuda()
+    d_ns = torch.tensor([lays[i % len(datas)].nstrips for i in range(frames)], dtype=torch.int32, device="cuda")
+    d_status = torch.zeros(frames, dtype=torch.int32, device="cuda")
+    d_out = torch.empty((frames, H, W), dtype=torch.uint8 if lay.bits == 8 else torch.uint16, device="cuda")
+    info = _lib.TiffInfo(*lay.key())
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call():
+        assert det.L.mrgingham_amd_tiff_decode_batch(det.ctx, d_files.data_ptr(), pitch, d_strips.data_ptr(), P, d_ns.data_ptr(), frames,
+                                                     ctypes.byref(info), d_out.data_ptr(), H * W, W, d_status.data_ptr(), None, stream) == 0
+    for _ in range(2):
+        call()
+    torch.cuda.synchronize()
+    assert not d_status.any().item()
+    for i in (0, 1, frames - 1):
+        assert np.array_equal(d_out[i].cpu().numpy(), want[i % len(want)]), "the kernels' output differs from the source"
+    ms = []
+    for _ in range(10):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    rowb = W * lay.samples * lay.bits // 8
+    return {"ms_per_launch": round(statistics.median(ms), 3), "ms_min_max": [round(min(ms), 3), round(max(ms), 3)], "strips_per_frame": P,
+            "decoded_bytes_per_strip": int(lay.strips["rows"][0]) * rowb, "file_bytes": [len(d) for d in datas],
+            "finish_bytes_per_launch": frames * (rowb * H + W * H * lay.bits // 8)}
+
+
+def main(args):
+    import torch
+    import mrgingham_amd
+    rounds, jobs, frames = int(opts(args, "--rounds", "3")), int(opts(args, "--jobs", "16")), int(opts(args, "--frames", "64"))
+    out_path = opts(args, "--out", os.path.join(ROOT, "profiles", "tiff_bench.json"))
+    doc = {"device": torch.cuda.get_device_name(0), "jobs": jobs, "rounds": rounds, "frames": frames, "frame": [W, H],
+           "hbm_peak_bytes_per_s": HBM_PEAK, "geometry_lanes_segment_step": list(mrgingham_amd.tiff_geometry())}
+    scratch = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    det = mrgingham_amd.Detector(0)
+    try:
+        files, source = write_files(scratch)
+        doc["launches"] = {}
+        for bits, name in ((8, "lzw_rows2"), (8, "lzw_rows16"), (8, "lzw_rows256"), (8, "none"), (16, "lzw_rows2"), (16, "none")):
+            datas = [open(files[bits, name, seed], "rb").read() for seed in (1, 2)]
+            r = launch_ms(det, datas, [source[bits, 1], source[bits, 2]], frames)
+            if name == "none":
+                t = r["ms_per_launch"] * 1e-3
+                r["finish_bytes_per_s"] = round(r["finish_bytes_per_launch"] / t)
+                r["finish_fraction_of_hbm_peak"] = round(r["finish_bytes_per_launch"] / t / HBM_PEAK, 4)
+            doc["launches"][f"b{bits}_{name}"] = r
+            print(f"launch b{bits}_{name}: {r['ms_per_launch']} ms per {frames} frames", file=sys.stderr, flush=True)
+        for bits in (8, 16):
+            lz, no = doc["launches"][f"b{bits}_lzw_rows2"], doc["launches"][f"b{bits}_none"]
+            lz["lzw_launch_ms_by_difference"] = round(lz["ms_per_launch"] - no["ms_per_launch"], 3)
+        doc["loader"] = {}
+        for bits, name in ((8, "lzw_rows2"), (8, "lzw_rows16"), (8, "lzw_rows256"), (8, "none"), (16, "lzw_rows2"), (16, "none")):
+            paths = [files[bits, name, 1 + i % 2] for i in range(frames)]
+            legs = {"device": 1 << 20} if name == "none" else {"device": 1 << 20, "host_forced": 1}
+            walls = {leg: [] for leg in legs}
+            for r in range(rounds + 1):               # (round 0 warms the staging up and is dropped)
+                for leg, max_strip in legs.items():
+                    det.set_option("tiff_lzw_max_strip", max_strip)
+                    t0 = time.perf_counter()
+                    fr, status = det.read_tiffs(paths, nthreads=jobs)
+                    wall = time.perf_counter() - t0
+                    assert not status.any() and np.array_equal(fr[1].cpu().numpy(), source[bits, 2])
+                    del fr
+                    if r:
+                        walls[leg].append(wall)
+            det.set_option("tiff_lzw_max_strip", 64 << 10)
+            doc["loader"][f"b{bits}_{name}"] = {leg: {"frames_per_s": round(frames / statistics.median(w), 1),
+                                                      "frames_per_s_rounds": [round(frames / v, 1) for v in w]} for leg, w in walls.items()}
+            print(f"loader b{bits}_{name}: {doc['loader'][f'b{bits}_{name}']}", file=sys.stderr, flush=True)
+    finally:
+        det.close()
+        shutil.rmtree(scratch, ignore_errors=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps(doc, indent=1))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
