@@ -19,11 +19,20 @@
  *     tests/golden/chess_kat.npz holds known-answer vectors produced by that
  *     real reference build (tests/golden/make_golden.py).
  *   - connected components / detect / refine (find_chessboard_corners.cc):
- *     PARITY UNPINNED.  The upstream file needs OpenCV headers, which this
- *     image lacks, and the upstream project holds no test, golden vector or
- *     fixture for this path, so the restatement cannot be
- *     executed against the real thing here.  It follows the upstream logic
- *     statement by statement (citations below).
+ *     PINNED, by the upstream file itself.  oracle/Makefile (target `ref`)
+ *     compiles it unmodified, where it lies, against the stand-in headers of
+ *     oracle/ref_stub (cv::Mat fields and Mat::zeros, no arithmetic) behind
+ *     oracle/ref_harness.cc: oracle/_ref/libfcc_ref.so runs it on images with
+ *     the upstream ChESS.c, oracle/_ref/libfcc_resp_ref.so runs its component
+ *     search on responses the caller builds.  tests/test_oracle_fcc.py checks
+ *     oracle_find_corners, oracle_refine_corners and oracle_cc_*_on_response
+ *     against them for equality (integers, order, levels, counts, the refined
+ *     doubles bit for bit) at levels 0..3, and tests/golden/fcc_kat.npz holds
+ *     upstream's recorded answers (tests/golden/make_fcc_golden.py).
+ *     NOT part of this pin: the resize arithmetic.  Above level 0 the build's
+ *     cv::resize computes nothing and hands upstream the level image the caller
+ *     supplies, so the pin covers the component search and the coordinate
+ *     scaling at every level, and the whole path at level 0 only.
  *   - level decimation (cv::resize INTER_LINEAR) and box blur (cv::blur):
  *     PARITY UNPINNED.  The arithmetic lives in OpenCV (un-vendored, version
  *     unpinned by upstream: "opencv >= 3.2", packaging/mrgingham.spec:12).  The

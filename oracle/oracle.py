@@ -14,6 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "liboracle.so")
 _REF = os.path.join(_HERE, "_ref", "libchess_ref.so")
+_REF_FCC = os.path.join(_HERE, "_ref", "libfcc_ref.so")
+_REF_FCC_RESP = os.path.join(_HERE, "_ref", "libfcc_resp_ref.so")
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _i16p = ctypes.POINTER(ctypes.c_int16)
@@ -27,7 +29,7 @@ def build(force=False):
     if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(
             os.path.getmtime(os.path.join(_HERE, f)) for f in ("mrgingham_oracle.c", "blobs_oracle.c", "cpu_bench.c")):
         subprocess.check_call(["make", "-s", "-C", _HERE, "all"], stdout=sys.stderr)
-    elif not os.path.exists(_REF) and os.path.exists("/root/reference/ChESS.c"):
+    elif not all(os.path.exists(p) for p in (_REF, _REF_FCC, _REF_FCC_RESP)) and os.path.exists("/root/reference/ChESS.c"):
         subprocess.check_call(["make", "-s", "-C", _HERE, "ref"], stdout=sys.stderr)
 
 
@@ -68,6 +70,37 @@ def ref_lib():
         R.mrgingham_ChESS_response_5.restype = None
         _ref = R
     return _ref
+
+
+def have_reference_fcc():
+    """Both builds of the upstream find_chessboard_corners.cc (oracle/Makefile, target `ref`) are present."""
+    return os.path.exists(_REF_FCC) and os.path.exists(_REF_FCC_RESP)
+
+
+_fcc = None
+_fcc_resp = None
+
+
+def _fcc_lib():
+    """The upstream find_chessboard_corners.cc + ChESS.c behind oracle/ref_harness.cc."""
+    global _fcc
+    if _fcc is None:
+        R = ctypes.CDLL(_REF_FCC)
+        R.fcc_ref_detect.argtypes = [_i32p, ctypes.c_int, _u8p] + [ctypes.c_int] * 4 + [_u8p] + [ctypes.c_int] * 2
+        R.fcc_ref_refine.argtypes = [_f64p, _i8p, ctypes.c_int, _u8p] + [ctypes.c_int] * 4 + [_u8p] + [ctypes.c_int] * 2
+        _fcc = R
+    return _fcc
+
+
+def _fcc_resp_lib():
+    """The upstream find_chessboard_corners.cc over a response that the caller supplies."""
+    global _fcc_resp
+    if _fcc_resp is None:
+        R = ctypes.CDLL(_REF_FCC_RESP)
+        R.fcc_ref_cc_detect_on_response.argtypes = [_i32p, ctypes.c_int, _i16p, _u8p] + [ctypes.c_int] * 3
+        R.fcc_ref_cc_refine_on_response.argtypes = [_f64p, _i8p, ctypes.c_int, _i16p, _u8p] + [ctypes.c_int] * 3
+        _fcc_resp = R
+    return _fcc_resp
 
 
 def _img2d(image):
@@ -219,6 +252,97 @@ def cc_refine_on_response(points, levels, resp, level_image, level):
     n = lib().oracle_cc_refine_on_response(pts.ctypes.data_as(_f64p), lv.ctypes.data_as(_i8p), len(lv),
                                            d.ctypes.data_as(_i16p), img.ctypes.data_as(_u8p), w, h, level)
     return pts, lv, n
+
+
+# ---- the upstream find_chessboard_corners.cc itself (oracle/_ref/libfcc_ref.so, libfcc_resp_ref.so) ------------
+# Same signatures and return shapes as the restatement's functions above.  Above level 0 upstream's only OpenCV
+# call is cv::resize, and the reference build's resize computes nothing: it hands upstream the `level_image` given
+# here.  The default is decimate(image, level), this project's restatement of that resize; callers that compare a
+# device result pass the level image the device produced.  So these pin the component search and the scaling at
+# every level, the whole path at level 0, and never the resize arithmetic.
+
+def _level_image(image, level, level_image):
+    if level_image is None:
+        H, W = image.shape
+        if level == 0 or not 0 <= level <= 10 or min(level_dims(W, H, level)) > 32767:
+            return np.zeros((1, 1), np.uint8)       # not read: level 0 takes the image itself, bad levels return early
+        level_image = decimate(image, level)
+    level_image = np.ascontiguousarray(level_image, dtype=np.uint8)
+    assert level_image.ndim == 2
+    return level_image
+
+
+def ref_find_corners(image, level, level_image=None):
+    """find_corners() by upstream's own code.  level_image: what cv::resize returns (default decimate(image, level))."""
+    image, H, W, stride = _img2d(image)
+    li = _level_image(image, level, level_image)
+    cap = 4096
+    while True:
+        out = np.empty((cap, 2), dtype=np.int32)
+        n = _fcc_lib().fcc_ref_detect(out.ctypes.data_as(_i32p), cap, image.ctypes.data_as(_u8p), H, W, stride, level,
+                                      li.ctypes.data_as(_u8p), li.shape[0], li.shape[1])
+        if n < 0:
+            return None
+        if n <= cap:
+            return out[:n].copy()
+        cap = n
+
+
+def ref_refine_corners(points, levels, image, level, level_image=None):
+    """refine_corners() by upstream's own code.  level_image as in ref_find_corners."""
+    image, H, W, stride = _img2d(image)
+    li = _level_image(image, level, level_image)
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2).copy()
+    lv = np.ascontiguousarray(levels, dtype=np.int8).copy()
+    n = _fcc_lib().fcc_ref_refine(pts.ctypes.data_as(_f64p), lv.ctypes.data_as(_i8p), len(lv), image.ctypes.data_as(_u8p),
+                                  H, W, stride, level, li.ctypes.data_as(_u8p), li.shape[0], li.shape[1])
+    return pts, lv, n
+
+
+def ref_cc_detect_on_response(resp, level_image, level=0):
+    """cc_detect_on_response() by upstream's own component search."""
+    d = np.ascontiguousarray(resp, dtype=np.int16)
+    img = np.ascontiguousarray(level_image, dtype=np.uint8)
+    h, w = d.shape
+    assert img.shape == (h, w)
+    cap = 4096
+    while True:
+        out = np.empty((cap, 2), dtype=np.int32)
+        n = _fcc_resp_lib().fcc_ref_cc_detect_on_response(out.ctypes.data_as(_i32p), cap, d.ctypes.data_as(_i16p),
+                                                          img.ctypes.data_as(_u8p), w, h, level)
+        assert n >= 0
+        if n <= cap:
+            return out[:n].copy()
+        cap = n
+
+
+def ref_cc_refine_on_response(points, levels, resp, level_image, level):
+    """cc_refine_on_response() by upstream's own component search."""
+    d = np.ascontiguousarray(resp, dtype=np.int16)
+    img = np.ascontiguousarray(level_image, dtype=np.uint8)
+    h, w = d.shape
+    assert img.shape == (h, w)
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2).copy()
+    lv = np.ascontiguousarray(levels, dtype=np.int8).copy()
+    n = _fcc_resp_lib().fcc_ref_cc_refine_on_response(pts.ctypes.data_as(_f64p), lv.ctypes.data_as(_i8p), len(lv),
+                                                      d.ctypes.data_as(_i16p), img.ctypes.data_as(_u8p), w, h, level)
+    return pts, lv, n
+
+
+def ref_chain(image, start_level=3, level_images=None):
+    """chain() with upstream's own detect and refine: the loop of mrgingham.cc:50, :81-99 without the grid finder.
+    level_images: {level: image} for the levels above 0 (default decimate(image, level))."""
+    li = level_images or {}
+    cand = ref_find_corners(image, start_level, li.get(start_level))
+    if cand is None:
+        return None
+    pts = cand.astype(np.float64) / 1000.0
+    lv = np.full(len(pts), start_level, dtype=np.int8)
+    for L in range(start_level - 1, -1, -1):
+        pts, lv, n = ref_refine_corners(pts, lv, image, L, li.get(L))
+        if n <= 0:
+            break
+    return pts, lv
 
 
 def find_blobs(image):

@@ -109,6 +109,66 @@ def detect_cases():
     d = _z(); d[30, 40] = 300; d[30, 41] = 300; d[12, 50] = 300; d[13, 50] = 300; d[12, 20] = 300; d[12, 21] = 200
     add("three blobs: output in seed raster order", d,
         [_pt(300 * 20 + 200 * 21, 12 * 500, 500), [50000, 12500], [40500, 30000]])
+
+    # ---- cases the upstream build is run on as well (tests/test_oracle_fcc.py) --------------------------------
+    # equal peaks, strict > (:176): the variance test looks at the FIRST maximum visited (the seed, x = 30), and the
+    # image decides which of the two windows (columns 20..40 about x = 30, 21..41 about x = 31) is flat.  One
+    # column of 255 in an image of 0: mean 255*21/441 = 12, variance (21*243^2 + 420*12^2)/441 = 2948 > 400.
+    d = _z(); d[20, 30] = 300; d[20, 31] = 300
+    only_first = np.zeros((H, W), np.uint8); only_first[:, 20] = 255
+    only_second = np.zeros((H, W), np.uint8); only_second[:, 41] = 255
+    add("equal peaks: variance is high about the first (x=30) only -> accepted", d, [[30500, 20000]], only_first)
+    add("equal peaks: variance is high about the second (x=31) only -> rejected", d, [], only_second)
+    # the largest int16 response: 32767 >> 4 = 2047 (:27, the uint16_t cast); the seed is the peak, the third pixel
+    # keeps N >= 2 either way so that the centroid says whether the neighbour was taken
+    d = _z(); d[20, 20] = 32767; d[21, 20] = 3000; d[20, 21] = 2047
+    add("peak 32767: 2047 is not > 32767>>4 = 2047", d,
+        [[20000, int(0.5 + (32767 * 20 + 3000 * 21) / 35767 * 1000)]])
+    d = _z(); d[20, 20] = 32767; d[21, 20] = 3000; d[20, 21] = 2048
+    add("peak 32767: 2048 > 2047 is taken", d,
+        [_pt(32767 * 20 + 3000 * 20 + 2048 * 21, 32767 * 20 + 3000 * 21 + 2048 * 20, 37815)])
+    # a component that touches the ring is dropped, but it consumed its pixels all the same (:245, :250): seed
+    # (8,20) = 2000, pops x=7 (200, taken; its neighbour x=6 is outside: touched), then x=9 (100, not > 125: zeroed,
+    # not expanded).  The seed loop goes on to x=10, which now stands apart from what was dropped.
+    d = _z(); d[20, 7:12] = [200, 2000, 100, 300, 200]
+    add("touched component is dropped yet zeroes its rejected pixel: the remainder 300,200 is found", d,
+        [_pt(300 * 10 + 200 * 11, 20 * 500, 500)])
+    # more pixels than the upstream list's first allocation (128 entries, :104, :127)
+    rng = np.random.RandomState(128)
+    d = _z(); d[12:28, 12:25] = rng.randint(130, 400, (16, 13)); d[20, 18] = 2040
+    add("208-pixel component: the list grows past 128 entries", d, None)
+    # the variance window against the top and bottom sides (:52-53), both sides of the >=
+    d = _z(); d[10, 30] = 300; d[11, 30] = 100
+    add("variance window fits at y_peak = 10", d, [_pt(30 * 400, 300 * 10 + 100 * 11, 400)])
+    d = _z(); d[H - 11, 30] = 300; d[H - 12, 30] = 100
+    add("variance window fits at y_peak = h-11", d, [_pt(30 * 400, 300 * (H - 11) + 100 * (H - 12), 400)])
+    d = _z(); d[H - 10, 30] = 300; d[H - 11, 30] = 100
+    add("variance window leaves the image at y_peak = h-10", d, [])
+    # variance against 400 (:87, strict) with truncating divisions (:69, :80).  Window about (30,20): 221 pixels of 120
+    # and 220 of 80 -> sum 44120, mean 100 (100.05 truncated), every deviation +-20: sum of squares 176400 = 441 * 400.
+    d = _z(); d[20, 30] = 300; d[20, 31] = 100
+    base = np.full((H, W), 80, np.uint8); base[10:20, 20:41] = 120; base[20, 20:31] = 120
+    add("variance exactly 400 is not > 400", d, [], base)
+    im = base.copy(); im[10, 20] = 125      # +25^2 - 20^2 = +225: 176625 / 441 = 400.51 -> truncates to 400
+    add("variance 400.51 truncates to 400: rejected", d, [], im)
+    im = base.copy(); im[10, 20] = 131      # +31^2 - 20^2 = +561: 176961 / 441 = 401.27 -> 401
+    add("variance 401 passes", d, [_pt(300 * 30 + 100 * 31, 20 * 400, 400)], im)
+    return cases
+
+
+LARGE_H, LARGE_W = 64, 96
+
+
+def large_detect_cases():
+    """Like detect_cases(), on a frame large enough for one component of more than 2048 hot pixels (the search out of
+    LDS holds 2048 per frame and hands larger frames over)."""
+    h, w = LARGE_H, LARGE_W
+    rng = np.random.RandomState(2048)
+    d = np.zeros((h, w), np.int16)
+    d[8:56, 8:88] = rng.randint(130, 400, (48, 80)); d[30, 48] = 2040      # 2040 >> 4 = 127: every pixel stays valid
+    cases = [("3840-pixel component inside the ring: accepted, more than 2048 hot pixels", d, flat_img(h, w), None)]
+    d = d.copy(); d[30, 7] = 200
+    cases.append(("3841-pixel component reaching column 7: touched, all consumed", d, flat_img(h, w), []))
     return cases
 
 
@@ -137,6 +197,36 @@ def refine_cases():
     # a point on the image border: seeds outside the image are skipped (:159-163)
     cases.append(("point at the image corner", np.array([[0.0, 0.0], [63.0, 47.0]]), np.array([1, 1], np.int8),
                   d, img, 0, (np.array([[0.0, 0.0], [63.0, 47.0]]), [1, 1], 0)))
+
+    # ---- cases the upstream build is run on as well (tests/test_oracle_fcc.py) --------------------------------
+    # (int)(x + 0.5) truncates towards zero (:371-372): every x in (-1.5, 0.5) seeds about column 0, so that the
+    # 3x3 neighbourhood hangs over the image's side (:162-163).  Nothing in columns 0..1 can ever be accepted (the
+    # ring), so all these do is find nothing -- the truncation itself shows in the wrapped case below.
+    xs = [-1.6, -1.5, -1.4, -1.0, -0.6, -0.5, -0.4, 0.4]
+    pts = np.array([[x, 20.0] for x in xs] + [[20.0, y] for y in xs])
+    cases.append(("seeds about (int)(x+0.5) for x around (-1.5,-0.5): 3x3 partly outside the image, nothing found",
+                  pts, np.ones(len(pts), np.int8), d, img, 0, (pts.copy(), [1] * len(pts), 0)))
+    # seeds far outside wrap through the int16_t parameters of is_valid / xylist_push (:159, :124, :381-382): the int
+    # seed x = +-65536 + k or +-131072 + k is column k to them.  Four blobs, one per point; the last point is far
+    # outside and wraps to column 4464, outside again.
+    d4 = _z()
+    for y in (12, 20, 28, 36):
+        d4[y, 20] = 300; d4[y, 21] = 100
+    far = np.array([[65536.0 + 20.2, 12.0], [-65536.0 + 20.2, 20.0], [131072.0 + 19.8, 28.0], [20.0, -131072.0 + 36.3],
+                    [70000.0, 20.0]])
+    cases.append(("seeds at +-65536+k and +-131072+k wrap into the image through int16_t", far, np.ones(5, np.int8), d4,
+                  img, 0, (np.array([[cx, 12.0], [cx, 20.0], [cx, 28.0], [cx, 36.0], [70000.0, 20.0]]), [0, 0, 0, 0, 1], 4)))
+    # ... and there the truncation towards zero shows: -65536 + 20.3 + 0.5 = -65515.2 -> -65515 -> column 21 (floor
+    # would give 20), whose neighbourhood 20..22 reaches the blob at 22..23; +65536 + 19.7 + 0.5 -> 65556 -> column 20,
+    # whose neighbourhood 19..21 does not
+    d5 = _z(); d5[20, 22] = 300; d5[20, 23] = 100; d5[30, 22] = 300; d5[30, 23] = 100
+    cases.append(("wrapped negative seed truncates towards zero: column 21, not 20", np.array([[-65536.0 + 20.3, 20.0], [65536.0 + 19.7, 30.0]]),
+                  np.ones(2, np.int8), d5, img, 0,
+                  (np.array([[(300 * 22 + 100 * 23) / 400, 20.0], [65536.0 + 19.7, 30.0]]), [0, 1], 1)))
+    # levels other than level + 1 on every side of it (:362), at level 1: 0, 1, 3 and -1 are skipped, 2 is taken
+    cases.append(("levels 0, 1, 3, -1 are skipped at level 1, 2 is taken", np.array([[40.7, 40.3]] * 5),
+                  np.array([0, 1, 3, -1, 2], np.int8), d, img, 1,
+                  (np.array([[40.7, 40.3]] * 4 + [[(cx + 0.5) * 2 - 0.5, (20.0 + 0.5) * 2 - 0.5]]), [0, 1, 3, -1, 1], 1)))
     return cases
 
 

@@ -61,6 +61,33 @@ def test_unpack_equals_numpy(det, h, w, bits):
     assert np.array_equal(got, want)
 
 
+@pytest.mark.parametrize("bits", [8, 16])
+@pytest.mark.parametrize("rows_per_workgroup", [1, 256])
+def test_unpack_takes_a_second_trip_over_the_rows(det, bits, rows_per_workgroup):
+    """The grid is capped at eight workgroups per CU and the kernel loops over the rows beyond: every full-size call
+    takes that loop, no other shape of this file does.  A row is taken by the power of two of lanes that covers its
+    16-byte words, so a workgroup of 256 lanes holds one row of 2049 bytes or more (129 words and one more, the rows
+    beginning inside a word), and 256 dense rows of 16 bytes.  The smallest row count above one trip, the last trip ragged."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rows_per_trip = 8 * cus * rows_per_workgroup
+    if rows_per_workgroup == 1:
+        B, h, rowb = 1, rows_per_trip + 37, 2050
+        assert (rowb + 15) // 16 + 1 > 128 and rowb % 16 != 0            # more words than 128 lanes cover; rows at every phase
+    else:
+        rowb = 16                                                        # dense and aligned: one word per row, one lane
+        h = next(h for h in range(4099, 4200) if ((rows_per_trip // h + 1) * h - rows_per_trip) % 256)
+        B = rows_per_trip // h + 1
+    w, nrows = rowb * 8 // bits, B * h
+    assert rows_per_trip < nrows < 2 * rows_per_trip                     # two trips
+    assert (nrows - rows_per_trip) % rows_per_workgroup or rows_per_workgroup == 1   # ... whose last workgroup is not full
+    samples = _random(B, h, w, bits, seed=bits + rows_per_workgroup)
+    pay, want = _payload(samples, bits)
+    got = _unpack(det, pay, h, w, bits)
+    assert got.dtype == want.dtype and got.shape == (B, h, w)
+    assert np.array_equal(got, want)
+
+
 def test_every_16_bit_value_once(det):
     """(a wrong permute selector cannot hide: 0x0102 must come out as 0x0102 from the bytes 01 02)"""
     samples = np.arange(65536, dtype=np.uint16).reshape(1, 256, 256)

@@ -141,6 +141,27 @@ def test_finish_kernel(det, tmp_path, width):
     assert n == 32
 
 
+@pytest.mark.parametrize("bits,samples,compression,predictor,order", [(8, 1, tc.NONE, 1, "<"), (16, 3, tc.LZW, 2, ">")],
+                         ids=["8bit_uncompressed", "16bit_be_lzw_predictor2_rgb"])
+def test_finish_kernel_takes_a_second_trip_over_the_rows(det, tmp_path, bits, samples, compression, predictor, order):
+    """The finish kernel's grid is capped at eight workgroups per CU, four waves each, one row per wave and trip: every
+    full-size call loops, no other shape of this file does.  Two frames of 17 x (16 CUs + 100): one full trip and 200 rows
+    of a second one, which begins in the middle of the second frame."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rows_per_trip = 8 * cus * 4
+    W, H, B = 17, 16 * cus + 100, 2
+    assert rows_per_trip < B * H < 2 * rows_per_trip and H < rows_per_trip     # two trips, the last one ragged
+    imgs = [tc.random_image(W, H, samples, bits, seed=40 + k) for k in range(B)]
+    datas = [tc.encode(img, order=order, compression=compression, predictor=predictor, rows_per_strip=128)[0] for img in imgs]
+    got, status, strip_status = _decode(det, datas)
+    assert status.tolist() == [0] * B and not strip_status.any()
+    for k in range(B):
+        want = tc.grey_of(imgs[k], 2 if samples >= 3 else 1)
+        assert got[k].dtype == want.dtype and np.array_equal(got[k], want), k
+        assert np.array_equal(_high(want), _host(tmp_path, datas[k])), k
+
+
 def test_decode_batch_refuses_bad_descriptors(det):
     import ctypes
     import torch
