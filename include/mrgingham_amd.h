@@ -62,7 +62,12 @@ extern "C" {
  *      mrgingham_amd_tiff_layout, _tiff_decode_batch, _tiff_geometry, _read_tiffs_batch (TIFF: LZW strips, predictor and
  *      grey on the device); options "tiff_chunk_frames", "tiff_lzw_max_strip", "tiff_lzw_lanes";
  *      mrgingham_amd_find_boards_files_ex2 (loader flag MRGINGHAM_AMD_FILES_TIFF_DEVICE).  The device route is off unless
- *      asked for. */
+ *      asked for.
+ *      Later, additive (the version stays 4): mrgingham_amd_tiff_layout_ex and _tiff_inflate_lanes;
+ *      mrgingham_amd_tiff_decode_batch takes compression 8 and 32946 (Deflate strips on the device); options "tiff_deflate",
+ *      "tiff_deflate_max_strip", "tiff_deflate_lanes"; mrgingham_amd_find_boards_files_ex3 (loader flag
+ *      MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE).  Off unless asked for: mrgingham_amd_tiff_layout goes on leaving Deflate
+ *      files to the host decoder. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -574,21 +579,37 @@ typedef struct mrgingham_amd_tiff_strip {
 int mrgingham_amd_tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info,
                               mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips);
 
-/* TIFF, device half: nframes files of ONE size, depth, sample count, photometric, compression (1 or 5), predictor and byte
- * order (`info`, HOST; what mrgingham_amd_tiff_layout reported for every one of them) from their bytes to grey frames,
+/* mrgingham_amd_tiff_layout that also takes Deflate files (compression 8 and 32946) whose strips each decode to at most
+ * deflate_max_strip bytes (above 2^20: 2^20; option "tiff_deflate_max_strip" of a context): it returns 0 for them, and
+ * MRGINGHAM_AMD_TIFF_NOT_TAKEN with a larger strip, and with a strip of more bytes in the file than what it decodes to
+ * plus an eighth plus 512: a Deflate block need not give a byte, so a lane's work goes with the strip's bytes, and no zlib
+ * stream of the rows needs more (such a file keeps the host decoder, which reads it as before).  deflate_max_strip <= 0: no Deflate file is taken, which is
+ * mrgingham_amd_tiff_layout.  A Deflate strip is a zlib stream (RFC 1950 around RFC 1951) and the contract is zlib's: the
+ * device accepts a strip exactly when uncompress() into a buffer of exactly rows x rowbytes returns Z_OK with that many
+ * bytes, which is the host decoder's test -- the decoder goes on behind the last byte to the final block and checks the
+ * Adler-32; bytes behind the trailer are ignored (csrc/tiff_inflate.h). */
+int mrgingham_amd_tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip,
+                                 mrgingham_amd_tiff_info* info, mrgingham_amd_tiff_strip* strips, size_t capacity,
+                                 size_t* nstrips);
+
+/* TIFF, device half: nframes files of ONE size, depth, sample count, photometric, compression (1, 5, or 8 / 32946),
+ * predictor and byte order (`info`, HOST; what mrgingham_amd_tiff_layout or _tiff_layout_ex reported for every one of them) from their bytes to grey frames,
  * byte for byte what mrgingham_amd_read_image computes.  d_files: file f's bytes at d_files + f*file_pitch (BYTES; d_files
  * 16-byte aligned, file_pitch a multiple of 16).  d_strips (DEVICE): file f's strip records, as mrgingham_amd_tiff_layout
  * wrote them, at d_strips + f*strips_pitch, d_nstrips[f] (DEVICE) of them, at most strips_pitch.  d_out: uint8_t frames
  * for bits 8, native-endian uint16_t frames for bits 16; frame f row y at d_out + f*frame_pitch + y*stride, ELEMENTS; only
  * the width x height samples are written, what lies between width and stride stays untouched.  d_status (DEVICE, nframes
- * words, written): 0 decoded; -1 an LZW strip broke a rule of the decoder, or a strip record does not fit its file or
- * frame (offset + nbytes above file_pitch, rows outside the frame or not in strip order, a decoded size above 1 MiB) --
+ * words, written): 0 decoded; -1 an LZW or Deflate strip broke a rule of the decoder, or a strip record does not fit its file or
+ * frame (offset + nbytes above file_pitch, rows outside the frame or not in strip order, a decoded size above 1 MiB, a
+ * Deflate strip of more bytes than its decoded size plus an eighth plus 512, which mrgingham_amd_tiff_layout_ex never hands out) --
  * that frame is zero-filled, the others are not affected.  d_strip_status (DEVICE, may be NULL; nframes*strips_pitch
- * words): per LZW strip 0, or what stopped its lane (tiff_lzw.h).
+ * words): per LZW or Deflate strip 0, or what stopped its lane (tiff_lzw.h, tiff_inflate.h).
  * Compression 5 first runs tiff_lzw_kernel, one lane per strip: a fixed number of lanes loops over the strips, each with
  * a table of 4096 dwords in context scratch (interleaved by lane: at most 16384 lanes x 16 KiB = 256 MiB, whatever the
  * batch), decoding into context scratch of nframes x rowbytes x height; a lane reads nothing beyond its strip's byte
- * count and writes nothing beyond its strip's rows.  Then tiff_finish_kernel, one wave per row: value order, predictor 2
+ * count and writes nothing beyond its strip's rows.  Compression 8 / 32946 runs tiff_inflate_kernel on the same schedule,
+ * each lane with 1280 16-bit words of decode tables in context scratch (at most 131072 lanes x 2560 bytes = 320 MiB, sized by the strips of the call); a match
+ * never reaches before the first byte of its own strip.  Then tiff_finish_kernel, one wave per row: value order, predictor 2
  * undone by a prefix sum mod 2^bits, WhiteIsZero inverted, grey.  Asynchronous on `stream` (NULL = default); allocates
  * nothing beyond context scratch.  Arguments are checked like mrgingham_amd_png_reconstruct_batch's (MRGINGHAM_AMD_ERR_ARG,
  * nothing written). */
@@ -602,6 +623,8 @@ int mrgingham_amd_tiff_decode_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_fil
  * lane of the finish kernel takes, and the pixels of a row a wave takes per step (the prefix sum of predictor 2 is carried
  * from lane to lane inside a step and from step to step). */
 void mrgingham_amd_tiff_geometry(int* lzw_lanes, int* segment_pixels, int* step_pixels);
+/* the lanes in flight of the Deflate launch, scheduled like the LZW one (option "tiff_deflate_lanes" lowers it) */
+int mrgingham_amd_tiff_inflate_lanes(void);
 
 /* nfiles TIFF files of ONE size and depth straight into device frames (layout and element type as d_out above): per file
  * a host thread (nthreads of them; <= 0: all cores, at most 32) reads the file straight into page-locked staging and runs
@@ -610,7 +633,8 @@ void mrgingham_amd_tiff_geometry(int* lzw_lanes, int* segment_pixels, int* step_
  * mrgingham_amd_tiff_decode_batch per run of files of equal (samples, photometric, compression, predictor, byte order)
  * while the host threads read the next.  A file the device route does not take (MRGINGHAM_AMD_TIFF_NOT_TAKEN, or a file
  * much larger than its samples) is decoded by the host thread with mrgingham_amd_read_image's decoder and uploaded: same
- * bytes.  h_status[f]: 0 decoded, -1 unreadable / unsupported / malformed (or not a TIFF), -2 a TIFF of another size or
+ * bytes.  Deflate files are among those unless option "tiff_deflate" is 1: then the layouts come from
+ * mrgingham_amd_tiff_layout_ex with option "tiff_deflate_max_strip", and a file with a larger strip keeps the host thread.  h_status[f]: 0 decoded, -1 unreadable / unsupported / malformed (or not a TIFF), -2 a TIFF of another size or
  * depth; the frame of a failed file is zero-filled.  SYNCHRONOUS: d_out is complete on return.  Returns MRGINGHAM_AMD_OK
  * also when files failed.  Completes the find_boards jobs in flight first and restores the caller's HIP device.  The
  * chunk buffers are those of mrgingham_amd_read_jpegs_batch, within the same 1 GiB (option "tiff_chunk_frames"). */
@@ -794,6 +818,16 @@ int mrgingham_amd_find_boards_files_ex2(const char* const* filenames, int nfiles
                                         int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
                                         double* stats, int nstats, int loader_flags);
 
+/* mrgingham_amd_find_boards_files_ex2 with one more loader flag (which _ex2 goes on refusing).
+ * MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE: the TIFF runs also send their Deflate files through the device (option
+ * "tiff_deflate" of the loader context).  It is part of the TIFF device route: without MRGINGHAM_AMD_FILES_TIFF_DEVICE it is
+ * MRGINGHAM_AMD_ERR_ARG, as is any bit above the four flags.  Same outputs. */
+#define MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE 8
+int mrgingham_amd_find_boards_files_ex3(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
+                                        double* h_boards, signed char* h_levels, signed char* h_found_level,
+                                        int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
+                                        double* stats, int nstats, int loader_flags);
+
 /* Where the find_boards calls of this context spent their HOST time since the last reset, and what their grid-finder
  * threads did (the reference's find_grid_from_points, mrgingham.cc:51, is the host part of the product call; on a busy
  * batch it is what bounds it).  out[0 .. n) receives up to MRGINGHAM_AMD_FB_STATS doubles:
@@ -951,6 +985,14 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         bounds the serial work of one lane: on 64 12 MP files mrgingham_amd_read_tiffs_batch was measured
  *                         faster through the device than on 16 host threads at 8 KiB and 64 KiB strips and slower at 1 MiB
  *                         (the sizes between were not measured).
+ *   "tiff_deflate"        0 (default): mrgingham_amd_read_tiffs_batch leaves Deflate files to its host threads; 1: it sends
+ *                         them through the device (mrgingham_amd_tiff_layout_ex), a strip per lane.
+ *   "tiff_deflate_max_strip" decoded bytes of a Deflate strip, 0 .. 1048576 (default 8192): with "tiff_deflate" 1, a file
+ *                         with a larger strip keeps the host threads.  Together with the limit on a strip's bytes in the
+ *                         file (mrgingham_amd_tiff_layout_ex) it bounds the serial work of one lane: on 64 12 MP
+ *                         files mrgingham_amd_read_tiffs_batch was measured against 16 host threads at 8 KiB, 64 KiB and
+ *                         1 MiB per strip and won at 8 KiB only.
+ *   "tiff_deflate_lanes"  test hook: lanes in flight of the Deflate launch, a multiple of 64 up to 131072; 0 (default) = 131072.
  *   "tiff_lzw_lanes"      test hook: lanes in flight of the LZW launch, a multiple of 64 up to 16384; 0 (default) = 16384.
  *                         Results never depend on it.
  *   "jpeg_entropy"        0 (default): mrgingham_amd_read_jpegs_batch entropy-decodes on its host threads; 1: files with

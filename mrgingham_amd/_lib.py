@@ -69,6 +69,7 @@ EXPORTS = [
     "mrgingham_amd_pgm_header", "mrgingham_amd_pgm_unpack_batch", "mrgingham_amd_read_pgms_batch",
     "mrgingham_amd_tiff_layout", "mrgingham_amd_tiff_decode_batch", "mrgingham_amd_tiff_geometry",
     "mrgingham_amd_read_tiffs_batch", "mrgingham_amd_find_boards_files_ex2",
+    "mrgingham_amd_tiff_layout_ex", "mrgingham_amd_tiff_inflate_lanes", "mrgingham_amd_find_boards_files_ex3",
 ]
 
 
@@ -189,6 +190,12 @@ def lib():
         L.mrgingham_amd_read_tiffs_batch.argtypes = [c_vp, ctypes.POINTER(ctypes.c_char_p), c_int, c_int, c_int, c_int, c_vp,
                                                      ctypes.c_int64, c_int, c_int, c_vp]
         L.mrgingham_amd_find_boards_files_ex2.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
+                                                          c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
+    if hasattr(L, "mrgingham_amd_tiff_layout_ex"):
+        L.mrgingham_amd_tiff_layout_ex.argtypes = [c_vp, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(TiffInfo), c_vp,
+                                                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        L.mrgingham_amd_tiff_inflate_lanes.argtypes = []
+        L.mrgingham_amd_find_boards_files_ex3.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
                                                           c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]

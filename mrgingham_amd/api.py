@@ -264,21 +264,28 @@ TIFF_NOT_TAKEN = -3
 TIFF_STRIP = np.dtype([("offset", "<i8"), ("nbytes", "<i8"), ("first_row", "<i4"), ("rows", "<i4")])
 
 
-def tiff_layout(data, lzw_max_strip=0, capacity=None):
+def tiff_layout(data, lzw_max_strip=0, capacity=None, deflate_max_strip=0):
     """The first image file directory of a TIFF held in memory (host only; mrgingham_amd_tiff_layout, which has the subset
     this library reads): -> TiffLayout, or None when the data is not a TIFF this library reads.  lzw_max_strip: the decoded
     bytes of an LZW strip above which the file is left to the host decoder (0: 1 MiB).  capacity: room for that many
-    strip records (default: all of them); with fewer than the file has, rc is -2 and the counts are still reported."""
+    strip records (default: all of them); with fewer than the file has, rc is -2 and the counts are still reported.
+    deflate_max_strip: above 0, Deflate files whose strips decode to at most that many bytes are taken as well
+    (mrgingham_amd_tiff_layout_ex); 0: they are left to the host decoder."""
     L = _lib.lib()
     buf = bytes(data)
     info, n = _lib.TiffInfo(), ctypes.c_size_t()
-    rc = L.mrgingham_amd_tiff_layout(buf, len(buf), int(lzw_max_strip), ctypes.byref(info), None, 0, ctypes.byref(n))
+
+    def call(strips, cap):
+        if int(deflate_max_strip) > 0:
+            return L.mrgingham_amd_tiff_layout_ex(buf, len(buf), int(lzw_max_strip), int(deflate_max_strip), ctypes.byref(info), strips, cap,
+                                                  ctypes.byref(n))
+        return L.mrgingham_amd_tiff_layout(buf, len(buf), int(lzw_max_strip), ctypes.byref(info), strips, cap, ctypes.byref(n))
+    rc = call(None, 0)
     if rc not in (0, TIFF_NOT_TAKEN):
         return None
     cap = n.value if capacity is None else int(capacity)
     strips = np.zeros(cap, dtype=TIFF_STRIP)
-    rc = L.mrgingham_amd_tiff_layout(buf, len(buf), int(lzw_max_strip), ctypes.byref(info), strips.ctypes.data if cap else None, cap,
-                                     ctypes.byref(n))
+    rc = call(strips.ctypes.data if cap else None, cap)
     if cap == 0 and n.value > 0 and capacity is not None:
         rc = -2   # (no array to write into is "counts only" at the C boundary)
     if rc not in (0, TIFF_NOT_TAKEN, -2):
@@ -342,7 +349,8 @@ FILES_STATS = ("chunks", "files_device_loader", "files_host_decoded", "files_one
 
 
 def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_radius=1, refine=True, batch=64, nthreads=0,
-                      entropy="host", device=None, progress=None, png="host", deep="one", tiff="host"):
+                      entropy="host", device=None, progress=None, png="host", deep="one", tiff="host",
+                      tiff_deflate="host"):
     """A list of image files (binary PGM, PNG, baseline JPEG, TIFF; any sizes) to boards (mrgingham_amd_find_boards_files): a
     loader thread fills chunks of `batch` equally-sized frames on the device -- JPEG through the batch loader,
     entropy="device": Huffman-decoded on the device as well -- while the calling thread preprocesses and searches the
@@ -359,9 +367,12 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
     and are preprocessed at 16 bit a chunk at a time; same numbers.  TIFF files behave as PNG files do: 8-bit files share
     chunks and are decoded on the loader's host threads, 16-bit files follow `deep`; tiff="device": the runs of TIFF files
     of a chunk go through the TIFF batch loader (Detector.read_tiffs: the host threads only read the files, LZW strips are
-    decoded one lane each) and count as files_device_loader; same numbers."""
+    decoded one lane each) and count as files_device_loader; same numbers.  tiff_deflate="device", with tiff="device" only:
+    the Deflate strips of those files are decoded on the device as well, else the loader's host threads inflate them."""
     if tiff not in ("host", "device"):
         raise ValueError('find_boards_files: tiff is "host" or "device"')
+    if tiff_deflate not in ("host", "device") or (tiff_deflate == "device" and tiff != "device"):
+        raise ValueError('find_boards_files: tiff_deflate is "host" or "device", "device" only with tiff="device"')
     if entropy not in ("host", "device"):
         raise ValueError('find_boards_files: entropy is "host" or "device"')
     if png not in ("host", "device"):
@@ -389,9 +400,10 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
                 raised.append(e)
     cb = _lib.PROGRESS_F(on_progress)
     arr = (ctypes.c_char_p * max(n, 1))(*names)
-    rc = L.mrgingham_amd_find_boards_files_ex2(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
+    rc = L.mrgingham_amd_find_boards_files_ex3(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
                                                status.ctypes.data, cb, None, stats.ctypes.data, len(stats),
-                                               int(png == "device") | 2 * int(deep == "chunks") | 4 * int(tiff == "device"))
+                                               int(png == "device") | 2 * int(deep == "chunks") | 4 * int(tiff == "device") |
+                                               8 * int(tiff_deflate == "device"))
     if raised:
         raise raised[0]
     if rc == -1:
@@ -914,7 +926,7 @@ class Detector:
         """Context manager: the options set for the duration of a call, and what they were afterwards."""
         @contextlib.contextmanager
         def scope():
-            defaults = {"jpeg_entropy": 0, "jpeg_sync": 0}
+            defaults = {"jpeg_entropy": 0, "jpeg_sync": 0, "tiff_deflate": 0}
             before = {k: self._options.get(k, defaults[k]) for k in values}
             try:
                 for k, v in values.items():
@@ -1117,7 +1129,7 @@ class Detector:
         """TIFF files held in memory to grey frames on the device (mrgingham_amd_tiff_decode_batch), on torch's current
         stream: datas, a list of bytes; layouts, their tiff_layout results (default: computed here), which must all be
         taken by the device route and agree in every field -> (frames uint8 or uint16 [B, height, width], the samples
-        read_image's decoder gives; status int32 [B] numpy: 0, or -1 for a file whose LZW strips broke a rule -- its frame
+        read_image's decoder gives; status int32 [B] numpy: 0, or -1 for a file whose LZW or Deflate strips broke a rule -- its frame
         is zero; strip_status int32 [B, P] numpy: per strip what stopped its lane, 0 for none).  `out`: a [B, height,
         >= width] device tensor of that type (unit column stride) to write into; what lies beyond `width` is not touched.
         Synchronises (the status words come back)."""
@@ -1155,14 +1167,22 @@ class Detector:
             d_sstatus.data_ptr(), stream))
         return out[:, :, :W], d_status.cpu().numpy(), d_sstatus.cpu().numpy()
 
-    def read_tiffs(self, paths, nthreads=0):
+    def read_tiffs(self, paths, nthreads=0, deflate=None):
         """TIFF files of one size and depth straight into device frames (mrgingham_amd_read_tiffs_batch): `nthreads` host
         threads (0: all cores, at most 32) read the files into page-locked staging and parse their directories, the device
         decodes the LZW strips one lane each, undoes the predictor and reduces colour to grey.  -> (frames uint8 or uint16
         [B,H,W] on the device, status int32 [B] numpy: 0 decoded, -1 unreadable / unsupported / malformed, -2 a TIFF of
         another size or depth; failed frames are zero).  Size and depth are those of the first file whose directory
         parses (none does: uint8 frames [B,0,0]).  PackBits and Deflate files, and LZW files with a strip above option
-        "tiff_lzw_max_strip", are decoded by the host threads: same bytes.  Synchronous."""
+        "tiff_lzw_max_strip", are decoded by the host threads: same bytes.  deflate="device": Deflate files whose strips
+        decode to at most option "tiff_deflate_max_strip" go through the device like LZW files; "host": the host threads
+        inflate them; None (default): as option "tiff_deflate" of this detector says.  Either value holds for this call
+        only: the option is afterwards what it was.  Synchronous."""
+        if deflate not in (None, "host", "device"):
+            raise ValueError('read_tiffs: deflate is None, "host" or "device"')
+        if deflate is not None:
+            with self._with_options(tiff_deflate=int(deflate == "device")):
+                return self.read_tiffs(paths, nthreads)
         t = self.torch
         names = [os.fsencode(p) for p in paths]
         B = len(names)

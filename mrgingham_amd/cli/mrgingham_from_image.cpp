@@ -48,12 +48,13 @@ struct Options {
     bool png_device = false;      // --png-reconstruct device
     bool deep_chunks = false;     // --deep-batch chunks
     bool tiff_device = false;     // --tiff-lzw device
+    bool tiff_deflate_device = false;  // --tiff-deflate device
 } opt;
 
 const char* kUsage =
     "Usage: %s [--gridn N] [--noclahe] [--blur radius] [--level l] [--no-refine] [--jobs N]\n"
     "          [--gpus N|all] [--batch N [--jpeg-entropy host|device] [--png-reconstruct host|device]\n"
-    "          [--deep-batch one|chunks] [--tiff-lzw host|device]]\n"
+    "          [--deep-batch one|chunks] [--tiff-lzw host|device [--tiff-deflate host|device]]]\n"
     "          [--debug] [--debug-sequence x,y]\n"
     "          imageglobs...\n"
     "\n"
@@ -86,6 +87,8 @@ const char* kUsage =
     "                  in chunks of their own, the byte swap and the 16-bit preprocessing a chunk at a time on the device)\n"
     "  --tiff-lzw host|device   with --batch: where the strips of TIFF files are decoded and their rows reduced to grey\n"
     "                  (default host; device: the --jobs threads only read the files, LZW strips are decoded one lane each)\n"
+    "  --tiff-deflate host|device   with --batch and --tiff-lzw device: where the Deflate strips of TIFF files are inflated\n"
+    "                  (default host: the --jobs threads; device: one lane per strip)\n"
     "  --blobs         find a grid of dark circles instead of a chessboard (no --level, no refinement)\n"
     "  --debug         one image only: write the preprocessed image, the level images, the ChESS\n"
     "                  responses and the corner vnlogs to /tmp like the reference does\n"
@@ -280,11 +283,12 @@ int run_batch() {
     o.jpeg_entropy = opt.entropy_device;
     o.device = -1;
     double stats[MRGINGHAM_AMD_FILES_STATS] = {};
-    const int rc = mrgingham_amd_find_boards_files_ex2(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
+    const int rc = mrgingham_amd_find_boards_files_ex3(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
                                                        B.status.data(), batch_progress, &B, stats, MRGINGHAM_AMD_FILES_STATS,
                                                        (opt.png_device ? MRGINGHAM_AMD_FILES_PNG_DEVICE : 0) |
                                                            (opt.deep_chunks ? MRGINGHAM_AMD_FILES_DEEP_CHUNKS : 0) |
-                                                           (opt.tiff_device ? MRGINGHAM_AMD_FILES_TIFF_DEVICE : 0));
+                                                           (opt.tiff_device ? MRGINGHAM_AMD_FILES_TIFF_DEVICE : 0) |
+                                                           (opt.tiff_deflate_device ? MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE : 0));
     fflush(stdout);
     if (getenv("MRGINGHAM_AMD_CLI_TIMING"))
         fprintf(stderr, "batch: %.0f chunks; files: %.0f device loader, %.0f host-decoded, %.0f one at a time, %.0f unreadable; "
@@ -311,8 +315,9 @@ int main(int argc, char* argv[]) {
         {"png-reconstruct", required_argument, nullptr, 'P'},
         {"deep-batch", required_argument, nullptr, 'Q'},
         {"tiff-lzw", required_argument, nullptr, 'Z'},
+        {"tiff-deflate", required_argument, nullptr, 'Y'},
         {nullptr, 0, nullptr, 0}};
-    bool doblobs = false, entropy_given = false, png_given = false, deep_given = false, tiff_given = false;
+    bool doblobs = false, entropy_given = false, png_given = false, deep_given = false, tiff_given = false, deflate_given = false;
     int c;
     while ((c = getopt_long(argc, argv, "hj:b:l:", longopts, nullptr)) != -1) {
         switch (c) {
@@ -384,6 +389,15 @@ int main(int argc, char* argv[]) {
                 tiff_given = true;
                 opt.tiff_device = !strcmp(optarg, "device");
                 break;
+            case 'Y':
+                if (strcmp(optarg, "host") && strcmp(optarg, "device")) {
+                    fprintf(stderr, "--tiff-deflate takes 'host' or 'device', got '%s'\n", optarg);
+                    fprintf(stderr, kUsage, argv[0]);
+                    return 1;
+                }
+                deflate_given = true;
+                opt.tiff_deflate_device = !strcmp(optarg, "device");
+                break;
             default:
                 fprintf(stderr, "Unknown option\n");
                 fprintf(stderr, kUsage, argv[0]);
@@ -404,6 +418,14 @@ int main(int argc, char* argv[]) {
     }
     if (tiff_given && !opt.batch) {
         fprintf(stderr, "--tiff-lzw is only accepted with --batch\n");
+        return 1;
+    }
+    if (deflate_given && !opt.batch) {
+        fprintf(stderr, "--tiff-deflate is only accepted with --batch\n");
+        return 1;
+    }
+    if (opt.tiff_deflate_device && !opt.tiff_device) {
+        fprintf(stderr, "--tiff-deflate device is only accepted with --tiff-lzw device\n");
         return 1;
     }
     if (opt.batch && (opt.debug || doblobs || opt.gpus > 1 || opt.gpus == -1)) {

@@ -623,6 +623,22 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
         ctx->tiff_lzw_lanes = value;
         return 0;
     }
+    if (!strcmp(name, "tiff_deflate")) {
+        if (value != 0 && value != 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "tiff_deflate: 0 (host threads) or 1 (the device, for strips up to tiff_deflate_max_strip)");
+        ctx->tiff_deflate = value;
+        return 0;
+    }
+    if (!strcmp(name, "tiff_deflate_max_strip")) {
+        if (value < 0 || value > (1 << 20)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "tiff_deflate_max_strip: decoded bytes per strip, 0 (no file) .. 1048576");
+        ctx->tiff_deflate_max_strip = value;
+        return 0;
+    }
+    if (!strcmp(name, "tiff_deflate_lanes")) {
+        if (value < 0 || value > mrgingham_amd_tiff_inflate_lanes() || (value & 63))
+            return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "tiff_deflate_lanes: 0 (the shipped count) or a multiple of 64 up to it");
+        ctx->tiff_deflate_lanes = value;
+        return 0;
+    }
     if (!strcmp(name, "jpeg_entropy")) {
         if (value != 0 && value != 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "jpeg_entropy: 0 (host threads) or 1 (the device, for files with restart intervals)");
         ctx->jpeg_entropy = value;

@@ -314,10 +314,17 @@ struct mrgingham_amd_ctx {
     // tiff_broken: per frame, set by a lane whose strip broke a rule.  Options "tiff_chunk_frames" (test hook: at most
     // that many files per chunk, 0 = by the budget), "tiff_lzw_max_strip" (decoded bytes of an LZW strip above which a
     // file keeps the host decoder) and "tiff_lzw_lanes" (test hook: lanes in flight of the LZW launch, 0 = 16384)
-    mrg::DevBuf tiff_raw, tiff_table, tiff_broken;
+    // Deflate strips: tiff_inflate_table: 1280 16-bit words per lane in flight (at most 131072), interleaved by lane.
+    // Options "tiff_deflate" (1: mrgingham_amd_read_tiffs_batch sends Deflate files through the device; 0, the default:
+    // they keep the host threads), "tiff_deflate_max_strip" (decoded bytes of a Deflate strip above which a file keeps the
+    // host decoder) and "tiff_deflate_lanes" (test hook: lanes in flight of the Deflate launch, 0 = 131072)
+    mrg::DevBuf tiff_raw, tiff_table, tiff_broken, tiff_inflate_table;
     int tiff_chunk_frames = 0;
     int tiff_lzw_max_strip = 64 << 10;  // (measured: DESIGN.md section 4.14)
     int tiff_lzw_lanes = 0;
+    int tiff_deflate = 0;
+    int tiff_deflate_max_strip = 8 << 10;  // (measured: DESIGN.md section 4.15)
+    int tiff_deflate_lanes = 0;
     mrg::DevBuf fb_xy, fb_cnt, fb_pts, fb_lv, fb_np, fb_frames, fb_frames2;  // find_boards_batch: candidates, counts, boards, levels, point counts
     // find_boards_batch's frame-by-frame retries (full-capacity detect, 1-by-1 refine) run on a single-frame
     // context of THIS context's device, created on first use -- not on the calling thread's default context, which

@@ -238,7 +238,20 @@ int mrgingham_amd_find_boards_files_ex2(const char* const* filenames, int nfiles
                                         double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
                                         void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
                                         int loader_flags) {
-    if (nfiles < 0 || (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE)) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
+    if (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE)) return MRGINGHAM_AMD_ERR_ARG;
+    return mrgingham_amd_find_boards_files_ex3(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
+                                               nstats, loader_flags);
+}
+
+int mrgingham_amd_find_boards_files_ex3(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
+                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
+                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
+                                        int loader_flags) {
+    constexpr int kFlags = MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE |
+                           MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE;
+    // (Deflate strips on the device are a part of the TIFF device route, not a route of their own)
+    if ((loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE) && !(loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEVICE)) return MRGINGHAM_AMD_ERR_ARG;
+    if (nfiles < 0 || (loader_flags & ~kFlags) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
         o->blur_radius > 64 || o->device < -1 || nstats < 0 || (nstats > 0 && !stats) ||
         (nfiles > 0 && (!filenames || !h_boards || !h_levels || !h_found_level || !h_status)))
         return MRGINGHAM_AMD_ERR_ARG;
@@ -332,6 +345,8 @@ int mrgingham_amd_find_boards_files_ex2(const char* const* filenames, int nfiles
             if (mrgingham_amd_set_option(R.loader, "jpeg_entropy", 1) || mrgingham_amd_set_option(R.loader, "jpeg_sync", 1))
                 return MRGINGHAM_AMD_ERR_DEVICE;
         }
+        if ((loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE) && mrgingham_amd_set_option(R.loader, "tiff_deflate", 1))
+            return MRGINGHAM_AMD_ERR_DEVICE;
         const int nslots = nchunks < kRing ? nchunks : kRing;
         const size_t bytes = (size_t)R.batch * max_frame;
         for (int k = 0; k < nslots; ++k) {

@@ -2,6 +2,7 @@
 #include "image_io.h"
 #include "jpeg.h"
 #include "png_filter.h"
+#include "tiff_inflate.h"
 #include "tiff_lzw.h"
 #include "../../include/mrgingham_amd.h"
 
@@ -262,6 +263,11 @@ const uint16_t kTiffTagIds[kTags] = {256, 257, 258, 259, 262, 266, 273, 274, 277
 
 int tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info_out,
                 mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips_out) {
+    return tiff_layout_ex(data, nbytes, lzw_max_strip, 0, info_out, strips, capacity, nstrips_out);
+}
+
+int tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info_out,
+                   mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips_out) {
     if (nstrips_out) *nstrips_out = 0;
     if (!data || nbytes < 8) return -1;
     TiffReader r{data, nbytes, false};
@@ -329,7 +335,9 @@ int tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgin
     const uint32_t ns = (h + rps - 1) / rps;
     if (e[kTagStripOffsets].count != ns || e[kTagStripByteCounts].count != ns) return -1;
     const uint64_t rowb = (uint64_t)w * spp * (bits / 8);
-    bool taken = comp == 1 || comp == 5;
+    const bool deflate = comp == 8 || comp == 32946;
+    bool taken = comp == 1 || comp == 5 || (deflate && deflate_max_strip > 0);
+    if (deflate_max_strip > (int64_t)kTiffInflateMaxStrip) deflate_max_strip = (int64_t)kTiffInflateMaxStrip;
     if (lzw_max_strip <= 0 || lzw_max_strip > (int64_t)kTiffLzwMaxStrip20) lzw_max_strip = (int64_t)kTiffLzwMaxStrip20;
     for (uint32_t i = 0; i < ns; ++i) {
         const uint64_t off = r.value(e[kTagStripOffsets], i), cnt = r.value(e[kTagStripByteCounts], i);
@@ -340,8 +348,10 @@ int tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgin
         // anything is sized for them)
         if (comp == 5 && (cnt * 8 / 9 + 1) * 4096 < rows * rowb) return -1;
         if (comp == 32773 && cnt * 64 < rows * rowb) return -1;                       // (two bytes give at most 128)
-        if ((comp == 8 || comp == 32946) && (cnt + 1) * 1040 < rows * rowb) return -1;  // (Deflate: below 1032 to 1)
+        if (deflate && (cnt + 1) * 1040 < rows * rowb) return -1;  // (Deflate: below 1032 to 1)
         if (comp == 5 && rows * rowb > (uint64_t)lzw_max_strip) taken = false;
+        // (and not with more bytes than any zlib stream of its rows needs: a block need not give a byte, tiff_inflate.h)
+        if (deflate && taken && (rows * rowb > (uint64_t)deflate_max_strip || cnt > tiff_inflate_max_bytes(rows * rowb))) taken = false;
         if (strips && i < capacity) strips[i] = mrgingham_amd_tiff_strip{(int64_t)off, (int64_t)cnt, (int32_t)first, (int32_t)rows};
     }
     if (info_out)
@@ -612,6 +622,11 @@ extern "C" int mrgingham_amd_pgm_header(const uint8_t* data, size_t nbytes, int*
 extern "C" int mrgingham_amd_tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info,
                                          mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips) {
     return mrg::tiff_layout(data, nbytes, lzw_max_strip, info, strips, capacity, nstrips);
+}
+
+extern "C" int mrgingham_amd_tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip,
+                                            mrgingham_amd_tiff_info* info, mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips) {
+    return mrg::tiff_layout_ex(data, nbytes, lzw_max_strip, deflate_max_strip, info, strips, capacity, nstrips);
 }
 
 extern "C" int mrgingham_amd_png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan_capacity, int* width,

@@ -60,6 +60,9 @@ int png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan
 constexpr int kTiffNotTaken = -3;
 int tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info,
                 mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips);
+// the same with Deflate files taken whose strips decode to at most deflate_max_strip bytes (<= 0: none, tiff_layout)
+int tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info,
+                   mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips);
 // The IHDR fields of a PNG file as they stand, nothing judged (a routing hint: png_scanlines decides what is readable):
 // returns the colour type byte, -1 for a file that does not begin with a PNG signature and a whole IHDR.
 int png_header(const char* path, int* width, int* height, int* bits);

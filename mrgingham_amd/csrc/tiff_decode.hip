@@ -1,7 +1,8 @@
 // TIFF on the device: the LZW strips of a batch of files decoded one lane per strip (tiff_lzw.h, the host decoder's text),
-// the rows put into value order, predictor 2 undone and the samples reduced to grey, and the batch loader that reads the
-// files straight into page-locked staging.  See include/mrgingham_amd.h for the contract of the entry points and
-// DESIGN.md section 4.14 for the schedule and the numbers.
+// Deflate strips likewise (tiff_inflate.h, zlib's contract), the rows put into value order, predictor 2 undone and the
+// samples reduced to grey, and the batch loader that reads the files straight into page-locked staging.  See
+// include/mrgingham_amd.h for the contract of the entry points and DESIGN.md sections 4.14 and 4.15 for the schedule and
+// the numbers.
 #include <stdio.h>
 #include <string.h>
 
@@ -11,6 +12,7 @@
 #include "image_io.h"
 #include "loader.h"
 #include "png_filter.h"
+#include "tiff_inflate.h"
 #include "tiff_lzw.h"
 
 using namespace mrg;
@@ -23,6 +25,14 @@ namespace {
 constexpr int kLzwLanes = 16384;
 constexpr int kLzwBlock = 64;      // one wave per workgroup: a wave runs as long as its longest strip, a workgroup no longer
 static_assert((size_t)kLzwLanes * kTiffLzwCodes * sizeof(uint32_t) == (size_t)256 << 20, "the table scratch bound stated in the header");
+// Deflate: the same schedule with more lanes.  Every lane has kTiffInflateWords 16-bit words (decode tables and the
+// code-length work area) in context scratch, interleaved by lane: kInflateLanes x 2560 bytes = 320 MiB bounds that scratch.
+// A lane waits for memory at nearly every symbol, so the launch lives on the number of lanes in flight: measured on 98304
+// strips of 8 KiB, 16384 lanes took 100 ms, 32768 61 ms, 65536 49 ms, 131072 35 ms.
+constexpr int kInflateLanes = 131072;
+constexpr int kInflateBlock = 64;
+static_assert((size_t)kInflateLanes * kTiffInflateWords * sizeof(uint16_t) == (size_t)320 << 20, "the table scratch bound stated in the header");
+enum { kCodecNone = 0, kCodecLzw = 1, kCodecDeflate = 2 };
 // finish: a wave per row, a lane per kSegPx pixels of it, kStepPx pixels per step of the wave
 constexpr int kSegPx = 16;
 constexpr int kWave = 64;
@@ -31,11 +41,11 @@ constexpr int kFinishBlock = 256;
 
 // One lane per strip slot (frame * strips_pitch + index), behind a memset of `status`: the strip table of every frame against
 // what the two kernels below rely on -- strips in row order, rps = the first strip's rows each (the last one the rest),
-// every strip inside its file's area, an uncompressed strip long enough for its rows, an LZW strip decoding to at most
-// 1 MiB.  A lane that finds a fault in its frame's counts or in its own strip stores -1 into status[f] (every such lane
+// every strip inside its file's area, an uncompressed strip long enough for its rows, an LZW or Deflate strip decoding to
+// at most 1 MiB, a Deflate strip of no more bytes than tiff_inflate_max_bytes allows (they bound its lane's work).  A lane that finds a fault in its frame's counts or in its own strip stores -1 into status[f] (every such lane
 // the same value): the frame is zero-filled.
 __global__ void tiff_check_kernel(const mrgingham_amd_tiff_strip* strips, int strips_pitch, const int32_t* nstrips, int nframes,
-                                  int height, uint32_t rowb, long long file_pitch, int lzw, int32_t* status) {
+                                  int height, uint32_t rowb, long long file_pitch, int codec, int32_t* status) {
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= (long long)nframes * strips_pitch) return;
     const int f = (int)(s / strips_pitch), i = (int)(s - (long long)f * strips_pitch);
@@ -50,7 +60,9 @@ __global__ void tiff_check_kernel(const mrgingham_amd_tiff_strip* strips, int st
             const unsigned long long need = (unsigned long long)rows * rowb;
             ok = t[i].first_row == first && t[i].rows == rows && t[i].offset >= 0 && t[i].nbytes >= 0 && t[i].offset <= file_pitch &&
                  t[i].nbytes <= file_pitch - t[i].offset && t[i].nbytes <= 0xFFFFFFFFll &&
-                 (lzw ? need <= kTiffLzwMaxStrip20 : (unsigned long long)t[i].nbytes >= need);
+                 (codec == kCodecLzw       ? need <= kTiffLzwMaxStrip20
+                  : codec == kCodecDeflate ? need <= kTiffInflateMaxStrip && (unsigned long long)t[i].nbytes <= tiff_inflate_max_bytes(need)
+                                           : (unsigned long long)t[i].nbytes >= need);
         }
     }
     if (!ok) status[f] = -1;
@@ -81,7 +93,31 @@ __global__ __launch_bounds__(kLzwBlock) void tiff_lzw_kernel(const uint8_t* file
     }
 }
 
-// behind the LZW launch: a frame with a broken strip gets status -1
+// The Deflate strips, scheduled as the LZW ones are: a lane reads src[0, nbytes) of its strip, writes the rows x rowb bytes
+// of its strip in `raw` and keeps its tables at table[lane + i * lanes], i < kTiffInflateWords -- the bounds are
+// arguments of tiff_inflate_decode, checked by tiff_check_kernel, and a copy never reaches before the strip's own first byte.
+__global__ __launch_bounds__(kInflateBlock) void tiff_inflate_kernel(const uint8_t* files, long long file_pitch,
+                                                                     const mrgingham_amd_tiff_strip* strips, int strips_pitch,
+                                                                     const int32_t* nstrips, int nframes, uint32_t rowb, uint8_t* raw,
+                                                                     long long raw_pitch, uint16_t* table, int32_t* status,
+                                                                     int32_t* strip_status, int32_t* broken) {
+    const uint32_t lanes = gridDim.x * blockDim.x, lane = blockIdx.x * blockDim.x + threadIdx.x;
+    TiffInflateStridedTable tab{table + lane, lanes};
+    const long long total = (long long)nframes * strips_pitch;
+    for (long long s = lane; s < total; s += lanes) {
+        const int f = (int)(s / strips_pitch), i = (int)(s - (long long)f * strips_pitch);
+        int rc = 0;
+        if (status[f] == 0 && i < nstrips[f]) {
+            const mrgingham_amd_tiff_strip st = strips[s];
+            rc = tiff_inflate_decode(files + f * file_pitch + st.offset, (uint32_t)st.nbytes, raw + f * raw_pitch + (long long)st.first_row * rowb,
+                                     (uint32_t)st.rows * rowb, tab);
+            if (rc) broken[f] = 1;
+        }
+        if (strip_status) strip_status[s] = rc;
+    }
+}
+
+// behind the LZW or Deflate launch: a frame with a broken strip gets status -1
 __global__ void tiff_verdict_kernel(const int32_t* broken, int nframes, int32_t* status) {
     const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (f < nframes && broken[f]) status[f] = -1;
@@ -226,37 +262,49 @@ __global__ __launch_bounds__(kFinishBlock) void tiff_finish_kernel(const uint8_t
 bool tiff_info_ok(const mrgingham_amd_tiff_info& t) {
     return t.width >= 1 && t.height >= 1 && t.width <= 32767 && t.height <= 32767 && (t.bits == 8 || t.bits == 16) && t.samples >= 1 &&
            t.samples <= 4 && t.photometric >= 0 && t.photometric <= 2 && (t.photometric != 2 || t.samples >= 3) &&
-           (t.compression == 1 || t.compression == 5) && (t.predictor == 1 || t.predictor == 2) && (t.big_endian == 0 || t.big_endian == 1);
+           (t.compression == 1 || t.compression == 5 || t.compression == 8 || t.compression == 32946) && (t.predictor == 1 || t.predictor == 2) && (t.big_endian == 0 || t.big_endian == 1);
 }
 
 int lzw_lanes_of(const mrgingham_amd_ctx* ctx) { return ctx->tiff_lzw_lanes > 0 ? ctx->tiff_lzw_lanes : kLzwLanes; }
+int inflate_lanes_of(const mrgingham_amd_ctx* ctx) { return ctx->tiff_deflate_lanes > 0 ? ctx->tiff_deflate_lanes : kInflateLanes; }
+int codec_of(const mrgingham_amd_tiff_info& t) { return t.compression == 5 ? kCodecLzw : t.compression == 1 ? kCodecNone : kCodecDeflate; }
 
-// checked arguments -> the launches; grows the LZW scratch
+// checked arguments -> the launches; grows the LZW / Deflate scratch
 int launch_tiff_decode(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch, const mrgingham_amd_tiff_strip* d_strips,
                        int strips_pitch, const int32_t* d_nstrips, int nframes, const mrgingham_amd_tiff_info& ti, void* d_out,
                        int64_t frame_pitch, int stride, int32_t* d_status, int32_t* d_strip_status, hipStream_t s) {
     const int width = ti.width, height = ti.height, bpp = ti.samples * ti.bits / 8;
     const uint32_t rowb = (uint32_t)width * bpp;
-    const bool lzw = ti.compression == 5;
+    const int codec = codec_of(ti);
+    const bool lzw = codec == kCodecLzw, from_raw = codec != kCodecNone;
     const unsigned frame_blocks = (unsigned)((nframes + 63) / 64);
     const long long slots = (long long)nframes * strips_pitch;
     MRG_HIP_CHECK(hipMemsetAsync(d_status, 0, (size_t)nframes * sizeof(int32_t), s));
     hipLaunchKernelGGL(tiff_check_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, d_strips, strips_pitch, d_nstrips, nframes, height,
-                       rowb, (long long)file_pitch, lzw ? 1 : 0, d_status);
+                       rowb, (long long)file_pitch, codec, d_status);
     const uint8_t* src = d_files;
     long long src_pitch = file_pitch;
-    if (lzw) {
+    if (from_raw) {
+        static_assert(kLzwBlock == kInflateBlock, "one rounding of the lanes for both");
         const long long raw_pitch = ((long long)rowb * height + 15) & ~15ll;
+        const int most = lzw ? lzw_lanes_of(ctx) : inflate_lanes_of(ctx);
         long long lanes = (slots + kLzwBlock - 1) / kLzwBlock * kLzwBlock;
-        if (lanes > lzw_lanes_of(ctx)) lanes = lzw_lanes_of(ctx);
+        if (lanes > most) lanes = most;
         int rc;
         if ((rc = ensure(ctx, ctx->tiff_raw, (size_t)nframes * (size_t)raw_pitch))) return rc;
-        if ((rc = ensure(ctx, ctx->tiff_table, (size_t)lanes * kTiffLzwCodes * sizeof(uint32_t)))) return rc;
+        if (lzw) rc = ensure(ctx, ctx->tiff_table, (size_t)lanes * kTiffLzwCodes * sizeof(uint32_t));
+        else rc = ensure(ctx, ctx->tiff_inflate_table, (size_t)lanes * kTiffInflateWords * sizeof(uint16_t));
+        if (rc) return rc;
         if ((rc = ensure(ctx, ctx->tiff_broken, (size_t)nframes * sizeof(int32_t)))) return rc;
         MRG_HIP_CHECK(hipMemsetAsync(ctx->tiff_broken.p, 0, (size_t)nframes * sizeof(int32_t), s));
-        hipLaunchKernelGGL(tiff_lzw_kernel, dim3((unsigned)(lanes / kLzwBlock)), dim3(kLzwBlock), 0, s, d_files, (long long)file_pitch, d_strips,
-                           strips_pitch, d_nstrips, nframes, rowb, (uint8_t*)ctx->tiff_raw.p, raw_pitch, (uint32_t*)ctx->tiff_table.p, d_status,
-                           d_strip_status, (int32_t*)ctx->tiff_broken.p);
+        if (lzw)
+            hipLaunchKernelGGL(tiff_lzw_kernel, dim3((unsigned)(lanes / kLzwBlock)), dim3(kLzwBlock), 0, s, d_files, (long long)file_pitch, d_strips,
+                               strips_pitch, d_nstrips, nframes, rowb, (uint8_t*)ctx->tiff_raw.p, raw_pitch, (uint32_t*)ctx->tiff_table.p, d_status,
+                               d_strip_status, (int32_t*)ctx->tiff_broken.p);
+        else
+            hipLaunchKernelGGL(tiff_inflate_kernel, dim3((unsigned)(lanes / kInflateBlock)), dim3(kInflateBlock), 0, s, d_files, (long long)file_pitch,
+                               d_strips, strips_pitch, d_nstrips, nframes, rowb, (uint8_t*)ctx->tiff_raw.p, raw_pitch,
+                               (uint16_t*)ctx->tiff_inflate_table.p, d_status, d_strip_status, (int32_t*)ctx->tiff_broken.p);
         hipLaunchKernelGGL(tiff_verdict_kernel, dim3(frame_blocks), dim3(64), 0, s, (const int32_t*)ctx->tiff_broken.p, nframes, d_status);
         src = (const uint8_t*)ctx->tiff_raw.p;
         src_pitch = raw_pitch;
@@ -269,7 +317,7 @@ int launch_tiff_decode(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t f
     if (blocks > (long long)cus * 8) blocks = (long long)cus * 8;
 #define MRG_TIFF_CASE(B, C)                                                                                                              \
     hipLaunchKernelGGL((tiff_finish_kernel<B, C>), dim3((unsigned)blocks), dim3(kFinishBlock), 0, s, src, src_pitch, limit, d_strips,      \
-                       strips_pitch, lzw ? 1 : 0, width, height, nrows, ti.photometric == 2 ? 1 : 0, ti.photometric == 0 ? 1 : 0,           \
+                       strips_pitch, from_raw ? 1 : 0, width, height, nrows, ti.photometric == 2 ? 1 : 0, ti.photometric == 0 ? 1 : 0,           \
                        ti.predictor == 2 ? 1 : 0, ti.big_endian, d_out, (long long)frame_pitch, stride, (const int32_t*)d_status)
     const int ch = ti.samples;
     if (ti.bits == 8) {
@@ -284,13 +332,15 @@ int launch_tiff_decode(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t f
 
 // what makes two files of a chunk share a launch
 uint32_t launch_key(const mrgingham_amd_tiff_info& t) {
-    return (uint32_t)t.samples | (uint32_t)t.photometric << 4 | (uint32_t)(t.compression == 5) << 8 | (uint32_t)t.predictor << 12 |
+    return (uint32_t)t.samples | (uint32_t)t.photometric << 4 | (uint32_t)codec_of(t) << 8 | (uint32_t)t.predictor << 12 |
            (uint32_t)t.big_endian << 16;
 }
 
 }  // namespace
 
 extern "C" {
+
+int mrgingham_amd_tiff_inflate_lanes(void) { return kInflateLanes; }
 
 void mrgingham_amd_tiff_geometry(int* lzw_lanes, int* segment_pixels, int* step_pixels) {
     if (lzw_lanes) *lzw_lanes = kLzwLanes;
@@ -307,7 +357,7 @@ int mrgingham_amd_tiff_decode_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_fil
         (nframes > 0 && (!d_files || !d_strips || !d_nstrips || !d_out || !d_status)))
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad TIFF batch descriptor");
     if (!tiff_info_ok(*info) || stride < info->width)
-        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "TIFF batch: sides 1..32767, 8 or 16 bits, 1..4 samples, photometric 0..2, compression 1 or 5, predictor 1 or 2, stride >= width");
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "TIFF batch: sides 1..32767, 8 or 16 bits, 1..4 samples, photometric 0..2, compression 1, 5, 8 or 32946, predictor 1 or 2, stride >= width");
     if ((file_pitch & 15) || ((uintptr_t)d_files & 15) || ((uintptr_t)d_strips & 7) || ((uintptr_t)d_nstrips & 3) || ((uintptr_t)d_status & 3) ||
         ((uintptr_t)d_strip_status & 3) || (info->bits == 16 && ((uintptr_t)d_out & 1)))
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "TIFF batch: files 16-byte aligned, file_pitch a multiple of 16; 16-bit frames 2-byte aligned");
@@ -355,7 +405,7 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
     const size_t off_strips = (size_t)chunk * area, off_ns = off_strips + (size_t)chunk * height * sizeof(mrgingham_amd_tiff_strip),
                  off_status = off_ns + (size_t)chunk * sizeof(int32_t), slot_bytes = off_status + (size_t)chunk * sizeof(int32_t);
     hipStream_t s = ctx->pix;
-    const int64_t max_strip = ctx->tiff_lzw_max_strip;
+    const int64_t max_strip = ctx->tiff_lzw_max_strip, deflate_strip = ctx->tiff_deflate ? ctx->tiff_deflate_max_strip : 0;
     // per slot and file of its chunk: -1 failed, 0 decoded on the host (its samples lie in its area), 1 the device's
     struct InSlot { int f0 = 0, n = 0; std::vector<int> kind; std::vector<mrgingham_amd_tiff_info> info; } in_slot[2];
     struct Buffers { std::vector<uint8_t> file; Image im; };
@@ -385,9 +435,9 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
                     fclose(f);
                     if (whole) {
                         staged = true;
-                        head = tiff_layout(dst, got, max_strip, &ti, h_strips + (size_t)i * height, (size_t)height, &ns);
+                        head = tiff_layout_ex(dst, got, max_strip, deflate_strip, &ti, h_strips + (size_t)i * height, (size_t)height, &ns);
                     } else if (read_file(filenames[f0 + i], t.file)) {
-                        head = tiff_layout(t.file.data(), t.file.size(), max_strip, &ti, nullptr, 0, &ns);
+                        head = tiff_layout_ex(t.file.data(), t.file.size(), max_strip, deflate_strip, &ti, nullptr, 0, &ns);
                         if (head == 0) head = kTiffNotTaken;
                     }
                 }
@@ -397,7 +447,7 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
                     else if (head == 0 && staged) {
                         h_ns[i] = (int32_t)ns;
                         kind = 1;
-                        st = 0;  // (an LZW strip may still break a rule: known when the chunk has passed the stream)
+                        st = 0;  // (an LZW or Deflate strip may still break a rule: known when the chunk has passed the stream)
                     } else if (head != -2 && read_image(filenames[f0 + i], t.im) && t.im.depth == bits && t.im.w == width && t.im.h == height) {
                         // the device route does not take it: the host decoder's samples
                         memcpy(dst, bits == 8 ? (const void*)t.im.px8.data() : (const void*)t.im.px16.data(), px_bytes);

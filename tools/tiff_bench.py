@@ -1,10 +1,10 @@
 """What the TIFF device route (tiff_decode.hip, mrgingham_amd_read_tiffs_batch) costs and buys at 12 MP:
 
-    python tools/tiff_bench.py [--rounds 3] [--jobs 16] [--frames 64] [--out profiles/tiff_bench.json]
+    python tools/tiff_bench.py [--rounds 3] [--jobs 16] [--frames 64] [--codec lzw|deflate|both] [--out profiles/tiff_bench.json; --codec deflate: profiles/tiff_deflate_bench.json]
 
 Files: two 4096x3072 frames (synth.board_frame plus noise), 8 bit and 16 bit, written by Pillow's libtiff into a RAM-backed
 directory -- LZW with predictor 2 at 2, 16 and 256 rows per strip (8 KiB, 64 KiB and 1 MiB decoded per strip at 8 bit) and
-uncompressed.
+uncompressed (--codec lzw, the default); with --codec deflate or both the same files as Deflate (Pillow's tiff_adobe_deflate) with predictor 2.
 1. The launches alone: `--frames` files uploaded once, mrgingham_amd_tiff_decode_batch between two device events (two
    warm-up calls, the median of ten), its output checked against the source array.  On an LZW file that is the check
    kernel, the LZW kernel (one lane per strip) and the finish kernel; on the same pixels uncompressed it is the check and
@@ -14,7 +14,9 @@ uncompressed.
 2. The loader: `--frames` names over the two files through Detector.read_tiffs with `--jobs` host threads, at every strip
    size of the sweep: the device route (option "tiff_lzw_max_strip" at its limit, 1 MiB, so that every file is taken)
    against the same call with every file forced to the host decoder (the option at 1), alternating, `--rounds` times in
-   one process; frames per second of wall time.  These pairs are what the option's default is read from.
+   one process; frames per second of wall time.  These pairs are what the option's default is read from.  The Deflate
+   legs: read_tiffs(deflate="device") with option "tiff_deflate_max_strip" at 1 MiB against read_tiffs(deflate="host"), which
+   leaves every Deflate file to the host threads and zlib.
 One JSON document."""
 import ctypes
 import json
@@ -46,21 +48,24 @@ def board(seed, bits):
     return img.astype(np.uint8) if bits == 8 else (img * 257 + rng.integers(0, 64, grey.shape)).astype(np.uint16)
 
 
-def write_files(scratch):
+PILLOW_NAME = {"lzw": "tiff_lzw", "deflate": "tiff_adobe_deflate"}
+
+
+def write_files(scratch, codecs):
     from PIL import Image
     files, source = {}, {}
     for bits in (8, 16):
         for seed in (1, 2):
             img = board(seed, bits)
             source[bits, seed] = img
-            for name, kw in (("lzw_rows2", dict(compression="tiff_lzw", tiffinfo={317: 2, 278: 2})),
-                             ("lzw_rows16", dict(compression="tiff_lzw", tiffinfo={317: 2, 278: 16})),
-                             ("lzw_rows256", dict(compression="tiff_lzw", tiffinfo={317: 2, 278: 256})),
-                             ("none", dict(tiffinfo={278: 2}))):
-                if bits == 16 and name in ("lzw_rows16", "lzw_rows256"):
+            variants = [("none", dict(tiffinfo={278: 2}))]
+            for codec in codecs:
+                variants += [(f"{codec}_rows{rows}", dict(compression=PILLOW_NAME[codec], tiffinfo={317: 2, 278: rows})) for rows in (2, 16, 256)]
+            for name, kw in variants:
+                if bits == 16 and name.endswith(("_rows16", "_rows256")):
                     continue
-                if bits == 16 and name == "lzw_rows2":
-                    kw = dict(compression="tiff_lzw", tiffinfo={317: 2, 278: 1})     # 8 KiB decoded per strip at 16 bit
+                if bits == 16 and name.endswith("_rows2"):
+                    kw = dict(kw, tiffinfo={317: 2, 278: 1})     # 8 KiB decoded per strip at 16 bit
                 p = os.path.join(scratch, f"b{bits}_{name}_{seed}.tif")
                 Image.fromarray(img).save(p, "TIFF", **kw)
                 files[bits, name, seed] = p
@@ -72,7 +77,7 @@ def launch_ms(det, datas, want, frames):
     import torch
     import mrgingham_amd
     from mrgingham_amd import _lib, api
-    lays = [mrgingham_amd.tiff_layout(d) for d in datas]
+    lays = [mrgingham_amd.tiff_layout(d, deflate_max_strip=1 << 20) for d in datas]
     assert all(l is not None and l.taken for l in lays) and len({l.key() for l in lays}) == 1
     lay, P = lays[0], max(l.nstrips for l in lays)
     pitch = (max(len(d) for d in datas) + 15) // 16 * 16
@@ -116,16 +121,20 @@ def launch_ms(det, datas, want, frames):
 def main(args):
     import torch
     import mrgingham_amd
+    from mrgingham_amd import _lib
     rounds, jobs, frames = int(opts(args, "--rounds", "3")), int(opts(args, "--jobs", "16")), int(opts(args, "--frames", "64"))
-    out_path = opts(args, "--out", os.path.join(ROOT, "profiles", "tiff_bench.json"))
+    codecs = {"lzw": ["lzw"], "deflate": ["deflate"], "both": ["lzw", "deflate"]}[opts(args, "--codec", "lzw")]
+    out_path = opts(args, "--out", os.path.join(ROOT, "profiles", "tiff_deflate_bench.json" if codecs == ["deflate"] else "tiff_bench.json"))
+    cases = [(8, f"{c}_rows{r}") for c in codecs for r in (2, 16, 256)] + [(8, "none")] + [(16, f"{c}_rows2") for c in codecs] + [(16, "none")]
     doc = {"device": torch.cuda.get_device_name(0), "jobs": jobs, "rounds": rounds, "frames": frames, "frame": [W, H],
-           "hbm_peak_bytes_per_s": HBM_PEAK, "geometry_lanes_segment_step": list(mrgingham_amd.tiff_geometry())}
+           "hbm_peak_bytes_per_s": HBM_PEAK, "geometry_lanes_segment_step": list(mrgingham_amd.tiff_geometry()), "codecs": codecs,
+           "inflate_lanes": _lib.lib().mrgingham_amd_tiff_inflate_lanes()}
     scratch = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     det = mrgingham_amd.Detector(0)
     try:
-        files, source = write_files(scratch)
+        files, source = write_files(scratch, codecs)
         doc["launches"] = {}
-        for bits, name in ((8, "lzw_rows2"), (8, "lzw_rows16"), (8, "lzw_rows256"), (8, "none"), (16, "lzw_rows2"), (16, "none")):
+        for bits, name in cases:
             datas = [open(files[bits, name, seed], "rb").read() for seed in (1, 2)]
             r = launch_ms(det, datas, [source[bits, 1], source[bits, 2]], frames)
             if name == "none":
@@ -134,25 +143,30 @@ def main(args):
                 r["finish_fraction_of_hbm_peak"] = round(r["finish_bytes_per_launch"] / t / HBM_PEAK, 4)
             doc["launches"][f"b{bits}_{name}"] = r
             print(f"launch b{bits}_{name}: {r['ms_per_launch']} ms per {frames} frames", file=sys.stderr, flush=True)
-        for bits in (8, 16):
-            lz, no = doc["launches"][f"b{bits}_lzw_rows2"], doc["launches"][f"b{bits}_none"]
-            lz["lzw_launch_ms_by_difference"] = round(lz["ms_per_launch"] - no["ms_per_launch"], 3)
+        for bits, name in cases:      # the check and the finish kernel run on the uncompressed pixels too: the rest is the strip launch
+            if name != "none":
+                r, no = doc["launches"][f"b{bits}_{name}"], doc["launches"][f"b{bits}_none"]
+                r[name.split("_")[0] + "_launch_ms_by_difference"] = round(r["ms_per_launch"] - no["ms_per_launch"], 3)
         doc["loader"] = {}
-        for bits, name in ((8, "lzw_rows2"), (8, "lzw_rows16"), (8, "lzw_rows256"), (8, "none"), (16, "lzw_rows2"), (16, "none")):
+        for bits, name in cases:
             paths = [files[bits, name, 1 + i % 2] for i in range(frames)]
+            deflate = name.startswith("deflate")
             legs = {"device": 1 << 20} if name == "none" else {"device": 1 << 20, "host_forced": 1}
             walls = {leg: [] for leg in legs}
+            det.set_option("tiff_deflate_max_strip", 1 << 20)
             for r in range(rounds + 1):               # (round 0 warms the staging up and is dropped)
                 for leg, max_strip in legs.items():
-                    det.set_option("tiff_lzw_max_strip", max_strip)
+                    if not deflate:
+                        det.set_option("tiff_lzw_max_strip", max_strip)
                     t0 = time.perf_counter()
-                    fr, status = det.read_tiffs(paths, nthreads=jobs)
+                    fr, status = det.read_tiffs(paths, nthreads=jobs, deflate="device" if deflate and leg == "device" else "host")
                     wall = time.perf_counter() - t0
                     assert not status.any() and np.array_equal(fr[1].cpu().numpy(), source[bits, 2])
                     del fr
                     if r:
                         walls[leg].append(wall)
             det.set_option("tiff_lzw_max_strip", 64 << 10)
+            det.set_option("tiff_deflate_max_strip", 8 << 10)
             doc["loader"][f"b{bits}_{name}"] = {leg: {"frames_per_s": round(frames / statistics.median(w), 1),
                                                       "frames_per_s_rounds": [round(frames / v, 1) for v in w]} for leg, w in walls.items()}
             print(f"loader b{bits}_{name}: {doc['loader'][f'b{bits}_{name}']}", file=sys.stderr, flush=True)
