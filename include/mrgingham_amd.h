@@ -67,7 +67,11 @@ extern "C" {
  *      mrgingham_amd_tiff_decode_batch takes compression 8 and 32946 (Deflate strips on the device); options "tiff_deflate",
  *      "tiff_deflate_max_strip", "tiff_deflate_lanes"; mrgingham_amd_find_boards_files_ex3 (loader flag
  *      MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE).  Off unless asked for: mrgingham_amd_tiff_layout goes on leaving Deflate
- *      files to the host decoder. */
+ *      files to the host decoder.
+ *      Later, additive (the version stays 4): mrgingham_amd_tiff_layout_tiled and _tiff_decode_batch_tiled (tiled TIFF:
+ *      LZW and Deflate tiles one lane each, tile rows gathered into image rows on the device); mrgingham_amd_read_image,
+ *      _probe_image, _read_tiffs_batch and the file-list entry points read tiled files, which were unreadable before.
+ *      mrgingham_amd_tiff_layout and _tiff_layout_ex go on calling any tile tag unreadable, and no option changes. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -359,8 +363,8 @@ bool find_chessboard_from_image_file_C(const char* filename, const int gridn, in
 
 /* The image decoder behind the two functions above and the command-line tool, on its own (host only, no
  * device needed): binary PGM (8 / 16 bit), non-interlaced PNG, baseline JPEG (see
- * mrgingham_amd_jpeg_coefficients for what is accepted) and strip TIFF (see mrgingham_amd_tiff_layout for
- * what is accepted).  `out` (may be NULL: sizes only)
+ * mrgingham_amd_jpeg_coefficients for what is accepted) and strip or tiled TIFF (see mrgingham_amd_tiff_layout
+ * and _tiff_layout_tiled for what is accepted).  `out` (may be NULL: sizes only)
  * receives width*height grey bytes.  16-bit samples: cli_scaling = 0 keeps the high byte, what
  * cv::imread(IMREAD_GRAYSCALE) gives the file entry points; 1 rescales by 255/65535 with rounding, what
  * the CLI's convertTo does (mrgingham-from-image.cc:85-92).  Returns 0; -1 unreadable, unsupported or
@@ -550,7 +554,8 @@ int mrgingham_amd_read_pgms_batch(mrgingham_amd_ctx* ctx, const char* const* fil
  *   BitsPerSample 8 or 16, one value per sample, all equal; SampleFormat absent or 1; SamplesPerPixel 1 .. 4 (samples
  *   behind the first -- grey -- or the third -- RGB -- are extra samples and ignored); PlanarConfiguration, FillOrder and
  *   Orientation absent or 1; Photometric 0 (WhiteIsZero: read as maxval - v), 1, or 2 (RGB, at least 3 samples: grey is
- *   (R*4899 + G*9617 + B*1868 + 8192) >> 14); strips only (any tile tag: unreadable), RowsPerStrip absent or above the
+ *   (R*4899 + G*9617 + B*1868 + 8192) >> 14); strips only HERE (any tile tag: unreadable to this function and to
+ *   _tiff_layout_ex; mrgingham_amd_tiff_layout_tiled reads tiled files), RowsPerStrip absent or above the
  *   height = one strip, the last strip may be short, strips lie anywhere in the file in any order; sides 1 .. 32767;
  *   Compression 1 (none), 5 (LZW: MSB-first codes of 9 .. 12 bits, ClearCode 256, EOI 257, the width growing one code
  *   early), 32773 (PackBits, a run never crossing its row), 8 and 32946 (Deflate); Predictor absent, 1 or 2 (horizontal
@@ -592,6 +597,29 @@ int mrgingham_amd_tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw
                                  mrgingham_amd_tiff_info* info, mrgingham_amd_tiff_strip* strips, size_t capacity,
                                  size_t* nstrips);
 
+/* mrgingham_amd_tiff_layout_ex that also reads TILED files: the parser behind mrgingham_amd_read_image, _probe_image and
+ * _read_tiffs_batch.  (mrgingham_amd_tiff_layout and _tiff_layout_ex go on calling a file with any tile tag unreadable:
+ * their callers hand the records to mrgingham_amd_tiff_decode_batch, which would read tiles as strips.)
+ * A file is tiled when TileWidth (322), TileLength (323), TileOffsets (324) and TileByteCounts (325) are all present and
+ * neither StripOffsets nor StripByteCounts is; any other mixture of tile and strip tags is unreadable.  RowsPerStrip in a
+ * tiled file is ignored.  Everything else of the subset above holds, and on top of it: tile width tw and length tl
+ * 1 .. 32767 each (any value, multiples of 16 or not); across = ceil(width / tw), down = ceil(height / tl), and both count
+ * tags hold exactly across x down values; tile i (row-major) covers the image's rows from (i / across) x tl and its columns
+ * from (i % across) x tw; every tile decodes to exactly tl x tw x samples x bits/8 bytes -- tiles at the right and bottom
+ * edges are padded to the full size, and the padding may hold anything; predictor 2 runs along each row OF A TILE and
+ * restarts at every tile's left edge; PackBits runs do not cross a tile's row.  The rules on a byte count that cannot give
+ * its rows hold per tile, with the tile's full size.
+ * A strip file: exactly mrgingham_amd_tiff_layout_ex, with *tile_width = *tile_length = 0.  A tiled file: *tile_width = tw,
+ * *tile_length = tl, record i is tile i with first_row = (i / across) x tl and rows = tl (what it decodes to, not what the
+ * image keeps of it), *nrecords = across x down.  Returns 0 when mrgingham_amd_tiff_decode_batch_tiled takes the file: tw a
+ * multiple of 16, compression 1, or 5 with every tile decoding to at most lzw_max_strip bytes, or 8 / 32946 with
+ * deflate_max_strip > 0, every tile decoding to at most that and held in no more bytes than its decoded size plus an
+ * eighth plus 512; otherwise MRGINGHAM_AMD_TIFF_NOT_TAKEN, -1 or -2 as above.  tile_width and tile_length may be NULL (a
+ * tiled file is read all the same).  Never throws, allocates nothing, never reads out of bounds on a crafted file. */
+int mrgingham_amd_tiff_layout_tiled(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip,
+                                    mrgingham_amd_tiff_info* info, int32_t* tile_width, int32_t* tile_length,
+                                    mrgingham_amd_tiff_strip* records, size_t capacity, size_t* nrecords);
+
 /* TIFF, device half: nframes files of ONE size, depth, sample count, photometric, compression (1, 5, or 8 / 32946),
  * predictor and byte order (`info`, HOST; what mrgingham_amd_tiff_layout or _tiff_layout_ex reported for every one of them) from their bytes to grey frames,
  * byte for byte what mrgingham_amd_read_image computes.  d_files: file f's bytes at d_files + f*file_pitch (BYTES; d_files
@@ -618,6 +646,25 @@ int mrgingham_amd_tiff_decode_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_fil
                                     int nframes, const mrgingham_amd_tiff_info* info, void* d_out, int64_t frame_pitch,
                                     int stride, int32_t* d_status, int32_t* d_strip_status, void* stream);
 
+/* mrgingham_amd_tiff_decode_batch for tiled files: nframes files that also agree in tile_width and tile_length, d_records
+ * what mrgingham_amd_tiff_layout_tiled wrote for them (record i = tile i).  tile_width == tile_length == 0 is
+ * mrgingham_amd_tiff_decode_batch.  MRGINGHAM_AMD_ERR_ARG, nothing written: only one of the two is 0, tile_width is not a
+ * multiple of 16, either is negative or above 32767.  Everything else as above: the alignment rules, the status words (-1
+ * also for a frame whose record count is not across x down, or with a record whose first_row is not (i / across) x
+ * tile_length or whose rows is not tile_length, or a tile decoding to more than 1 MiB), d_strip_status per TILE, failed
+ * frames zero-filled, asynchronous on `stream`.  tiff_lzw_kernel / tiff_inflate_kernel decode tile i of frame f to context
+ * scratch at f*raw_pitch + i * tile bytes, dense and tile-major (nframes x across x down x tile bytes, which may be well above
+ * the samples of the frames where the edge tiles are mostly padding), a lane writing its own tile's bytes alone.  Then
+ * tiff_finish_tiles_kernel, one wave per image row: lane l takes 16 pixels, which lie in one tile because tile_width is a
+ * multiple of 16, from that tile's row in the scratch or -- compression 1 -- in the file's bytes at any byte address; the
+ * prefix sum of predictor 2 is a segmented scan that restarts at every tile's left edge; columns at or beyond the width and
+ * tile rows at or beyond the height are never stored. */
+int mrgingham_amd_tiff_decode_batch_tiled(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch,
+                                          const mrgingham_amd_tiff_strip* d_records, int records_pitch,
+                                          const int32_t* d_nrecords, int nframes, const mrgingham_amd_tiff_info* info,
+                                          int tile_width, int tile_length, void* d_out, int64_t frame_pitch, int stride,
+                                          int32_t* d_status, int32_t* d_strip_status, void* stream);
+
 /* The constants of those kernels' schedules, for tests that place their shapes on the seams: the lanes in flight of the
  * LZW launch (strip s is decoded by lane s modulo that many; option "tiff_lzw_lanes" lowers it), the pixels of a row a
  * lane of the finish kernel takes, and the pixels of a row a wave takes per step (the prefix sum of predictor 2 is carried
@@ -634,7 +681,14 @@ int mrgingham_amd_tiff_inflate_lanes(void);
  * while the host threads read the next.  A file the device route does not take (MRGINGHAM_AMD_TIFF_NOT_TAKEN, or a file
  * much larger than its samples) is decoded by the host thread with mrgingham_amd_read_image's decoder and uploaded: same
  * bytes.  Deflate files are among those unless option "tiff_deflate" is 1: then the layouts come from
- * mrgingham_amd_tiff_layout_ex with option "tiff_deflate_max_strip", and a file with a larger strip keeps the host thread.  h_status[f]: 0 decoded, -1 unreadable / unsupported / malformed (or not a TIFF), -2 a TIFF of another size or
+ * mrgingham_amd_tiff_layout_ex with option "tiff_deflate_max_strip", and a file with a larger strip keeps the host thread.
+ * Tiled files: the directories are parsed by mrgingham_amd_tiff_layout_tiled, and strip and tiled files of one size may
+ * share a call and a chunk (runs are also split by tile width and length; they go through
+ * mrgingham_amd_tiff_decode_batch_tiled).  A slot keeps `height` records per file: a tiled file with MORE TILES THAN ROWS
+ * keeps the host thread, and so does one the route does not take -- a tile width that is not a multiple of 16, PackBits, a
+ * tile that decodes to more than "tiff_lzw_max_strip" / "tiff_deflate_max_strip" bytes, Deflate without "tiff_deflate",
+ * tiles that are mostly padding (all of them decoded take more than 16 x the frame's grey bytes + 1 MiB) --
+ * both through mrgingham_amd_read_image's decoder: same bytes.  h_status[f]: 0 decoded, -1 unreadable / unsupported / malformed (or not a TIFF), -2 a TIFF of another size or
  * depth; the frame of a failed file is zero-filled.  SYNCHRONOUS: d_out is complete on return.  Returns MRGINGHAM_AMD_OK
  * also when files failed.  Completes the find_boards jobs in flight first and restores the caller's HIP device.  The
  * chunk buffers are those of mrgingham_amd_read_jpegs_batch, within the same 1 GiB (option "tiff_chunk_frames"). */

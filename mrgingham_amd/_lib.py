@@ -70,6 +70,7 @@ EXPORTS = [
     "mrgingham_amd_tiff_layout", "mrgingham_amd_tiff_decode_batch", "mrgingham_amd_tiff_geometry",
     "mrgingham_amd_read_tiffs_batch", "mrgingham_amd_find_boards_files_ex2",
     "mrgingham_amd_tiff_layout_ex", "mrgingham_amd_tiff_inflate_lanes", "mrgingham_amd_find_boards_files_ex3",
+    "mrgingham_amd_tiff_layout_tiled", "mrgingham_amd_tiff_decode_batch_tiled",
 ]
 
 
@@ -195,6 +196,12 @@ def lib():
         L.mrgingham_amd_tiff_layout_ex.argtypes = [c_vp, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(TiffInfo), c_vp,
                                                    ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
         L.mrgingham_amd_tiff_inflate_lanes.argtypes = []
+    if hasattr(L, "mrgingham_amd_tiff_layout_tiled"):
+        L.mrgingham_amd_tiff_layout_tiled.argtypes = [c_vp, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(TiffInfo),
+                                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), c_vp,
+                                                      ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        L.mrgingham_amd_tiff_decode_batch_tiled.argtypes = [c_vp, c_vp, ctypes.c_int64, c_vp, c_int, c_vp, c_int, ctypes.POINTER(TiffInfo),
+                                                            c_int, c_int, c_vp, ctypes.c_int64, c_int, c_vp, c_vp, c_vp]
         L.mrgingham_amd_find_boards_files_ex3.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
                                                           c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]

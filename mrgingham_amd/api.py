@@ -245,37 +245,46 @@ class TiffLayout:
     """What tiff_layout found in a TIFF file: height, width, bits, samples, photometric, compression, predictor, big_endian;
     nstrips and strips, a structured array (offset, nbytes, first_row, rows) of the records that fitted the capacity;
     taken: the device route (Detector.tiff_decode) takes the file, False: read_image's decoder alone reads it; rc: the
-    C call's return value (0, TIFF_NOT_TAKEN, or -2 where a given capacity was too small)."""
+    C call's return value (0, TIFF_NOT_TAKEN, or -2 where a given capacity was too small).  tile_width, tile_length: 0 for a
+    strip file; for a tiled file (tiff_layout(tiles=True)) the tile sizes, and `strips` holds one record per tile, row-major,
+    rows = tile_length each."""
     FIELDS = ("width", "height", "bits", "samples", "photometric", "compression", "predictor", "big_endian")
 
-    def __init__(self, info, strips, nstrips, rc):
+    def __init__(self, info, strips, nstrips, rc, tile_width=0, tile_length=0):
         for n in self.FIELDS:
             setattr(self, n, int(getattr(info, n)))
         self.strips, self.nstrips, self.rc, self.taken = strips, int(nstrips), int(rc), rc == 0
+        self.tile_width, self.tile_length = int(tile_width), int(tile_length)
 
     def key(self):
         return tuple(getattr(self, n) for n in self.FIELDS)
 
     def __repr__(self):
-        return "TiffLayout(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.FIELDS) + f", nstrips={self.nstrips}, rc={self.rc})"
+        return "TiffLayout(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.FIELDS) + f", nstrips={self.nstrips}, tile={self.tile_width}x{self.tile_length}, rc={self.rc})"
 
 
 TIFF_NOT_TAKEN = -3
 TIFF_STRIP = np.dtype([("offset", "<i8"), ("nbytes", "<i8"), ("first_row", "<i4"), ("rows", "<i4")])
 
 
-def tiff_layout(data, lzw_max_strip=0, capacity=None, deflate_max_strip=0):
+def tiff_layout(data, lzw_max_strip=0, capacity=None, deflate_max_strip=0, tiles=False):
     """The first image file directory of a TIFF held in memory (host only; mrgingham_amd_tiff_layout, which has the subset
     this library reads): -> TiffLayout, or None when the data is not a TIFF this library reads.  lzw_max_strip: the decoded
     bytes of an LZW strip above which the file is left to the host decoder (0: 1 MiB).  capacity: room for that many
     strip records (default: all of them); with fewer than the file has, rc is -2 and the counts are still reported.
     deflate_max_strip: above 0, Deflate files whose strips decode to at most that many bytes are taken as well
-    (mrgingham_amd_tiff_layout_ex); 0: they are left to the host decoder."""
+    (mrgingham_amd_tiff_layout_ex); 0: they are left to the host decoder.  tiles=True: tiled files are read as well
+    (mrgingham_amd_tiff_layout_tiled: one record per tile, tile_width and tile_length in the result; taken with a tile width
+    that is a multiple of 16); False: a file with any tile tag gives None, as before."""
     L = _lib.lib()
     buf = bytes(data)
     info, n = _lib.TiffInfo(), ctypes.c_size_t()
+    tw, tl = ctypes.c_int32(), ctypes.c_int32()
 
     def call(strips, cap):
+        if tiles:
+            return L.mrgingham_amd_tiff_layout_tiled(buf, len(buf), int(lzw_max_strip), int(deflate_max_strip), ctypes.byref(info),
+                                                     ctypes.byref(tw), ctypes.byref(tl), strips, cap, ctypes.byref(n))
         if int(deflate_max_strip) > 0:
             return L.mrgingham_amd_tiff_layout_ex(buf, len(buf), int(lzw_max_strip), int(deflate_max_strip), ctypes.byref(info), strips, cap,
                                                   ctypes.byref(n))
@@ -290,7 +299,7 @@ def tiff_layout(data, lzw_max_strip=0, capacity=None, deflate_max_strip=0):
         rc = -2   # (no array to write into is "counts only" at the C boundary)
     if rc not in (0, TIFF_NOT_TAKEN, -2):
         return None
-    return TiffLayout(info, strips[:min(cap, n.value)], n.value, rc)
+    return TiffLayout(info, strips[:min(cap, n.value)], n.value, rc, tw.value, tl.value)
 
 
 def tiff_geometry():
@@ -302,7 +311,7 @@ def tiff_geometry():
 
 
 def read_image(filename, cli_scaling=False):
-    """Decode a binary PGM, non-interlaced PNG, baseline JPEG or strip TIFF (uncompressed, LZW, PackBits, Deflate; grey or
+    """Decode a binary PGM, non-interlaced PNG, baseline JPEG or strip or tiled TIFF (uncompressed, LZW, PackBits, Deflate; grey or
     RGB, 8 or 16 bit) to uint8 [H, W] with the library's own decoder (host only).
     16-bit files: the high byte (cv::imread(IMREAD_GRAYSCALE)) or, with cli_scaling, the CLI's
     convertTo(255/65535).  None when the file is unreadable, unsupported or malformed."""
@@ -1126,9 +1135,9 @@ class Detector:
         return frames, status
 
     def tiff_decode(self, datas, layouts=None, out=None):
-        """TIFF files held in memory to grey frames on the device (mrgingham_amd_tiff_decode_batch), on torch's current
-        stream: datas, a list of bytes; layouts, their tiff_layout results (default: computed here), which must all be
-        taken by the device route and agree in every field -> (frames uint8 or uint16 [B, height, width], the samples
+        """TIFF files held in memory to grey frames on the device (mrgingham_amd_tiff_decode_batch_tiled), on torch's current
+        stream: datas, a list of bytes; layouts, their tiff_layout results (default: computed here, with tiles=True), which must
+        all be taken by the device route and agree in every field, the tile sizes among them -> (frames uint8 or uint16 [B, height, width], the samples
         read_image's decoder gives; status int32 [B] numpy: 0, or -1 for a file whose LZW or Deflate strips broke a rule -- its frame
         is zero; strip_status int32 [B, P] numpy: per strip what stopped its lane, 0 for none).  `out`: a [B, height,
         >= width] device tensor of that type (unit column stride) to write into; what lies beyond `width` is not touched.
@@ -1136,9 +1145,10 @@ class Detector:
         t = self.torch
         datas = [bytes(d) for d in datas]
         if layouts is None:
-            layouts = [tiff_layout(d) for d in datas]
+            layouts = [tiff_layout(d, tiles=True) for d in datas]
         B = len(datas)
-        if B == 0 or len(layouts) != B or any(l is None or not l.taken for l in layouts) or len({l.key() for l in layouts}) != 1:
+        if (B == 0 or len(layouts) != B or any(l is None or not l.taken for l in layouts)
+                or len({l.key() + (l.tile_width, l.tile_length) for l in layouts}) != 1):
             raise ValueError("tiff_decode: at least one file, all taken by the device route (tiff_layout) and equal in every field")
         lay = layouts[0]
         W, H, P = lay.width, lay.height, max(l.nstrips for l in layouts)
@@ -1161,8 +1171,9 @@ class Detector:
             raise ValueError("tiff_decode: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
         info = _lib.TiffInfo(*lay.key())
         stream = t.cuda.current_stream(self.device).cuda_stream
-        self._check(self.L.mrgingham_amd_tiff_decode_batch(
-            self.ctx, d_files.data_ptr(), pitch, d_strips.data_ptr(), P, d_ns.data_ptr(), B, ctypes.byref(info), out.data_ptr(),
+        self._check(self.L.mrgingham_amd_tiff_decode_batch_tiled(
+            self.ctx, d_files.data_ptr(), pitch, d_strips.data_ptr(), P, d_ns.data_ptr(), B, ctypes.byref(info), lay.tile_width,
+            lay.tile_length, out.data_ptr(),
             out.stride(0) if B > 1 else H * out.stride(1), out.stride(1) if H > 1 else out.shape[2], d_status.data_ptr(),
             d_sstatus.data_ptr(), stream))
         return out[:, :, :W], d_status.cpu().numpy(), d_sstatus.cpu().numpy()
@@ -1174,7 +1185,9 @@ class Detector:
         [B,H,W] on the device, status int32 [B] numpy: 0 decoded, -1 unreadable / unsupported / malformed, -2 a TIFF of
         another size or depth; failed frames are zero).  Size and depth are those of the first file whose directory
         parses (none does: uint8 frames [B,0,0]).  PackBits and Deflate files, and LZW files with a strip above option
-        "tiff_lzw_max_strip", are decoded by the host threads: same bytes.  deflate="device": Deflate files whose strips
+        "tiff_lzw_max_strip", are decoded by the host threads: same bytes.  Tiled files go the same ways tile by tile, and may
+        share a list with strip files; one whose tile width is no multiple of 16, or with more tiles than rows, keeps the host
+        threads.  deflate="device": Deflate files whose strips
         decode to at most option "tiff_deflate_max_strip" go through the device like LZW files; "host": the host threads
         inflate them; None (default): as option "tiff_deflate" of this detector says.  Either value holds for this call
         only: the option is afterwards what it was.  Synchronous."""

@@ -58,7 +58,7 @@ const char* kUsage =
     "          [--debug] [--debug-sequence x,y]\n"
     "          imageglobs...\n"
     "\n"
-    "Finds the chessboard in every image (binary PGM, PNG, baseline JPEG or strip TIFF) and writes a vnlog table\n"
+    "Finds the chessboard in every image (binary PGM, PNG, baseline JPEG, strip or tiled TIFF) and writes a vnlog table\n"
     "\n"
     "  # filename x y level\n"
     "\n"

@@ -261,6 +261,9 @@ const uint16_t kTiffTagIds[kTags] = {256, 257, 258, 259, 262, 266, 273, 274, 277
 
 }  // namespace
 
+static int tiff_parse(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info_out,
+                      int32_t* tile_width, int32_t* tile_length, mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips_out);
+
 int tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info_out,
                 mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips_out) {
     return tiff_layout_ex(data, nbytes, lzw_max_strip, 0, info_out, strips, capacity, nstrips_out);
@@ -268,7 +271,24 @@ int tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgin
 
 int tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info_out,
                    mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips_out) {
+    return tiff_parse(data, nbytes, lzw_max_strip, deflate_max_strip, info_out, nullptr, nullptr, strips, capacity, nstrips_out);
+}
+
+int tiff_layout_tiled(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info_out,
+                      int32_t* tile_width, int32_t* tile_length, mrgingham_amd_tiff_strip* records, size_t capacity, size_t* nrecords_out) {
+    int32_t tw = 0, tl = 0;
+    const int rc = tiff_parse(data, nbytes, lzw_max_strip, deflate_max_strip, info_out, &tw, &tl, records, capacity, nrecords_out);
+    if (tile_width) *tile_width = tw;
+    if (tile_length) *tile_length = tl;
+    return rc;
+}
+
+// tile_width / tile_length NULL: tiff_layout_ex, to which any tile tag is unreadable; else tiff_layout_tiled
+static int tiff_parse(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info_out,
+                      int32_t* tile_width, int32_t* tile_length, mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips_out) {
     if (nstrips_out) *nstrips_out = 0;
+    if (tile_width) *tile_width = 0;
+    if (tile_length) *tile_length = 0;
     if (!data || nbytes < 8) return -1;
     TiffReader r{data, nbytes, false};
     if (data[0] == 'I' && data[1] == 'I') r.be = false;
@@ -308,13 +328,16 @@ int tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, in
         return r.value(e[t], 0);
     };
     bool ok = true;
-    if (e[kTagTileWidth].present || e[kTagTileLength].present || e[kTagTileOffsets].present || e[kTagTileByteCounts].present) return -1;
-    if (!e[kTagWidth].present || !e[kTagHeight].present || !e[kTagBits].present || !e[kTagPhotometric].present ||
-        !e[kTagStripOffsets].present || !e[kTagStripByteCounts].present)
-        return -1;
+    const bool any_tile = e[kTagTileWidth].present || e[kTagTileLength].present || e[kTagTileOffsets].present || e[kTagTileByteCounts].present;
+    // tiled: all four tile tags and neither strip tag; any other mixture is unreadable
+    const bool tiled = tile_width && tile_length && e[kTagTileWidth].present && e[kTagTileLength].present && e[kTagTileOffsets].present &&
+                       e[kTagTileByteCounts].present && !e[kTagStripOffsets].present && !e[kTagStripByteCounts].present;
+    if (any_tile && !tiled) return -1;
+    if (!e[kTagWidth].present || !e[kTagHeight].present || !e[kTagBits].present || !e[kTagPhotometric].present) return -1;
+    if (!tiled && (!e[kTagStripOffsets].present || !e[kTagStripByteCounts].present)) return -1;
     const uint32_t w = one(kTagWidth, 0, &ok), h = one(kTagHeight, 0, &ok), spp = one(kTagSamples, 1, &ok);
     const uint32_t comp = one(kTagCompression, 1, &ok), photo = one(kTagPhotometric, 0, &ok), pred = one(kTagPredictor, 1, &ok);
-    uint32_t rps = one(kTagRowsPerStrip, 0xFFFFFFFFu, &ok);
+    uint32_t rps = tiled ? 0 : one(kTagRowsPerStrip, 0xFFFFFFFFu, &ok);  // (RowsPerStrip in a tiled file is ignored)
     if (!ok || one(kTagFillOrder, 1, &ok) != 1 || one(kTagOrientation, 1, &ok) != 1 || one(kTagPlanar, 1, &ok) != 1 || !ok) return -1;
     if (w == 0 || h == 0 || w > (uint32_t)kMaxSide || h > (uint32_t)kMaxSide || spp < 1 || spp > 4) return -1;
     if (e[kTagBits].count != spp) return -1;
@@ -330,18 +353,32 @@ int tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, in
     if (photo > 2 || (photo == 2 && spp < 3)) return -1;
     if (comp != 1 && comp != 5 && comp != 32773 && comp != 8 && comp != 32946) return -1;
     if (pred != 1 && pred != 2) return -1;
-    if (rps == 0) return -1;
-    if (rps > h) rps = h;
-    const uint32_t ns = (h + rps - 1) / rps;
-    if (e[kTagStripOffsets].count != ns || e[kTagStripByteCounts].count != ns) return -1;
-    const uint64_t rowb = (uint64_t)w * spp * (bits / 8);
+    uint32_t tw = 0, tl = 0, across = 0;
+    if (tiled) {
+        tw = one(kTagTileWidth, 0, &ok);
+        tl = one(kTagTileLength, 0, &ok);
+        if (!ok || tw == 0 || tl == 0 || tw > (uint32_t)kMaxSide || tl > (uint32_t)kMaxSide) return -1;
+        across = (w + tw - 1) / tw;
+        rps = tl;
+    } else {
+        if (rps == 0) return -1;
+        if (rps > h) rps = h;
+    }
+    // (tiles: at most 32767 x 32767 of them)
+    const uint32_t ns = tiled ? across * ((h + tl - 1) / tl) : (h + rps - 1) / rps;
+    const TiffEntry& eoff = e[tiled ? kTagTileOffsets : kTagStripOffsets];
+    const TiffEntry& ecnt = e[tiled ? kTagTileByteCounts : kTagStripByteCounts];
+    if (eoff.count != ns || ecnt.count != ns) return -1;
+    // a tile decodes to its full size whatever the image keeps of it: the rules below hold per tile
+    const uint64_t rowb = (uint64_t)(tiled ? tw : w) * spp * (bits / 8);
     const bool deflate = comp == 8 || comp == 32946;
     bool taken = comp == 1 || comp == 5 || (deflate && deflate_max_strip > 0);
+    if (tiled && tw % 16 != 0) taken = false;  // (a lane's 16 pixels lie in one tile: tiff_finish_tiles_kernel)
     if (deflate_max_strip > (int64_t)kTiffInflateMaxStrip) deflate_max_strip = (int64_t)kTiffInflateMaxStrip;
     if (lzw_max_strip <= 0 || lzw_max_strip > (int64_t)kTiffLzwMaxStrip20) lzw_max_strip = (int64_t)kTiffLzwMaxStrip20;
     for (uint32_t i = 0; i < ns; ++i) {
-        const uint64_t off = r.value(e[kTagStripOffsets], i), cnt = r.value(e[kTagStripByteCounts], i);
-        const uint32_t first = i * rps, rows = h - first < rps ? h - first : rps;
+        const uint64_t off = r.value(eoff, i), cnt = r.value(ecnt, i);
+        const uint32_t first = tiled ? (i / across) * tl : i * rps, rows = tiled ? tl : h - first < rps ? h - first : rps;
         if (off > nbytes || cnt > nbytes - off) return -1;
         if (comp == 1 && cnt < rows * rowb) return -1;
         // (a code is at least 9 bits and gives fewer than 4096 bytes: a strip that cannot hold its rows is refused before
@@ -358,6 +395,7 @@ int tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, in
         *info_out = mrgingham_amd_tiff_info{(int32_t)w, (int32_t)h, (int32_t)bits, (int32_t)spp, (int32_t)photo, (int32_t)comp,
                                             (int32_t)pred, r.be ? 1 : 0};
     if (nstrips_out) *nstrips_out = ns;
+    if (tiled) { *tile_width = (int32_t)tw; *tile_length = (int32_t)tl; }
     if (strips && capacity < ns) return -2;
     return taken ? 0 : kTiffNotTaken;
 }
@@ -406,43 +444,54 @@ static bool tiff_unpackbits(const uint8_t* s, size_t ns, uint8_t* o, size_t rowb
     return true;
 }
 
+// one compressed strip or tile (compression 5, 32773, 8 or 32946) to exactly rows x rowb bytes, or false
+static bool tiff_decompress(const mrgingham_amd_tiff_info& ti, const uint8_t* src, const mrgingham_amd_tiff_strip& st, size_t rowb,
+                            std::vector<uint8_t>& raw, std::unique_ptr<TiffLzwHostTable>& tab) {
+    const size_t need = rowb * (size_t)st.rows;
+    // (the decoders count in 32 bits: a strip of 4 GiB or more is refused before anything is sized for it)
+    if (need > 0xFFFFFFFFull || (uint64_t)st.nbytes > 0xFFFFFFFFull) return false;
+    raw.resize(need);
+    if (ti.compression == 5) {
+        if (!tab) tab.reset(new TiffLzwHostTable);
+        return tiff_lzw_decode(src, (uint32_t)st.nbytes, raw.data(), (uint32_t)need, *tab) == kTiffLzwOk;
+    }
+    if (ti.compression == 32773) return tiff_unpackbits(src, (size_t)st.nbytes, raw.data(), rowb, (size_t)st.rows);
+    uLongf got = (uLongf)need;
+    return uncompress(raw.data(), &got, src, (uLong)st.nbytes) == Z_OK && got == need;
+}
+
 static bool decode_tiff(const std::vector<uint8_t>& b, Image& im) {
     mrgingham_amd_tiff_info ti;
     size_t ns = 0;
-    int rc = tiff_layout(b.data(), b.size(), 0, &ti, nullptr, 0, &ns);
+    int32_t tw = 0, tl = 0;
+    int rc = tiff_layout_tiled(b.data(), b.size(), 0, 0, &ti, &tw, &tl, nullptr, 0, &ns);
     if (rc != 0 && rc != kTiffNotTaken) return false;
     std::vector<mrgingham_amd_tiff_strip> strips(ns);
-    rc = tiff_layout(b.data(), b.size(), 0, &ti, strips.data(), ns, &ns);
+    rc = tiff_layout_tiled(b.data(), b.size(), 0, 0, &ti, &tw, &tl, strips.data(), ns, &ns);
     if (rc != 0 && rc != kTiffNotTaken) return false;
-    const size_t rowb = (size_t)ti.width * ti.samples * (ti.bits / 8), n = (size_t)ti.width * ti.height;
+    const size_t bpp = (size_t)ti.samples * (ti.bits / 8), rowb = (size_t)(tw ? tw : ti.width) * bpp, n = (size_t)ti.width * ti.height;
     im.w = ti.width; im.h = ti.height; im.depth = ti.bits;
     if (ti.bits == 8) { about_to_hold(im, n, 0); im.px8.resize(n); }
     else { about_to_hold(im, 0, n); im.px16.resize(n); }
     std::vector<uint8_t> raw;
     std::unique_ptr<TiffLzwHostTable> tab;
-    for (const mrgingham_amd_tiff_strip& st : strips) {
-        const uint8_t* src = b.data() + st.offset;
-        const size_t need = rowb * (size_t)st.rows;
-        const uint8_t* rows = src;
+    const size_t across = tw ? ((size_t)ti.width + tw - 1) / tw : 1;
+    for (size_t i = 0; i < strips.size(); ++i) {
+        const mrgingham_amd_tiff_strip& st = strips[i];
+        const uint8_t* rows = b.data() + st.offset;
         if (ti.compression != 1) {
-            // (the decoders count in 32 bits: a strip of 4 GiB or more is refused before anything is sized for it)
-            if (need > 0xFFFFFFFFull || (uint64_t)st.nbytes > 0xFFFFFFFFull) return false;
-            raw.resize(need);
+            if (!tiff_decompress(ti, rows, st, rowb, raw, tab)) return false;
             rows = raw.data();
-            if (ti.compression == 5) {
-                if (!tab) tab.reset(new TiffLzwHostTable);
-                if (tiff_lzw_decode(src, (uint32_t)st.nbytes, raw.data(), (uint32_t)need, *tab) != kTiffLzwOk) return false;
-            } else if (ti.compression == 32773) {
-                if (!tiff_unpackbits(src, (size_t)st.nbytes, raw.data(), rowb, (size_t)st.rows)) return false;
-            } else {
-                uLongf got = (uLongf)need;
-                if (uncompress(raw.data(), &got, src, (uLong)st.nbytes) != Z_OK || got != need) return false;
-            }
         }
-        for (int y = 0; y < st.rows; ++y) {
-            const size_t row = (size_t)st.first_row + y;
-            if (ti.bits == 8) tiff_finish_row<uint8_t>(rows + rowb * y, ti, &im.px8[row * ti.width]);
-            else tiff_finish_row<uint16_t>(rows + rowb * y, ti, &im.px16[row * ti.width]);
+        // a tile: its rows inside the image, of each the columns inside the image; the predictor restarts at the tile's left edge
+        const size_t x0 = tw ? (i % across) * (size_t)tw : 0;
+        mrgingham_amd_tiff_info part = ti;
+        if (tw && (size_t)ti.width - x0 < (size_t)tw) part.width = (int32_t)((size_t)ti.width - x0);
+        else if (tw) part.width = tw;
+        for (int y = 0; y < st.rows && st.first_row + y < ti.height; ++y) {
+            const size_t at = ((size_t)st.first_row + y) * ti.width + x0;
+            if (ti.bits == 8) tiff_finish_row<uint8_t>(rows + rowb * y, part, &im.px8[at]);
+            else tiff_finish_row<uint16_t>(rows + rowb * y, part, &im.px16[at]);
         }
     }
     return true;
@@ -544,7 +593,8 @@ bool probe_image(const char* path, int* width, int* height, int* bits, int* kind
             ok = b.size() == (size_t)size || rest();  // (the IFD may lie anywhere, behind the strips as well)
             mrgingham_amd_tiff_info ti{};
             if (ok) {
-                const int rc = tiff_layout(b.data(), b.size(), 0, &ti, nullptr, 0, nullptr);
+                int32_t tw = 0, tl = 0;
+                const int rc = tiff_layout_tiled(b.data(), b.size(), 0, 0, &ti, &tw, &tl, nullptr, 0, nullptr);
                 ok = rc == 0 || rc == kTiffNotTaken;
             }
             w = ti.width; h = ti.height; d = ti.bits;
@@ -627,6 +677,12 @@ extern "C" int mrgingham_amd_tiff_layout(const uint8_t* data, size_t nbytes, int
 extern "C" int mrgingham_amd_tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip,
                                             mrgingham_amd_tiff_info* info, mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips) {
     return mrg::tiff_layout_ex(data, nbytes, lzw_max_strip, deflate_max_strip, info, strips, capacity, nstrips);
+}
+
+extern "C" int mrgingham_amd_tiff_layout_tiled(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip,
+                                               mrgingham_amd_tiff_info* info, int32_t* tile_width, int32_t* tile_length,
+                                               mrgingham_amd_tiff_strip* records, size_t capacity, size_t* nrecords) {
+    return mrg::tiff_layout_tiled(data, nbytes, lzw_max_strip, deflate_max_strip, info, tile_width, tile_length, records, capacity, nrecords);
 }
 
 extern "C" int mrgingham_amd_png_scanlines(const uint8_t* data, size_t nbytes, uint8_t* scan, size_t scan_capacity, int* width,

@@ -3,7 +3,7 @@
 // non-interlaced PNG (8 or 16 bit; grey, grey+alpha, RGB, RGBA, 8-bit palette) via zlib, baseline
 // JPEG (jpeg.h: sequential Huffman, one scan; the luma plane, byte for byte what libjpeg's default
 // decoder gives cv::imread(IMREAD_GRAYSCALE); progressive, arithmetic and multi-scan files are
-// unreadable) and strip TIFF (tiff_layout below has the subset; LZW through tiff_lzw.h).  PNG and TIFF
+// unreadable) and strip or tiled TIFF (tiff_layout and tiff_layout_tiled below have the subset; LZW through tiff_lzw.h).  PNG and TIFF
 // colour is reduced to grey with the fixed-point BT.601 weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14; byte-identity with cv::imread on colour files is not
 // claimed (its conversion depends on the codec build).
@@ -30,7 +30,7 @@ struct Image {
 bool read_image(const char* path, Image& im);
 // What read_image would produce, from the file's header alone (nothing is decoded): width, height, bits (8 or 16) and
 // kind -- 1 binary PGM, 2 PNG, 3 baseline JPEG (jpeg_coefficients' header parse, up to and including SOS), 4 TIFF
-// (tiff_layout: the IFD and the strip table).  false for
+// (tiff_layout_tiled: the IFD and the strip or tile table).  false for
 // whatever read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut
 // short or breaks a rule (sides above 32767 included), a PGM shorter than its header promises.  A file that passes may
 // still fail to decode.  Never throws, never sizes anything from an unchecked field.
@@ -63,6 +63,11 @@ int tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgin
 // the same with Deflate files taken whose strips decode to at most deflate_max_strip bytes (<= 0: none, tiff_layout)
 int tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info,
                    mrgingham_amd_tiff_strip* strips, size_t capacity, size_t* nstrips);
+// the same with tiled files read (mrgingham_amd_tiff_layout_tiled): a strip file as tiff_layout_ex with *tile_width =
+// *tile_length = 0; a tiled file one record per tile, row-major, rows = the tile's length; 0 for it only with a tile width
+// that is a multiple of 16.  read_image, probe_image and the batch loader parse through this one.
+int tiff_layout_tiled(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info,
+                      int32_t* tile_width, int32_t* tile_length, mrgingham_amd_tiff_strip* records, size_t capacity, size_t* nrecords);
 // The IHDR fields of a PNG file as they stand, nothing judged (a routing hint: png_scanlines decides what is readable):
 // returns the colour type byte, -1 for a file that does not begin with a PNG signature and a whole IHDR.
 int png_header(const char* path, int* width, int* height, int* bits);

@@ -2,7 +2,7 @@
 // Deflate strips likewise (tiff_inflate.h, zlib's contract), the rows put into value order, predictor 2 undone and the
 // samples reduced to grey, and the batch loader that reads the files straight into page-locked staging.  See
 // include/mrgingham_amd.h for the contract of the entry points and DESIGN.md sections 4.14 and 4.15 for the schedule and
-// the numbers.
+// the numbers, section 4.16 for tiled files (tiles one lane each, tiff_finish_tiles_kernel).
 #include <stdio.h>
 #include <string.h>
 
@@ -44,15 +44,29 @@ constexpr int kFinishBlock = 256;
 // every strip inside its file's area, an uncompressed strip long enough for its rows, an LZW or Deflate strip decoding to
 // at most 1 MiB, a Deflate strip of no more bytes than tiff_inflate_max_bytes allows (they bound its lane's work).  A lane that finds a fault in its frame's counts or in its own strip stores -1 into status[f] (every such lane
 // the same value): the frame is zero-filled.
+// Tiled files (tile_w > 0; rowb is then the bytes of a TILE's row): as many records as tiles, record i the tile i in
+// row-major order, first_row = (i / across) * tile_l and rows = tile_l, what it decodes to; the same rules on its place in
+// the file and on its decoded bytes, tile_l x rowb.
 __global__ void tiff_check_kernel(const mrgingham_amd_tiff_strip* strips, int strips_pitch, const int32_t* nstrips, int nframes,
-                                  int height, uint32_t rowb, long long file_pitch, int codec, int32_t* status) {
+                                  int height, uint32_t rowb, long long file_pitch, int codec, int tile_w, int tile_l, int across, int down,
+                                  int32_t* status) {
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= (long long)nframes * strips_pitch) return;
     const int f = (int)(s / strips_pitch), i = (int)(s - (long long)f * strips_pitch);
     const mrgingham_amd_tiff_strip* t = strips + (long long)f * strips_pitch;
     const int ns = nstrips[f];
     bool ok = ns >= 1 && ns <= strips_pitch;
-    if (ok) {
+    if (ok && tile_w > 0) {
+        ok = (long long)ns == (long long)across * down;
+        if (ok && i < ns) {
+            const unsigned long long need = (unsigned long long)tile_l * rowb;
+            ok = t[i].first_row == (i / across) * tile_l && t[i].rows == tile_l && t[i].offset >= 0 && t[i].nbytes >= 0 &&
+                 t[i].offset <= file_pitch && t[i].nbytes <= file_pitch - t[i].offset && t[i].nbytes <= 0xFFFFFFFFll &&
+                 (codec == kCodecLzw       ? need <= kTiffLzwMaxStrip20
+                  : codec == kCodecDeflate ? need <= kTiffInflateMaxStrip && (unsigned long long)t[i].nbytes <= tiff_inflate_max_bytes(need)
+                                           : (unsigned long long)t[i].nbytes >= need);
+        }
+    } else if (ok) {
         const int rps = t[0].rows;
         ok = rps >= 1 && rps <= height && (long long)(ns - 1) * rps < height && (long long)ns * rps >= height;
         if (ok && i < ns) {
@@ -72,6 +86,9 @@ __global__ void tiff_check_kernel(const mrgingham_amd_tiff_strip* strips, int st
 // reads src[0, nbytes) of its strip and writes the rows x rowb bytes of its strip in `raw` (frame f at raw + f*raw_pitch,
 // rows dense): both bounds are arguments of tiff_lzw_decode and were checked against the file's area and the frame by
 // tiff_check_kernel.  A rule broken: the lane stops, leaves the reason in strip_status and -1 in status[f].
+// TILED: rowb is the bytes of a tile's row, and tile i of frame f decodes to raw + f*raw_pitch + i * rows*rowb -- dense and
+// tile-major, every tile rows = tile_l long (tiff_check_kernel), so a lane still writes its own tile's bytes alone.
+template <bool TILED>
 __global__ __launch_bounds__(kLzwBlock) void tiff_lzw_kernel(const uint8_t* files, long long file_pitch,
                                                              const mrgingham_amd_tiff_strip* strips, int strips_pitch,
                                                              const int32_t* nstrips, int nframes, uint32_t rowb, uint8_t* raw,
@@ -85,8 +102,8 @@ __global__ __launch_bounds__(kLzwBlock) void tiff_lzw_kernel(const uint8_t* file
         int rc = 0;
         if (status[f] == 0 && i < nstrips[f]) {  // (status: only tiff_check_kernel's verdict is read here; lanes write `broken`)
             const mrgingham_amd_tiff_strip st = strips[s];
-            rc = tiff_lzw_decode(files + f * file_pitch + st.offset, (uint32_t)st.nbytes, raw + f * raw_pitch + (long long)st.first_row * rowb,
-                                 (uint32_t)st.rows * rowb, tab);
+            const long long at = TILED ? (long long)i * ((long long)st.rows * rowb) : (long long)st.first_row * rowb;
+            rc = tiff_lzw_decode(files + f * file_pitch + st.offset, (uint32_t)st.nbytes, raw + f * raw_pitch + at, (uint32_t)st.rows * rowb, tab);
             if (rc) broken[f] = 1;
         }
         if (strip_status) strip_status[s] = rc;
@@ -96,7 +113,10 @@ __global__ __launch_bounds__(kLzwBlock) void tiff_lzw_kernel(const uint8_t* file
 // The Deflate strips, scheduled as the LZW ones are: a lane reads src[0, nbytes) of its strip, writes the rows x rowb bytes
 // of its strip in `raw` and keeps its tables at table[lane + i * lanes], i < kTiffInflateWords -- the bounds are
 // arguments of tiff_inflate_decode, checked by tiff_check_kernel, and a copy never reaches before the strip's own first byte.
-__global__ __launch_bounds__(kInflateBlock) void tiff_inflate_kernel(const uint8_t* files, long long file_pitch,
+// TILED: as in tiff_lzw_kernel.  (flatten: with two instantiations the compiler would otherwise leave the decoder a function
+// of its own and call it; inlined, the strip instantiation is the kernel it was before there were tiles.)
+template <bool TILED>
+__global__ __launch_bounds__(kInflateBlock) __attribute__((flatten)) void tiff_inflate_kernel(const uint8_t* files, long long file_pitch,
                                                                      const mrgingham_amd_tiff_strip* strips, int strips_pitch,
                                                                      const int32_t* nstrips, int nframes, uint32_t rowb, uint8_t* raw,
                                                                      long long raw_pitch, uint16_t* table, int32_t* status,
@@ -109,8 +129,8 @@ __global__ __launch_bounds__(kInflateBlock) void tiff_inflate_kernel(const uint8
         int rc = 0;
         if (status[f] == 0 && i < nstrips[f]) {
             const mrgingham_amd_tiff_strip st = strips[s];
-            rc = tiff_inflate_decode(files + f * file_pitch + st.offset, (uint32_t)st.nbytes, raw + f * raw_pitch + (long long)st.first_row * rowb,
-                                     (uint32_t)st.rows * rowb, tab);
+            const long long at = TILED ? (long long)i * ((long long)st.rows * rowb) : (long long)st.first_row * rowb;
+            rc = tiff_inflate_decode(files + f * file_pitch + st.offset, (uint32_t)st.nbytes, raw + f * raw_pitch + at, (uint32_t)st.rows * rowb, tab);
             if (rc) broken[f] = 1;
         }
         if (strip_status) strip_status[s] = rc;
@@ -259,6 +279,139 @@ __global__ __launch_bounds__(kFinishBlock) void tiff_finish_kernel(const uint8_t
     }
 }
 
+// tiff_finish_kernel for tiled files: the same wave per image row, the same 16 pixels per lane and the same stores; what
+// differs is where a lane's bytes come from and how far the sums of predictor 2 reach.  tile_w is a multiple of kSegPx, so
+// the segment of a lane lies in ONE tile: tile i = (y / tile_l) * across + xs / tile_w, its row y % tile_l, at
+// `src` + f*src_pitch + i * tile_l*tile_rowb (from_raw: the LZW / Deflate launch's dense, tile-major output) or at the
+// record's offset inside the file's bytes, at any byte address (tiff_check_kernel: the whole padded tile lies inside the
+// file's area).  A tile is padded to its full width, so the last lane of a row loads padding, never another tile's bytes;
+// those pixels are computed and never stored.  Predictor 2 restarts at every tile's left edge: the scan over the wave is
+// SEGMENTED -- a lane adds the sum from d lanes to its left only when that lane lies in the same tile (lane - d >= l0,
+// the tile's first lane of this step) -- and `carry`, the sum of the steps before, applies only to lanes whose tile began
+// before x0 (l0 < 0); the carry handed on is the last lane's inclusive sum, with the old carry where that lane's tile
+// reaches back past x0.  All sums are modulo 2^BITS, exact in any order.
+template <int BITS, int SPP>
+__global__ __launch_bounds__(kFinishBlock) void tiff_finish_tiles_kernel(const uint8_t* __restrict__ src, long long src_pitch, long long limit,
+                                                                         const mrgingham_amd_tiff_strip* __restrict__ strips, int strips_pitch,
+                                                                         int from_raw, int width, int height, long long nrows, int tile_w,
+                                                                         int tile_l, int across, int rgb, int invert, int predictor2,
+                                                                         int big_endian, void* __restrict__ out, long long frame_pitch,
+                                                                         int stride, const int32_t* __restrict__ status) {
+    constexpr int ES = BITS / 8, BPP = SPP * ES, NC = SPP >= 3 ? 3 : 1, SEGB = kSegPx * BPP, ND = SEGB / 4;
+    constexpr uint32_t MASK = BITS == 8 ? 255u : 65535u;
+    const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x / kWave;
+    const long long nwaves = (long long)gridDim.x * (kFinishBlock / kWave), tile_rowb = (long long)tile_w * BPP,
+                    tile_bytes = tile_rowb * tile_l;
+    const int seg_per_tile = tile_w / kSegPx;
+    for (long long row = (long long)blockIdx.x * (kFinishBlock / kWave) + wave; row < nrows; row += nwaves) {
+        const long long f = row / height;
+        const int y = (int)(row - f * height);
+        const bool dead = status[f] != 0;
+        const int ty = y / tile_l;
+        const long long in_tile = (long long)(y - ty * tile_l) * tile_rowb;
+        const mrgingham_amd_tiff_strip* t = strips + f * strips_pitch + (long long)ty * across;
+        uint32_t carry[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) carry[c] = 0;
+        for (int x0 = 0; x0 < width; x0 += kStepPx) {
+            const int xs = x0 + lane * kSegPx, nx = width - xs;
+            const int tx = xs / tile_w;
+            // the tile's first lane of this step; below 0: the tile began in a step before
+            const int l0 = tx * seg_per_tile - x0 / kSegPx;
+            uint32_t v[kSegPx][NC], acc[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) acc[c] = 0;
+            if (!dead && nx > 0) {
+                // (nx > 0: tx < across, a record tiff_check_kernel has seen)
+                const long long tile_off = from_raw ? ((long long)ty * across + tx) * tile_bytes : t[tx].offset;
+                const long long first = f * src_pitch + tile_off + in_tile + (long long)(xs - tx * tile_w) * BPP, first4 = first & ~3ll;
+                const int shift = 8 * (int)(first & 3);
+                uint32_t w[ND + 1], in[ND];
+#pragma unroll
+                for (int i = 0; i <= ND; ++i) w[i] = load_dword(src, first4 + 4 * i, limit);
+#pragma unroll
+                for (int i = 0; i < ND; ++i) in[i] = (uint32_t)(((((unsigned long long)w[i + 1]) << 32) | w[i]) >> shift);
+#pragma unroll
+                for (int p = 0; p < kSegPx; ++p) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        const int b = (p * SPP + c) * ES;
+                        uint32_t s;
+                        if constexpr (BITS == 8) s = byte_of(in, b);
+                        else s = big_endian ? byte_of(in, b) << 8 | byte_of(in, b + 1) : byte_of(in, b + 1) << 8 | byte_of(in, b);
+                        if (predictor2) s = acc[c] += s;
+                        v[p][c] = s;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < kSegPx; ++p)
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) v[p][c] = 0;
+            }
+            if (predictor2) {  // (uniform over the wave)
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    uint32_t s = nx > 0 ? acc[c] : 0;
+                    const uint32_t own = s;
+#pragma unroll
+                    for (int d = 1; d < kWave; d <<= 1) {
+                        const uint32_t u = __shfl_up(s, d, kWave);
+                        if (lane >= d && lane - d >= l0) s += u;
+                    }
+                    const uint32_t reach = l0 < 0 ? carry[c] : 0u;
+                    const uint32_t before = s - own + reach;
+                    carry[c] = __shfl(s + reach, kWave - 1, kWave);
+#pragma unroll
+                    for (int p = 0; p < kSegPx; ++p) v[p][c] += before;
+                }
+            }
+            if (nx <= 0) continue;
+            uint32_t grey[kSegPx];
+#pragma unroll
+            for (int p = 0; p < kSegPx; ++p) {
+                uint32_t q[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    q[c] = v[p][c] & MASK;
+                    if (invert) q[c] = MASK - q[c];
+                }
+                uint32_t g = q[0];
+                if constexpr (NC == 3) {
+                    if (rgb) g = png_grey(q[0], q[1], q[2]);
+                }
+                grey[p] = dead ? 0u : g;
+            }
+            if (BITS == 8) {
+                uint8_t* o = (uint8_t*)out + f * frame_pitch + (long long)y * stride + xs;
+                if (nx >= kSegPx && ((uintptr_t)o & 15) == 0) {
+                    uint32_t d[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) d[i] = grey[4 * i] | grey[4 * i + 1] << 8 | grey[4 * i + 2] << 16 | grey[4 * i + 3] << 24;
+                    *(uint4*)o = make_uint4(d[0], d[1], d[2], d[3]);
+                } else {
+#pragma unroll
+                    for (int p = 0; p < kSegPx; ++p)
+                        if (p < nx) o[p] = (uint8_t)grey[p];
+                }
+            } else {
+                uint16_t* o = (uint16_t*)out + f * frame_pitch + (long long)y * stride + xs;
+                if (nx >= kSegPx && ((uintptr_t)o & 15) == 0) {
+                    uint32_t d[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) d[i] = (grey[2 * i] & 0xFFFFu) | grey[2 * i + 1] << 16;
+                    *(uint4*)o = make_uint4(d[0], d[1], d[2], d[3]);
+                    *(uint4*)(o + 8) = make_uint4(d[4], d[5], d[6], d[7]);
+                } else {
+#pragma unroll
+                    for (int p = 0; p < kSegPx; ++p)
+                        if (p < nx) o[p] = (uint16_t)grey[p];
+                }
+            }
+        }
+    }
+}
+
 bool tiff_info_ok(const mrgingham_amd_tiff_info& t) {
     return t.width >= 1 && t.height >= 1 && t.width <= 32767 && t.height <= 32767 && (t.bits == 8 || t.bits == 16) && t.samples >= 1 &&
            t.samples <= 4 && t.photometric >= 0 && t.photometric <= 2 && (t.photometric != 2 || t.samples >= 3) &&
@@ -269,24 +422,35 @@ int lzw_lanes_of(const mrgingham_amd_ctx* ctx) { return ctx->tiff_lzw_lanes > 0 
 int inflate_lanes_of(const mrgingham_amd_ctx* ctx) { return ctx->tiff_deflate_lanes > 0 ? ctx->tiff_deflate_lanes : kInflateLanes; }
 int codec_of(const mrgingham_amd_tiff_info& t) { return t.compression == 5 ? kCodecLzw : t.compression == 1 ? kCodecNone : kCodecDeflate; }
 
-// checked arguments -> the launches; grows the LZW / Deflate scratch
+// checked arguments -> the launches; grows the LZW / Deflate scratch.  tile_w == tile_l == 0: strip files.
 int launch_tiff_decode(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch, const mrgingham_amd_tiff_strip* d_strips,
-                       int strips_pitch, const int32_t* d_nstrips, int nframes, const mrgingham_amd_tiff_info& ti, void* d_out,
-                       int64_t frame_pitch, int stride, int32_t* d_status, int32_t* d_strip_status, hipStream_t s) {
+                       int strips_pitch, const int32_t* d_nstrips, int nframes, const mrgingham_amd_tiff_info& ti, int tile_w, int tile_l,
+                       void* d_out, int64_t frame_pitch, int stride, int32_t* d_status, int32_t* d_strip_status, hipStream_t s) {
     const int width = ti.width, height = ti.height, bpp = ti.samples * ti.bits / 8;
-    const uint32_t rowb = (uint32_t)width * bpp;
+    const bool tiled = tile_w > 0;
+    const int across = tiled ? (width + tile_w - 1) / tile_w : 0, down = tiled ? (height + tile_l - 1) / tile_l : 0;
+    // the bytes of a row of what a lane decodes: an image row, or a tile's
+    const uint32_t rowb = (uint32_t)(tiled ? tile_w : width) * bpp;
     const int codec = codec_of(ti);
     const bool lzw = codec == kCodecLzw, from_raw = codec != kCodecNone;
     const unsigned frame_blocks = (unsigned)((nframes + 63) / 64);
     const long long slots = (long long)nframes * strips_pitch;
     MRG_HIP_CHECK(hipMemsetAsync(d_status, 0, (size_t)nframes * sizeof(int32_t), s));
     hipLaunchKernelGGL(tiff_check_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, d_strips, strips_pitch, d_nstrips, nframes, height,
-                       rowb, (long long)file_pitch, codec, d_status);
+                       rowb, (long long)file_pitch, codec, tile_w, tile_l, across, down, d_status);
     const uint8_t* src = d_files;
     long long src_pitch = file_pitch;
     if (from_raw) {
         static_assert(kLzwBlock == kInflateBlock, "one rounding of the lanes for both");
-        const long long raw_pitch = ((long long)rowb * height + 15) & ~15ll;
+        static_assert(kTiffLzwMaxStrip20 == kTiffInflateMaxStrip, "one limit on a tile's decoded bytes");
+        long long raw_bytes = (long long)rowb * height;
+        if (tiled) {
+            // across * down tiles of tile_l x rowb bytes each.  Tiles of more than 1 MiB, or more tiles than strips_pitch
+            // records: tiff_check_kernel calls every frame dead, no lane decodes and no row is read -- nothing to hold
+            const long long tile_bytes = (long long)rowb * tile_l, tiles = (long long)across * down;
+            raw_bytes = tile_bytes > (long long)kTiffLzwMaxStrip20 || tiles > strips_pitch ? 16 : tiles * tile_bytes;
+        }
+        const long long raw_pitch = (raw_bytes + 15) & ~15ll;
         const int most = lzw ? lzw_lanes_of(ctx) : inflate_lanes_of(ctx);
         long long lanes = (slots + kLzwBlock - 1) / kLzwBlock * kLzwBlock;
         if (lanes > most) lanes = most;
@@ -297,14 +461,15 @@ int launch_tiff_decode(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t f
         if (rc) return rc;
         if ((rc = ensure(ctx, ctx->tiff_broken, (size_t)nframes * sizeof(int32_t)))) return rc;
         MRG_HIP_CHECK(hipMemsetAsync(ctx->tiff_broken.p, 0, (size_t)nframes * sizeof(int32_t), s));
-        if (lzw)
-            hipLaunchKernelGGL(tiff_lzw_kernel, dim3((unsigned)(lanes / kLzwBlock)), dim3(kLzwBlock), 0, s, d_files, (long long)file_pitch, d_strips,
-                               strips_pitch, d_nstrips, nframes, rowb, (uint8_t*)ctx->tiff_raw.p, raw_pitch, (uint32_t*)ctx->tiff_table.p, d_status,
-                               d_strip_status, (int32_t*)ctx->tiff_broken.p);
-        else
-            hipLaunchKernelGGL(tiff_inflate_kernel, dim3((unsigned)(lanes / kInflateBlock)), dim3(kInflateBlock), 0, s, d_files, (long long)file_pitch,
-                               d_strips, strips_pitch, d_nstrips, nframes, rowb, (uint8_t*)ctx->tiff_raw.p, raw_pitch,
-                               (uint16_t*)ctx->tiff_inflate_table.p, d_status, d_strip_status, (int32_t*)ctx->tiff_broken.p);
+#define MRG_TIFF_CODEC(KERNEL, BLOCK, TABLE_T, TABLE)                                                                                     \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)(lanes / BLOCK)), dim3(BLOCK), 0, s, d_files, (long long)file_pitch, d_strips, strips_pitch,  \
+                       d_nstrips, nframes, rowb, (uint8_t*)ctx->tiff_raw.p, raw_pitch, (TABLE_T*)TABLE.p, d_status, d_strip_status,          \
+                       (int32_t*)ctx->tiff_broken.p)
+        if (lzw && tiled) MRG_TIFF_CODEC(tiff_lzw_kernel<true>, kLzwBlock, uint32_t, ctx->tiff_table);
+        else if (lzw) MRG_TIFF_CODEC(tiff_lzw_kernel<false>, kLzwBlock, uint32_t, ctx->tiff_table);
+        else if (tiled) MRG_TIFF_CODEC(tiff_inflate_kernel<true>, kInflateBlock, uint16_t, ctx->tiff_inflate_table);
+        else MRG_TIFF_CODEC(tiff_inflate_kernel<false>, kInflateBlock, uint16_t, ctx->tiff_inflate_table);
+#undef MRG_TIFF_CODEC
         hipLaunchKernelGGL(tiff_verdict_kernel, dim3(frame_blocks), dim3(64), 0, s, (const int32_t*)ctx->tiff_broken.p, nframes, d_status);
         src = (const uint8_t*)ctx->tiff_raw.p;
         src_pitch = raw_pitch;
@@ -316,9 +481,18 @@ int launch_tiff_decode(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t f
     long long blocks = (nrows + kFinishBlock / kWave - 1) / (kFinishBlock / kWave);
     if (blocks > (long long)cus * 8) blocks = (long long)cus * 8;
 #define MRG_TIFF_CASE(B, C)                                                                                                              \
-    hipLaunchKernelGGL((tiff_finish_kernel<B, C>), dim3((unsigned)blocks), dim3(kFinishBlock), 0, s, src, src_pitch, limit, d_strips,      \
-                       strips_pitch, from_raw ? 1 : 0, width, height, nrows, ti.photometric == 2 ? 1 : 0, ti.photometric == 0 ? 1 : 0,           \
-                       ti.predictor == 2 ? 1 : 0, ti.big_endian, d_out, (long long)frame_pitch, stride, (const int32_t*)d_status)
+    do {                                                                                                                                 \
+        if (tiled)                                                                                                                       \
+            hipLaunchKernelGGL((tiff_finish_tiles_kernel<B, C>), dim3((unsigned)blocks), dim3(kFinishBlock), 0, s, src, src_pitch, limit,    \
+                               d_strips, strips_pitch, from_raw ? 1 : 0, width, height, nrows, tile_w, tile_l, across,                    \
+                               ti.photometric == 2 ? 1 : 0, ti.photometric == 0 ? 1 : 0, ti.predictor == 2 ? 1 : 0, ti.big_endian, d_out,    \
+                               (long long)frame_pitch, stride, (const int32_t*)d_status);                                                 \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((tiff_finish_kernel<B, C>), dim3((unsigned)blocks), dim3(kFinishBlock), 0, s, src, src_pitch, limit,          \
+                               d_strips, strips_pitch, from_raw ? 1 : 0, width, height, nrows, ti.photometric == 2 ? 1 : 0,                \
+                               ti.photometric == 0 ? 1 : 0, ti.predictor == 2 ? 1 : 0, ti.big_endian, d_out, (long long)frame_pitch,         \
+                               stride, (const int32_t*)d_status);                                                                         \
+    } while (0)
     const int ch = ti.samples;
     if (ti.bits == 8) {
         if (ch == 1) MRG_TIFF_CASE(8, 1); else if (ch == 2) MRG_TIFF_CASE(8, 2); else if (ch == 3) MRG_TIFF_CASE(8, 3); else MRG_TIFF_CASE(8, 4);
@@ -330,10 +504,16 @@ int launch_tiff_decode(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t f
     return 0;
 }
 
-// what makes two files of a chunk share a launch
-uint32_t launch_key(const mrgingham_amd_tiff_info& t) {
-    return (uint32_t)t.samples | (uint32_t)t.photometric << 4 | (uint32_t)codec_of(t) << 8 | (uint32_t)t.predictor << 12 |
-           (uint32_t)t.big_endian << 16;
+// what makes two files of a chunk share a launch: the fields of the kernels' arguments, the tile sizes among them (0 and 0
+// for strips)
+uint64_t launch_key(const mrgingham_amd_tiff_info& t, int tile_w, int tile_l) {
+    return (uint64_t)t.samples | (uint64_t)t.photometric << 4 | (uint64_t)codec_of(t) << 8 | (uint64_t)t.predictor << 12 |
+           (uint64_t)t.big_endian << 16 | (uint64_t)tile_w << 20 | (uint64_t)tile_l << 36;
+}
+
+bool tile_sizes_ok(int tile_w, int tile_l) {
+    if (tile_w == 0 && tile_l == 0) return true;
+    return tile_w >= kSegPx && tile_l >= 1 && tile_w <= 32767 && tile_l <= 32767 && tile_w % kSegPx == 0;
 }
 
 }  // namespace
@@ -348,23 +528,33 @@ void mrgingham_amd_tiff_geometry(int* lzw_lanes, int* segment_pixels, int* step_
     if (step_pixels) *step_pixels = kStepPx;
 }
 
-int mrgingham_amd_tiff_decode_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch,
-                                    const mrgingham_amd_tiff_strip* d_strips, int strips_pitch, const int32_t* d_nstrips, int nframes,
-                                    const mrgingham_amd_tiff_info* info, void* d_out, int64_t frame_pitch, int stride, int32_t* d_status,
-                                    int32_t* d_strip_status, void* stream) {
+int mrgingham_amd_tiff_decode_batch_tiled(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch,
+                                          const mrgingham_amd_tiff_strip* d_records, int records_pitch, const int32_t* d_nrecords,
+                                          int nframes, const mrgingham_amd_tiff_info* info, int tile_width, int tile_length, void* d_out,
+                                          int64_t frame_pitch, int stride, int32_t* d_status, int32_t* d_strip_status, void* stream) {
     if (!ctx) return MRGINGHAM_AMD_ERR_ARG;
-    if (!info || nframes < 0 || strips_pitch < 1 || frame_pitch < 0 || file_pitch < 0 ||
-        (nframes > 0 && (!d_files || !d_strips || !d_nstrips || !d_out || !d_status)))
+    if (!info || nframes < 0 || records_pitch < 1 || frame_pitch < 0 || file_pitch < 0 ||
+        (nframes > 0 && (!d_files || !d_records || !d_nrecords || !d_out || !d_status)))
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "bad TIFF batch descriptor");
     if (!tiff_info_ok(*info) || stride < info->width)
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "TIFF batch: sides 1..32767, 8 or 16 bits, 1..4 samples, photometric 0..2, compression 1, 5, 8 or 32946, predictor 1 or 2, stride >= width");
-    if ((file_pitch & 15) || ((uintptr_t)d_files & 15) || ((uintptr_t)d_strips & 7) || ((uintptr_t)d_nstrips & 3) || ((uintptr_t)d_status & 3) ||
+    if (!tile_sizes_ok(tile_width, tile_length))
+        return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "TIFF batch: tile width and length both 0 (strips), or a width that is a multiple of 16 and a length, 1..32767 each");
+    if ((file_pitch & 15) || ((uintptr_t)d_files & 15) || ((uintptr_t)d_records & 7) || ((uintptr_t)d_nrecords & 3) || ((uintptr_t)d_status & 3) ||
         ((uintptr_t)d_strip_status & 3) || (info->bits == 16 && ((uintptr_t)d_out & 1)))
         return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "TIFF batch: files 16-byte aligned, file_pitch a multiple of 16; 16-bit frames 2-byte aligned");
     if (nframes == 0) return 0;
     MRG_HIP_CHECK(hipSetDevice(ctx->device));
-    return launch_tiff_decode(ctx, d_files, file_pitch, d_strips, strips_pitch, d_nstrips, nframes, *info, d_out, frame_pitch, stride, d_status,
-                              d_strip_status, (hipStream_t)stream);  // (the stream used as given: NULL is HIP's default stream)
+    return launch_tiff_decode(ctx, d_files, file_pitch, d_records, records_pitch, d_nrecords, nframes, *info, tile_width, tile_length, d_out,
+                              frame_pitch, stride, d_status, d_strip_status, (hipStream_t)stream);  // (the stream used as given: NULL is HIP's default stream)
+}
+
+int mrgingham_amd_tiff_decode_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_files, int64_t file_pitch,
+                                    const mrgingham_amd_tiff_strip* d_strips, int strips_pitch, const int32_t* d_nstrips, int nframes,
+                                    const mrgingham_amd_tiff_info* info, void* d_out, int64_t frame_pitch, int stride, int32_t* d_status,
+                                    int32_t* d_strip_status, void* stream) {
+    return mrgingham_amd_tiff_decode_batch_tiled(ctx, d_files, file_pitch, d_strips, strips_pitch, d_nstrips, nframes, info, 0, 0, d_out,
+                                                 frame_pitch, stride, d_status, d_strip_status, stream);
 }
 
 int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height, int bits,
@@ -407,7 +597,9 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
     hipStream_t s = ctx->pix;
     const int64_t max_strip = ctx->tiff_lzw_max_strip, deflate_strip = ctx->tiff_deflate ? ctx->tiff_deflate_max_strip : 0;
     // per slot and file of its chunk: -1 failed, 0 decoded on the host (its samples lie in its area), 1 the device's
-    struct InSlot { int f0 = 0, n = 0; std::vector<int> kind; std::vector<mrgingham_amd_tiff_info> info; } in_slot[2];
+    // (tile: a tiled file's tile width and length, 0 and 0 for strips)
+    struct Tile { int32_t w = 0, l = 0; };
+    struct InSlot { int f0 = 0, n = 0; std::vector<int> kind; std::vector<mrgingham_amd_tiff_info> info; std::vector<Tile> tile; } in_slot[2];
     struct Buffers { std::vector<uint8_t> file; Image im; };
     auto stage = [&](int k, int f0, int n) -> int {
         uint8_t* const pin = (uint8_t*)ctx->loader_slot[k].pin.p;
@@ -417,11 +609,13 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
         S.f0 = f0; S.n = n;
         S.kind.assign((size_t)n, -1);
         S.info.assign((size_t)n, mrgingham_amd_tiff_info{});
+        S.tile.assign((size_t)n, Tile{});
         for_files<Buffers>(ctx->pool, nthreads, n, [&](int i, Buffers& t) {
             int32_t st = -1;
             int kind = -1;
             uint8_t* dst = pin + (size_t)i * area;
             mrgingham_amd_tiff_info ti{};
+            Tile tile;
             size_t ns = 0;
             h_ns[i] = 0;
             try {
@@ -435,13 +629,20 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
                     fclose(f);
                     if (whole) {
                         staged = true;
-                        head = tiff_layout_ex(dst, got, max_strip, deflate_strip, &ti, h_strips + (size_t)i * height, (size_t)height, &ns);
+                        head = tiff_layout_tiled(dst, got, max_strip, deflate_strip, &ti, &tile.w, &tile.l, h_strips + (size_t)i * height,
+                                                 (size_t)height, &ns);
                     } else if (read_file(filenames[f0 + i], t.file)) {
-                        head = tiff_layout_ex(t.file.data(), t.file.size(), max_strip, deflate_strip, &ti, nullptr, 0, &ns);
+                        head = tiff_layout_tiled(t.file.data(), t.file.size(), max_strip, deflate_strip, &ti, &tile.w, &tile.l, nullptr, 0, &ns);
                         if (head == 0) head = kTiffNotTaken;
                     }
                 }
-                // (-2: more strips than rows of THIS batch's frames -- a file of another height)
+                // (-2: more strips than rows of THIS batch's frames -- a file of another height; or a tiled file with more
+                // tiles than rows, which a slot has no records for: the host decoder's)
+                if (head == -2 && tile.w > 0 && ti.height == height) head = kTiffNotTaken;
+                // (and so does one whose tiles are mostly padding: the device holds every tile of a chunk decoded, the host
+                // decoder one tile; four times what the samples of a frame of four channels take, and 1 MiB, pass)
+                if (head == 0 && tile.w > 0 && (uint64_t)ns * tile.w * tile.l * ti.samples * (ti.bits / 8) > 16 * (uint64_t)px_bytes + (1u << 20))
+                    head = kTiffNotTaken;
                 if (head == 0 || head == kTiffNotTaken || head == -2) {
                     if (ti.width != width || ti.height != height || ti.bits != bits) st = -2;
                     else if (head == 0 && staged) {
@@ -461,6 +662,7 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
             }
             S.kind[(size_t)i] = kind;
             S.info[(size_t)i] = ti;
+            S.tile[(size_t)i] = tile;
             h_status[f0 + i] = st;
         });
         // The host threads wrote file i's records at a pitch of `height`, the most a file can have.  The launches get a dense
@@ -479,7 +681,9 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
         MRG_HIP_CHECK(hipMemcpyAsync(dev + off_ns, pin + off_ns, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
         MRG_HIP_CHECK(hipMemsetAsync(dev + off_status, 0, (size_t)n * sizeof(int32_t), s));
         auto same = [&](int a, int b) {
-            return S.kind[(size_t)a] == S.kind[(size_t)b] && (S.kind[(size_t)a] != 1 || launch_key(S.info[(size_t)a]) == launch_key(S.info[(size_t)b]));
+            return S.kind[(size_t)a] == S.kind[(size_t)b] &&
+                   (S.kind[(size_t)a] != 1 || launch_key(S.info[(size_t)a], S.tile[(size_t)a].w, S.tile[(size_t)a].l) ==
+                                                  launch_key(S.info[(size_t)b], S.tile[(size_t)b].w, S.tile[(size_t)b].l));
         };
         for (int i = 0; i < n;) {
             int e = i + 1;
@@ -487,8 +691,8 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
             if (S.kind[(size_t)i] == 1) {
                 int lrc;
                 if ((lrc = launch_tiff_decode(ctx, dev + (size_t)i * area, (int64_t)area, (const mrgingham_amd_tiff_strip*)(dev + off_strips) + (size_t)i * P,
-                                              P, (const int32_t*)(dev + off_ns) + i, e - i, S.info[(size_t)i],
-                                              out + (size_t)(f0 + i) * frame_pitch * es, frame_pitch, stride, (int32_t*)(dev + off_status) + i, nullptr, s)))
+                                              P, (const int32_t*)(dev + off_ns) + i, e - i, S.info[(size_t)i], S.tile[(size_t)i].w, S.tile[(size_t)i].l,
+                                              out +(size_t)(f0 + i) * frame_pitch * es, frame_pitch, stride, (int32_t*)(dev + off_status) + i, nullptr, s)))
                     return lrc;
             } else if (S.kind[(size_t)i] == 0) {
                 for (int q = i; q < e; ++q)
