@@ -71,7 +71,12 @@ extern "C" {
  *      Later, additive (the version stays 4): mrgingham_amd_tiff_layout_tiled and _tiff_decode_batch_tiled (tiled TIFF:
  *      LZW and Deflate tiles one lane each, tile rows gathered into image rows on the device); mrgingham_amd_read_image,
  *      _probe_image, _read_tiffs_batch and the file-list entry points read tiled files, which were unreadable before.
- *      mrgingham_amd_tiff_layout and _tiff_layout_ex go on calling any tile tag unreadable, and no option changes. */
+ *      mrgingham_amd_tiff_layout and _tiff_layout_ex go on calling any tile tag unreadable, and no option changes.
+ *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (kind 5) read Windows Bitmap files,
+ *      which were unreadable before; mrgingham_amd_bmp_layout, _bmp_unpack_batch, _bmp_unpack_geometry, _read_bmps_batch (BMP:
+ *      row order, row padding, sub-byte indices, the palette and grey on the device); options "bmp_chunk_frames",
+ *      "bmp_unpack"; mrgingham_amd_find_boards_files_ex4 (loader flag MRGINGHAM_AMD_FILES_BMP_DEVICE, which _ex3 goes on
+ *      refusing).  The device route of the file list is off unless asked for. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -363,8 +368,9 @@ bool find_chessboard_from_image_file_C(const char* filename, const int gridn, in
 
 /* The image decoder behind the two functions above and the command-line tool, on its own (host only, no
  * device needed): binary PGM (8 / 16 bit), non-interlaced PNG, baseline JPEG (see
- * mrgingham_amd_jpeg_coefficients for what is accepted) and strip or tiled TIFF (see mrgingham_amd_tiff_layout
- * and _tiff_layout_tiled for what is accepted).  `out` (may be NULL: sizes only)
+ * mrgingham_amd_jpeg_coefficients for what is accepted), strip or tiled TIFF (see mrgingham_amd_tiff_layout
+ * and _tiff_layout_tiled for what is accepted) and Windows Bitmap (see mrgingham_amd_bmp_layout for what is accepted).
+ * `out` (may be NULL: sizes only)
  * receives width*height grey bytes.  16-bit samples: cli_scaling = 0 keeps the high byte, what
  * cv::imread(IMREAD_GRAYSCALE) gives the file entry points; 1 rescales by 255/65535 with rounding, what
  * the CLI's convertTo does (mrgingham-from-image.cc:85-92).  Returns 0; -1 unreadable, unsupported or
@@ -543,6 +549,74 @@ int mrgingham_amd_pgm_unpack_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_payl
 int mrgingham_amd_read_pgms_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
                                   int bits, void* d_out, int64_t frame_pitch, int stride, int nthreads,
                                   int32_t* h_status);
+
+/* Windows Bitmap (BMP), host half (host only, no device needed): the one parser of a BMP's headers and palette, behind
+ * mrgingham_amd_read_image, _probe_image (kind 5) and _read_bmps_batch.  `data` is a whole file held in memory.  The subset
+ * is closed, and everything outside it is unreadable; every offset and product is checked in 64 bits against nbytes before
+ * anything is sized from it:
+ *   a "BM" file header; an info header of 40, 52, 56, 108 or 124 bytes (the 12-byte core header and the 64-byte OS/2 header:
+ *   unreadable); planes 1; width 1 .. 32767, |height| 1 .. 32767, a negative height = top-down rows;
+ *   bits 1, 4, 8 with compression 0: palette indices, the leftmost pixel in the most significant bits of a byte;
+ *   bits 8 with compression 1 (RLE8), bottom-up only: the host decoder's alone (MRGINGHAM_AMD_BMP_NOT_TAKEN);
+ *   bits 24 (B G R) and 32 (B G R X, the fourth byte ignored) with compression 0; bits 32 with compression 3 only with the
+ *   masks R 0x00FF0000, G 0x0000FF00, B 0x000000FF, behind a 40-byte header or inside a longer one;
+ *   16-bit files, RLE4, compressions 4, 5, 6, other masks, top-down RLE: unreadable.
+ *   Palette (bits <= 8): clrUsed entries, 2^bits when it is 0, more than 2^bits unreadable; B G R x per entry behind the
+ *   header (and its masks); it lies inside the file and ends at or before bfOffBits.  It is reduced to lut[256], the grey of
+ *   every index ((4899 R + 9617 G + 1868 B + 8192) >> 14; entries the file does not define are 0, so an index beyond the
+ *   palette reads 0); lut_identity: lut[i] == i for every index the depth can produce -- the grey camera file.
+ *   Rows are row_bytes = ((width*bits + 31) / 32) * 4 bytes; an uncompressed file is readable only when it holds
+ *   row_bytes * |height| bytes from payload_offset (bfOffBits) on.  bfSize and biSizeImage are neither trusted nor required.
+ *   RLE8: the stream runs from bfOffBits to the end of the file -- encoded runs, absolute runs padded to even, end of line,
+ *   end of bitmap, delta; pixels never written are index 0; a run that crosses the row's width or leaves the image is
+ *   unreadable, and so is a stream that ends without end-of-bitmap before the last row was begun.
+ * Returns 0: mrgingham_amd_bmp_unpack_batch takes the file; MRGINGHAM_AMD_BMP_NOT_TAKEN (-3): readable, but the host
+ * decoder's alone (RLE8; the sizes and the table are reported); -1 unreadable.  info may be NULL.  Allocates nothing,
+ * never throws.  The output is always 8-bit grey. */
+typedef struct mrgingham_amd_bmp_info {
+    int32_t width, height;  /* height: rows (positive, whatever the row order) */
+    int32_t bits;           /* 1, 4, 8, 24, 32 */
+    int32_t compression;    /* 0, 1 (RLE8), 3 (the one set of masks: pixels as with 0) */
+    int32_t top_down;       /* 1: the first row of the pixel array is the top row */
+    int32_t row_bytes;
+    int64_t payload_offset; /* bfOffBits */
+    uint8_t lut[256];
+    int32_t lut_identity;
+} mrgingham_amd_bmp_info;
+#define MRGINGHAM_AMD_BMP_NOT_TAKEN -3
+int mrgingham_amd_bmp_layout(const uint8_t* data, size_t nbytes, mrgingham_amd_bmp_info* info);
+
+/* BMP pixel arrays to grey frames on the device: frame f's pixel array as it lies in the file -- height rows of row_bytes
+ * bytes -- at d_payload + f*payload_pitch (BYTES; d_payload 16-byte aligned, payload_pitch a multiple of 16 and
+ * >= row_bytes*height), its grey table at d_lut + 256*f (not read for bits 24 and 32, nor for bits 8 with lut_identity;
+ * may then be NULL).  d_out: uint8_t frames, frame f row y at d_out + f*frame_pitch + y*stride; only the width x height
+ * samples are written, what lies between width and stride stays untouched; d_out may sit at any byte address.  Row y of a
+ * frame is row height-1-y of its pixel array unless top_down.  One streaming launch sized to the device: a lane produces
+ * one 16-byte word of a destination row per step from the 2, 8, 16, 48 or 64 source bytes of its 16 pixels, read as
+ * aligned dwords and never beyond the row's padded length, with the text the host decoder runs (csrc/bmp_pixels.h).
+ * Asynchronous on `stream` (NULL = default); allocates nothing.  Arguments are checked like mrgingham_amd_pgm_unpack_batch's
+ * (MRGINGHAM_AMD_ERR_ARG, nothing written); bits outside {1, 4, 8, 24, 32} are refused. */
+int mrgingham_amd_bmp_unpack_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_payload, int64_t payload_pitch,
+                                   const uint8_t* d_lut, int nframes, int width, int height, int bits, int top_down,
+                                   int lut_identity, uint8_t* d_out, int64_t frame_pitch, int stride, void* stream);
+
+/* the schedule of that launch: lanes per workgroup, and the workgroups per compute unit the grid is capped at; a row is
+ * taken by the power of two of lanes that covers its 16-byte words, so a launch has
+ * CUs * max_workgroups_per_cu * (lanes_per_workgroup / lanes of a row) row slots and loops over the rows beyond */
+void mrgingham_amd_bmp_unpack_geometry(int* lanes_per_workgroup, int* max_workgroups_per_cu);
+
+/* nfiles BMP files of ONE size straight into device frames (uint8, layout as d_out above); depth, row order and palette
+ * may differ from file to file.  Per file a host thread (nthreads of them; <= 0: all cores, at most 32) reads the header
+ * bytes, runs mrgingham_amd_bmp_layout and reads the grey table and the pixel array from the file straight into page-locked
+ * staging, at a 16-byte aligned offset -- no sample is touched on the host --; a chunk of files goes up in one copy and
+ * through one launch of mrgingham_amd_bmp_unpack_batch per run of files with equal bits, row order and lut_identity while
+ * the host threads read the next.  An RLE8 file is decoded by its host thread and copied into its frame.  h_status[f]: 0
+ * loaded, -1 unreadable or not a BMP by mrgingham_amd_read_image's rules, -2 a BMP of another size; the frame of a failed
+ * file is zero-filled.  SYNCHRONOUS: d_out is complete on return.  Returns MRGINGHAM_AMD_OK also when files failed.
+ * Completes the find_boards jobs in flight first and restores the caller's HIP device.  The chunk buffers are those of
+ * mrgingham_amd_read_jpegs_batch, within the same 1 GiB (options "bmp_chunk_frames", "bmp_unpack"). */
+int mrgingham_amd_read_bmps_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
+                                  uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status);
 
 /* TIFF, host half (host only, no device needed): the one parser of a TIFF's first image file directory, behind
  * mrgingham_amd_read_image, _probe_image and _read_tiffs_batch.  `data` is a whole file held in memory.  The subset is
@@ -779,7 +853,8 @@ int mrgingham_amd_find_boards_submit_ex(mrgingham_amd_ctx* ctx, const mrgingham_
  * What mrgingham_amd_read_image would produce for a file, from its header alone (host only, no device needed, nothing
  * is decoded): *width, *height, *bits (8 or 16), *kind (1 binary PGM, 2 PNG, 3 baseline JPEG: the header parse of
  * mrgingham_amd_jpeg_coefficients, up to and including SOS; 4 TIFF: mrgingham_amd_tiff_layout's parse of the directory
- * and the strip table).  Any output pointer may be NULL.  Returns 0; -1 for what
+ * and the strip table; 5 BMP: mrgingham_amd_bmp_layout's parse of the headers and the palette, from the file's first
+ * 4096 bytes and its size -- an RLE8 file is read whole and its stream walked).  Any output pointer may be NULL.  Returns 0; -1 for what
  * read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut short or
  * breaks a rule (sides above 32767, interlaced PNG, progressive JPEG, ...), a PGM shorter than its header promises.  A
  * file that passes may still fail to decode.  Never sizes anything from an unchecked field. */
@@ -829,8 +904,8 @@ typedef struct mrgingham_amd_files_options {
     int device;       /* -1: the device of the calling thread's context (mrgingham_amd_thread_device) */
 } mrgingham_amd_files_options;
 #define MRGINGHAM_AMD_FILES_CHUNKS 0           /* chunks that went through the ring */
-#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch (PNG_DEVICE) / _read_pgms_batch (DEEP_CHUNKS: 16-bit PGM) / _read_tiffs_batch (TIFF_DEVICE) */
-#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (8-bit PGM / PNG / TIFF; 16-bit PNG / TIFF with DEEP_CHUNKS alone) */
+#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch (PNG_DEVICE) / _read_pgms_batch (DEEP_CHUNKS: 16-bit PGM) / _read_tiffs_batch (TIFF_DEVICE) / _read_bmps_batch (BMP_DEVICE) */
+#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (8-bit PGM / PNG / TIFF, BMP; 16-bit PNG / TIFF with DEEP_CHUNKS alone) */
 #define MRGINGHAM_AMD_FILES_ONE_IMAGE 3        /* files through the one-image path */
 #define MRGINGHAM_AMD_FILES_UNREADABLE 4       /* files with status -1 ([1] + [2] + [3] + [4] = nfiles) */
 #define MRGINGHAM_AMD_FILES_DETECTOR_WAIT_MS 5 /* wall ms the calling thread waited for a loaded chunk: the loader bounds the run */
@@ -878,6 +953,17 @@ int mrgingham_amd_find_boards_files_ex2(const char* const* filenames, int nfiles
  * MRGINGHAM_AMD_ERR_ARG, as is any bit above the four flags.  Same outputs. */
 #define MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE 8
 int mrgingham_amd_find_boards_files_ex3(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
+                                        double* h_boards, signed char* h_levels, signed char* h_found_level,
+                                        int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
+                                        double* stats, int nstats, int loader_flags);
+
+/* mrgingham_amd_find_boards_files_ex3 with one more loader flag (which _ex3 goes on refusing).  Without it BMP files behave
+ * as 8-bit PGM files do: files of one size share chunks and are decoded by the loader's host threads
+ * (MRGINGHAM_AMD_FILES_HOST_DECODED).  MRGINGHAM_AMD_FILES_BMP_DEVICE: runs of consecutive BMP slots of a chunk go through
+ * mrgingham_amd_read_bmps_batch on the loader context and are counted under MRGINGHAM_AMD_FILES_DEVICE_LOADED.  Same
+ * outputs.  Any bit above the five flags is MRGINGHAM_AMD_ERR_ARG. */
+#define MRGINGHAM_AMD_FILES_BMP_DEVICE 16
+int mrgingham_amd_find_boards_files_ex4(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
                                         double* h_boards, signed char* h_levels, signed char* h_found_level,
                                         int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
                                         double* stats, int nstats, int loader_flags);
@@ -1034,6 +1120,10 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *   "png_chunk_frames"    test hook: the same for mrgingham_amd_read_pngs_batch.
  *   "pgm_chunk_frames"    test hook: the same for mrgingham_amd_read_pgms_batch.
  *   "tiff_chunk_frames"   test hook: the same for mrgingham_amd_read_tiffs_batch.
+ *   "bmp_chunk_frames"    test hook: the same for mrgingham_amd_read_bmps_batch.
+ *   "bmp_unpack"          1 (default): mrgingham_amd_read_bmps_batch sends the files' pixel arrays through
+ *                         mrgingham_amd_bmp_unpack_batch; 0: its host threads decode every file (the leg to compare
+ *                         against).  Same frames and statuses.
  *   "tiff_lzw_max_strip"  decoded bytes of an LZW strip, 1 .. 1048576 (the limit of the kernel's table entries; default
  *                         65536): a file with a larger strip keeps the host threads in mrgingham_amd_read_tiffs_batch.  It
  *                         bounds the serial work of one lane: on 64 12 MP files mrgingham_amd_read_tiffs_batch was measured

@@ -310,9 +310,48 @@ def tiff_geometry():
     return a.value, b.value, c.value
 
 
+BMP_NOT_TAKEN = -3
+
+
+class BmpLayout:
+    """What bmp_layout found in a Windows Bitmap: height, width, bits (1, 4, 8, 24, 32), compression (0, 1 RLE8, 3 the one
+    set of masks), top_down, payload_offset, row_bytes, lut (uint8 [256]: the grey of every palette index, 0 where the
+    file defines none), lut_identity; taken: the device route (Detector.bmp_unpack) takes the file, False: read_image's
+    decoder alone reads it (RLE8); rc: the C call's return value (0 or BMP_NOT_TAKEN)."""
+    FIELDS = ("width", "height", "bits", "compression", "top_down", "row_bytes", "payload_offset", "lut_identity")
+
+    def __init__(self, info, rc):
+        for n in self.FIELDS:
+            setattr(self, n, int(getattr(info, n)))
+        self.lut = np.frombuffer(bytes(info.lut), np.uint8).copy()
+        self.rc, self.taken = int(rc), rc == 0
+
+    def __repr__(self):
+        return "BmpLayout(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.FIELDS) + f", rc={self.rc})"
+
+
+def bmp_layout(data):
+    """The headers and the palette of a Windows Bitmap held in memory, whole (host only; mrgingham_amd_bmp_layout, which has
+    the subset this library reads): -> BmpLayout, or None when the data is not a BMP this library reads."""
+    buf = bytes(data)
+    info = _lib.BmpInfo()
+    rc = _lib.lib().mrgingham_amd_bmp_layout(buf, len(buf), ctypes.byref(info))
+    if rc not in (0, BMP_NOT_TAKEN):
+        return None
+    return BmpLayout(info, rc)
+
+
+def bmp_unpack_geometry():
+    """(lanes_per_workgroup, max_workgroups_per_cu) of the BMP unpack launch (mrgingham_amd_bmp_unpack_geometry)."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _lib.lib().mrgingham_amd_bmp_unpack_geometry(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
 def read_image(filename, cli_scaling=False):
-    """Decode a binary PGM, non-interlaced PNG, baseline JPEG or strip or tiled TIFF (uncompressed, LZW, PackBits, Deflate; grey or
-    RGB, 8 or 16 bit) to uint8 [H, W] with the library's own decoder (host only).
+    """Decode a binary PGM, non-interlaced PNG, baseline JPEG, strip or tiled TIFF (uncompressed, LZW, PackBits, Deflate; grey or
+    RGB, 8 or 16 bit) or Windows Bitmap (1, 4, 8 bit palette, RLE8, 24 and 32 bit; bmp_layout has the subset) to uint8 [H, W]
+    with the library's own decoder (host only).
     16-bit files: the high byte (cv::imread(IMREAD_GRAYSCALE)) or, with cli_scaling, the CLI's
     convertTo(255/65535).  None when the file is unreadable, unsupported or malformed."""
     L = _lib.lib()
@@ -330,8 +369,8 @@ def read_image(filename, cli_scaling=False):
 
 def probe_image(filename):
     """What read_image would produce for the file, from its header alone (mrgingham_amd_probe_image; host only, nothing is
-    decoded): (height, width, bits, kind) with kind 1 binary PGM, 2 PNG, 3 baseline JPEG, 4 TIFF; None for a file that is
-    unreadable at header level."""
+    decoded): (height, width, bits, kind) with kind 1 binary PGM, 2 PNG, 3 baseline JPEG, 4 TIFF, 5 BMP (always 8 bits: the
+    grey read_image gives; the stream of an RLE8 file is walked); None for a file that is unreadable at header level."""
     w, h, b, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     if _lib.lib().mrgingham_amd_probe_image(os.fsencode(filename), ctypes.byref(w), ctypes.byref(h), ctypes.byref(b),
                                             ctypes.byref(k)) != 0:
@@ -359,8 +398,8 @@ FILES_STATS = ("chunks", "files_device_loader", "files_host_decoded", "files_one
 
 def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_radius=1, refine=True, batch=64, nthreads=0,
                       entropy="host", device=None, progress=None, png="host", deep="one", tiff="host",
-                      tiff_deflate="host"):
-    """A list of image files (binary PGM, PNG, baseline JPEG, TIFF; any sizes) to boards (mrgingham_amd_find_boards_files): a
+                      tiff_deflate="host", bmp="host"):
+    """A list of image files (binary PGM, PNG, baseline JPEG, TIFF, BMP; any sizes) to boards (mrgingham_amd_find_boards_files): a
     loader thread fills chunks of `batch` equally-sized frames on the device -- JPEG through the batch loader,
     entropy="device": Huffman-decoded on the device as well -- while the calling thread preprocesses and searches the
     chunks before them.  Per file the same numbers as read_image + the one-image path with the same options.
@@ -377,7 +416,13 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
     chunks and are decoded on the loader's host threads, 16-bit files follow `deep`; tiff="device": the runs of TIFF files
     of a chunk go through the TIFF batch loader (Detector.read_tiffs: the host threads only read the files, LZW strips are
     decoded one lane each) and count as files_device_loader; same numbers.  tiff_deflate="device", with tiff="device" only:
-    the Deflate strips of those files are decoded on the device as well, else the loader's host threads inflate them."""
+    the Deflate strips of those files are decoded on the device as well, else the loader's host threads inflate them.
+    BMP files behave as 8-bit PGM files do: they share chunks and are decoded on the loader's host threads
+    (files_host_decoded); bmp="device": the runs of BMP files of a chunk go through the BMP batch loader (Detector.read_bmps:
+    the host threads only read the files, the device unpacks the pixel arrays) and count as files_device_loader; same
+    numbers."""
+    if bmp not in ("host", "device"):
+        raise ValueError('find_boards_files: bmp is "host" or "device"')
     if tiff not in ("host", "device"):
         raise ValueError('find_boards_files: tiff is "host" or "device"')
     if tiff_deflate not in ("host", "device") or (tiff_deflate == "device" and tiff != "device"):
@@ -409,10 +454,10 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
                 raised.append(e)
     cb = _lib.PROGRESS_F(on_progress)
     arr = (ctypes.c_char_p * max(n, 1))(*names)
-    rc = L.mrgingham_amd_find_boards_files_ex3(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
+    rc = L.mrgingham_amd_find_boards_files_ex4(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
                                                status.ctypes.data, cb, None, stats.ctypes.data, len(stats),
                                                int(png == "device") | 2 * int(deep == "chunks") | 4 * int(tiff == "device") |
-                                               8 * int(tiff_deflate == "device"))
+                                               8 * int(tiff_deflate == "device") | 16 * int(bmp == "device"))
     if raised:
         raise raised[0]
     if rc == -1:
@@ -1131,6 +1176,67 @@ class Detector:
         arr = (ctypes.c_char_p * B)(*names)
         t.cuda.current_stream(self.device).synchronize()
         self._check(self.L.mrgingham_amd_read_pgms_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
+                                                         status.ctypes.data))
+        return frames, status
+
+    def bmp_unpack(self, payload, lut, height, width, bits, top_down=False, out=None):
+        """The pixel arrays of Windows Bitmap files to grey frames on the device (mrgingham_amd_bmp_unpack_batch), on torch's
+        current stream: payload uint8 [B, P] device tensor, contiguous and 16-byte aligned, P a multiple of 16 and at least
+        row_bytes*height with row_bytes = ((width*bits + 31) // 32) * 4 -- row f holds file f's pixel array as it lies in
+        the file from bfOffBits on; lut uint8 [B, 256] device tensor, contiguous: the grey tables (bmp_layout(..).lut) for
+        bits 1, 4 and 8 -- None at 8 bits: the identity table, a flipped copy; not looked at for bits 24 and 32
+        -> uint8 [B, height, width].  top_down: row 0 of the array is the top row (a negative height in the file).  `out`: a
+        [B, height, >= width] uint8 device tensor (unit column stride, any byte address) to write into; what lies beyond
+        `width` is not touched."""
+        t = self.torch
+        if bits not in (1, 4, 8, 24, 32):
+            raise ValueError("bmp_unpack: bits 1, 4, 8, 24 or 32")
+        rowb = (width * bits + 31) // 32 * 4
+        if not (payload.is_cuda and payload.dtype == t.uint8 and payload.dim() == 2 and payload.is_contiguous()
+                and payload.shape[1] % 16 == 0 and payload.shape[1] >= height * rowb and payload.data_ptr() % 16 == 0):
+            raise ValueError("bmp_unpack: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least row_bytes*height")
+        B = payload.shape[0]
+        need_lut = bits < 8 or (bits == 8 and lut is not None)
+        if bits < 8 and lut is None:
+            raise ValueError("bmp_unpack: bits 1 and 4 need the grey tables")
+        if need_lut and not (lut.is_cuda and lut.dtype == t.uint8 and tuple(lut.shape) == (B, 256) and lut.is_contiguous()):
+            raise ValueError("bmp_unpack: lut is a contiguous uint8 [B,256] tensor on the device")
+        if out is None:
+            out = t.empty((B, height, width), dtype=t.uint8, device=payload.device)
+        if not (out.is_cuda and out.dtype == t.uint8 and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
+                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
+            raise ValueError("bmp_unpack: out is a uint8 [B,height,>=width] tensor on the device with unit column stride")
+        stream = t.cuda.current_stream(payload.device).cuda_stream
+        self._check(self.L.mrgingham_amd_bmp_unpack_batch(
+            self.ctx, payload.data_ptr(), payload.shape[1], lut.data_ptr() if need_lut else None, B, int(width), int(height), int(bits),
+            int(bool(top_down)), int(bits == 8 and lut is None), out.data_ptr(), out.stride(0) if B > 1 else height * out.stride(1),
+            out.stride(1) if height > 1 else out.shape[2], stream))
+        return out[:, :, :width]
+
+    def read_bmps(self, paths, nthreads=0):
+        """Windows Bitmap files of one size straight into device frames (mrgingham_amd_read_bmps_batch); depth, row order and
+        palette may differ from file to file: `nthreads` host threads (0: all cores, at most 32) read the grey tables and
+        the pixel arrays from the files into page-locked staging, the device flips and unpads the rows, unpacks the indices,
+        looks up the palette and reduces colour to grey (option "bmp_unpack" 0: the host threads decode instead); RLE8 files
+        are decoded by their host thread.  -> (frames uint8 [B,H,W] on the device, status int32 [B] numpy: 0 loaded, -1
+        unreadable or not a BMP, -2 a BMP of another size; failed frames are zero).  The size is that of the first file
+        whose header parses (none does: frames [B,0,0]).  Synchronous."""
+        t = self.torch
+        names = [os.fsencode(p) for p in paths]
+        B = len(names)
+        status = np.full((B,), -1, dtype=np.int32)
+        H = W = 0
+        for name in names:
+            probe = probe_image(name)
+            if probe is not None and probe[3] == 5:
+                H, W = probe[0], probe[1]
+                break
+        frames = t.zeros((B, H, W), dtype=t.uint8, device=self.device)
+        if B == 0 or H == 0:
+            return frames, status
+        arr = (ctypes.c_char_p * B)(*names)
+        t.cuda.current_stream(self.device).synchronize()
+        self._check(self.L.mrgingham_amd_read_bmps_batch(self.ctx, arr, B, W, H, frames.data_ptr(), H * W, W, int(nthreads),
                                                          status.ctypes.data))
         return frames, status
 

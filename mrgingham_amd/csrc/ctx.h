@@ -308,6 +308,11 @@ struct mrgingham_amd_ctx {
     // mrgingham_amd_read_pgms_batch (pgm_unpack.hip): on loader_slot within jpeg_coef_budget as well (staging: the files'
     // payloads); option "pgm_chunk_frames" (test hook): at most that many files per chunk, 0 = by the budget
     int pgm_chunk_frames = 0;
+    // mrgingham_amd_read_bmps_batch (bmp_unpack.hip): on loader_slot within jpeg_coef_budget as well (staging: the files'
+    // grey tables and pixel arrays); options "bmp_chunk_frames" (test hook, as above) and "bmp_unpack" (1: the device
+    // unpacks the pixel arrays; 0: the host threads decode every file)
+    int bmp_chunk_frames = 0;
+    int bmp_unpack = 1;
     // mrgingham_amd_read_tiffs_batch / _tiff_decode_batch (tiff_decode.hip): the loader runs on loader_slot within
     // jpeg_coef_budget too (staging: the files as they lie on disk, their strip tables); tiff_raw: the decoded strips of an
     // LZW launch, rowbytes x height per frame; tiff_table: 4096 dwords per lane in flight, interleaved by lane;

@@ -1,5 +1,6 @@
 // See image_io.h.
 #include "image_io.h"
+#include "bmp_pixels.h"
 #include "jpeg.h"
 #include "png_filter.h"
 #include "tiff_inflate.h"
@@ -497,6 +498,131 @@ static bool decode_tiff(const std::vector<uint8_t>& b, Image& im) {
     return true;
 }
 
+// ---- Windows Bitmap (image_io.h: bmp_layout; include/mrgingham_amd.h has the subset)
+
+// The RLE8 stream s[0, n) of a bottom-up file, from bfOffBits to the end of the file: the walk that decides whether it
+// keeps the rules and, with out != NULL (w * h bytes the caller has filled with lut[0]), the decoder.
+static bool bmp_rle8(const uint8_t* s, size_t n, int w, int h, const uint8_t* lut, uint8_t* out) {
+    size_t p = 0;
+    int x = 0, y = 0;  // (y counts from the bottom row)
+    for (;;) {
+        if (n - p < 2) return y >= h - 1;  // no end-of-bitmap: fine once the last row was begun
+        const int c = s[p], v = s[p + 1];
+        p += 2;
+        if (c > 0) {  // an encoded run
+            if (y >= h || c > w - x) return false;
+            if (out) memset(out + (size_t)(h - 1 - y) * w + x, lut[v], (size_t)c);
+            x += c;
+        } else if (v == 0) {  // end of line
+            x = 0;
+            if (y < h) ++y;
+        } else if (v == 1) {  // end of bitmap
+            return true;
+        } else if (v == 2) {  // delta
+            if (n - p < 2) return false;
+            x += s[p];
+            y += s[p + 1];
+            p += 2;
+            if (x > w || y > h) return false;
+        } else {  // an absolute run, padded to even
+            if (y >= h || v > w - x || n - p < (size_t)v) return false;
+            if (out)
+                for (int i = 0; i < v; ++i) out[(size_t)(h - 1 - y) * w + x + i] = lut[s[p + i]];
+            x += v;
+            p += (size_t)v + (v & 1);
+            if (p > n) p = n;  // (the pad byte of a run that ends the file)
+        }
+    }
+}
+
+int bmp_layout(const uint8_t* b, size_t have, size_t file_size, mrgingham_amd_bmp_info* info_out) {
+    if (!b || have > file_size || have < 14 + 40 || b[0] != 'B' || b[1] != 'M') return -1;
+    auto u16 = [&](size_t p) { return (uint32_t)(b[p] | b[p + 1] << 8); };
+    auto u32 = [&](size_t p) { return (uint32_t)b[p] | (uint32_t)b[p + 1] << 8 | (uint32_t)b[p + 2] << 16 | (uint32_t)b[p + 3] << 24; };
+    const uint64_t off = u32(10), hsize = u32(14);
+    // (12: the core header, 64: OS/2 -- other field widths)
+    if (hsize != 40 && hsize != 52 && hsize != 56 && hsize != 108 && hsize != 124) return -1;
+    if (14 + hsize > have) return -1;
+    const int32_t w = (int32_t)u32(18), hraw = (int32_t)u32(22);
+    const uint32_t planes = u16(26), bits = u16(28), comp = u32(30), used = u32(46);
+    if (planes != 1 || w < 1 || w > kMaxSide || hraw == INT32_MIN) return -1;
+    const bool top_down = hraw < 0;
+    const int32_t h = top_down ? -hraw : hraw;
+    if (h < 1 || h > kMaxSide) return -1;
+    uint64_t pal = 14 + hsize;  // where the palette begins
+    if (comp == 0) {
+        if (bits != 1 && bits != 4 && bits != 8 && bits != 24 && bits != 32) return -1;
+    } else if (comp == 1) {
+        if (bits != 8 || top_down) return -1;
+    } else if (comp == 3) {
+        if (bits != 32) return -1;
+        // the masks: behind a 40-byte header, inside a longer one (at the same place)
+        if (hsize == 40) pal += 12;
+        if (pal > have) return -1;
+        if (u32(54) != 0x00FF0000u || u32(58) != 0x0000FF00u || u32(62) != 0x000000FFu) return -1;
+    } else {
+        return -1;
+    }
+    mrgingham_amd_bmp_info bi;
+    memset(&bi, 0, sizeof(bi));
+    bi.width = w; bi.height = h; bi.bits = (int32_t)bits; bi.compression = (int32_t)comp; bi.top_down = top_down ? 1 : 0;
+    bi.row_bytes = (int32_t)((((uint64_t)w * bits + 31) / 32) * 4);
+    bi.payload_offset = (int64_t)off;
+    if (bits <= 8) {
+        const uint64_t most = (uint64_t)1 << bits, n = used ? used : most;
+        if (n > most) return -1;
+        const uint64_t end = pal + 4 * n;  // (at most 14 + 124 + 12 + 1024)
+        if (end > file_size || end > off) return -1;
+        if (end > have) return -1;  // (a caller that holds fewer than the first 4096 bytes of the file)
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint8_t* q = b + pal + 4 * i;
+            bi.lut[i] = (uint8_t)png_grey(q[2], q[1], q[0]);
+        }
+        bi.lut_identity = 1;
+        for (uint64_t i = 0; i < most; ++i)
+            if (bi.lut[i] != i) bi.lut_identity = 0;
+    } else if (off < pal) {
+        return -1;  // (the pixel array inside the headers)
+    }
+    if (off > file_size) return -1;
+    int rc = 0;
+    if (comp == 1) {
+        rc = kBmpNotTaken;
+        if (have == file_size && !bmp_rle8(b + off, (size_t)(file_size - off), w, h, bi.lut, nullptr)) return -1;
+    } else if ((uint64_t)bi.row_bytes * (uint64_t)h > file_size - off) {
+        return -1;
+    }
+    if (info_out) *info_out = bi;
+    return rc;
+}
+
+static bool decode_bmp(const std::vector<uint8_t>& b, Image& im) {
+    mrgingham_amd_bmp_info bi;
+    const int rc = bmp_layout(b.data(), b.size(), b.size(), &bi);
+    if (rc != 0 && rc != kBmpNotTaken) return false;
+    const int w = bi.width, h = bi.height;
+    const size_t n = (size_t)w * h;
+    im.w = w; im.h = h; im.depth = 8;
+    about_to_hold(im, n, 0);
+    if (rc == kBmpNotTaken) {
+        im.px8.assign(n, bi.lut[0]);
+        return bmp_rle8(b.data() + bi.payload_offset, b.size() - (size_t)bi.payload_offset, w, h, bi.lut, im.px8.data());
+    }
+    im.px8.resize(n);
+    const uint8_t* lut = bi.bits == 8 && bi.lut_identity ? nullptr : bi.lut;
+    for (int y = 0; y < h; ++y) {
+        const uint8_t* row = b.data() + bi.payload_offset + (size_t)bi.row_bytes * (size_t)(bi.top_down ? y : h - 1 - y);
+        uint8_t* o = &im.px8[(size_t)w * y];
+        for (int x0 = 0; x0 < w; x0 += 16) {
+            const int k = w - x0 < 16 ? w - x0 : 16;
+            uint32_t d[4];
+            bmp_pixels_any(row, bi.row_bytes, bi.bits, lut, x0, k, d);
+            for (int p = 0; p < k; ++p) o[x0 + p] = (uint8_t)(d[p >> 2] >> (8 * (p & 3)));
+        }
+    }
+    return true;
+}
+
 // 8-bit binary PGM, the format a calibration run usually feeds the tool: the pixels go from the file straight into
 // px8 -- no copy of the whole file in between (a 12 MB image: one pass over memory less per image).  Returns 1 = done,
 // 0 = not such a file (the general path decides), -1 = such a file, but broken.
@@ -532,14 +658,15 @@ bool read_image(const char* path, Image& im) {
         if (b[0] == 0x89 && b[1] == 'P') return decode_png(b, im);
         if (b[0] == 0xFF && b[1] == 0xD8) return decode_jpeg(b, im);
         if ((b[0] == 'I' && b[1] == 'I') || (b[0] == 'M' && b[1] == 'M')) return decode_tiff(b, im);
+        if (b[0] == 'B' && b[1] == 'M') return decode_bmp(b, im);
         return false;
     } catch (...) {  // std::bad_alloc / length_error on a file that claims more than can be held
         return false;
     }
 }
 
-// The header checks of decode_pgm / read_pgm8_direct, decode_png, decode_jpeg and decode_tiff without the decoding.  PGM
-// and PNG keep what they need in front: only the first kProbeBytes of such a file are read (a PGM whose comments push the
+// The header checks of decode_pgm / read_pgm8_direct, decode_png, decode_jpeg, decode_tiff and decode_bmp without the decoding.  PGM,
+// PNG and uncompressed BMP keep what they need in front: only the first kProbeBytes of such a file are read (a PGM whose comments push the
 // header beyond them is read whole); a JPEG is read whole, its tables may lie anywhere before SOS, and so is a TIFF.
 bool probe_image(const char* path, int* width, int* height, int* bits, int* kind) {
     constexpr size_t kProbeBytes = 4096;
@@ -598,6 +725,14 @@ bool probe_image(const char* path, int* width, int* height, int* bits, int* kind
                 ok = rc == 0 || rc == kTiffNotTaken;
             }
             w = ti.width; h = ti.height; d = ti.bits;
+        } else if (ok && b[0] == 'B' && b[1] == 'M') {
+            k = 5;
+            // the headers, the masks and the palette lie in the first bytes; the stream of an RLE8 file is walked whole
+            mrgingham_amd_bmp_info bi{};
+            int rc = bmp_layout(b.data(), b.size(), (size_t)size, &bi);
+            if (rc == kBmpNotTaken && b.size() < (size_t)size) rc = rest() ? bmp_layout(b.data(), b.size(), b.size(), &bi) : -1;
+            ok = rc == 0 || rc == kBmpNotTaken;
+            w = bi.width; h = bi.height; d = 8;
         } else {
             ok = false;
         }
@@ -667,6 +802,10 @@ void to_8bit(const Image& im, std::vector<uint8_t>& out) {
 
 extern "C" int mrgingham_amd_pgm_header(const uint8_t* data, size_t nbytes, int* width, int* height, int* bits, size_t* payload_offset) {
     return mrg::pgm_header(data, nbytes, width, height, bits, payload_offset);
+}
+
+extern "C" int mrgingham_amd_bmp_layout(const uint8_t* data, size_t nbytes, mrgingham_amd_bmp_info* info) {
+    return mrg::bmp_layout(data, nbytes, nbytes, info);
 }
 
 extern "C" int mrgingham_amd_tiff_layout(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, mrgingham_amd_tiff_info* info,

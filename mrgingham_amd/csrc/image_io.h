@@ -3,7 +3,8 @@
 // non-interlaced PNG (8 or 16 bit; grey, grey+alpha, RGB, RGBA, 8-bit palette) via zlib, baseline
 // JPEG (jpeg.h: sequential Huffman, one scan; the luma plane, byte for byte what libjpeg's default
 // decoder gives cv::imread(IMREAD_GRAYSCALE); progressive, arithmetic and multi-scan files are
-// unreadable) and strip or tiled TIFF (tiff_layout and tiff_layout_tiled below have the subset; LZW through tiff_lzw.h).  PNG and TIFF
+// unreadable), strip or tiled TIFF (tiff_layout and tiff_layout_tiled below have the subset; LZW through tiff_lzw.h) and
+// Windows Bitmap (bmp_layout below; the pixels through bmp_pixels.h).  PNG, TIFF and BMP
 // colour is reduced to grey with the fixed-point BT.601 weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14; byte-identity with cv::imread on colour files is not
 // claimed (its conversion depends on the codec build).
@@ -30,7 +31,7 @@ struct Image {
 bool read_image(const char* path, Image& im);
 // What read_image would produce, from the file's header alone (nothing is decoded): width, height, bits (8 or 16) and
 // kind -- 1 binary PGM, 2 PNG, 3 baseline JPEG (jpeg_coefficients' header parse, up to and including SOS), 4 TIFF
-// (tiff_layout_tiled: the IFD and the strip or tile table).  false for
+// (tiff_layout_tiled: the IFD and the strip or tile table), 5 BMP (bmp_layout).  false for
 // whatever read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut
 // short or breaks a rule (sides above 32767 included), a PGM shorter than its header promises.  A file that passes may
 // still fail to decode.  Never throws, never sizes anything from an unchecked field.
@@ -68,6 +69,14 @@ int tiff_layout_ex(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, in
 // that is a multiple of 16.  read_image, probe_image and the batch loader parse through this one.
 int tiff_layout_tiled(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip, int64_t deflate_max_strip, mrgingham_amd_tiff_info* info,
                       int32_t* tile_width, int32_t* tile_length, mrgingham_amd_tiff_strip* records, size_t capacity, size_t* nrecords);
+// The one parser of a Windows Bitmap's headers and palette, behind read_image, probe_image and the batch loader
+// (mrgingham_amd_bmp_layout has the contract and the subset).  `data` holds the file's first `have` bytes, file_size is
+// the size of the whole file: the headers, the masks and the palette end by byte 1174 at the latest, so the first 4096
+// bytes (or the whole of a shorter file) decide; the pixel array is checked against file_size alone.  0 the device route
+// takes the file; kBmpNotTaken readable, but the host decoder's alone (RLE8) -- with have == file_size the stream has
+// been walked, with fewer bytes only its header is judged; -1 unreadable.  Never throws, allocates nothing.
+constexpr int kBmpNotTaken = -3;
+int bmp_layout(const uint8_t* data, size_t have, size_t file_size, mrgingham_amd_bmp_info* info);
 // The IHDR fields of a PNG file as they stand, nothing judged (a routing hint: png_scanlines decides what is readable):
 // returns the colour type byte, -1 for a file that does not begin with a PNG signature and a whole IHDR.
 int png_header(const char* path, int* width, int* height, int* bits);
