@@ -76,7 +76,13 @@ extern "C" {
  *      which were unreadable before; mrgingham_amd_bmp_layout, _bmp_unpack_batch, _bmp_unpack_geometry, _read_bmps_batch (BMP:
  *      row order, row padding, sub-byte indices, the palette and grey on the device); options "bmp_chunk_frames",
  *      "bmp_unpack"; mrgingham_amd_find_boards_files_ex4 (loader flag MRGINGHAM_AMD_FILES_BMP_DEVICE, which _ex3 goes on
- *      refusing).  The device route of the file list is off unless asked for. */
+ *      refusing).  The device route of the file list is off unless asked for.
+ *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (kind 6) read binary PBM (P4)
+ *      and PAM (P7) files, which were unreadable before; mrgingham_amd_pnm_header, _pnm_unpack_batch,
+ *      _pnm_unpack_geometry, _read_pnms_batch (colour to grey, big-endian pairs and packed bits on the device); options
+ *      "pnm_chunk_frames", "pnm_unpack"; mrgingham_amd_find_boards_files_ex5 (loader flag MRGINGHAM_AMD_FILES_PNM_DEVICE,
+ *      which _ex4 goes on refusing).  mrgingham_amd_pgm_header goes on refusing every magic but P5; ASCII Netpbm (P1, P2, P3)
+ *      stays unreadable, and so does P6.  The device route of the file list is off unless asked for. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -369,7 +375,8 @@ bool find_chessboard_from_image_file_C(const char* filename, const int gridn, in
 /* The image decoder behind the two functions above and the command-line tool, on its own (host only, no
  * device needed): binary PGM (8 / 16 bit), non-interlaced PNG, baseline JPEG (see
  * mrgingham_amd_jpeg_coefficients for what is accepted), strip or tiled TIFF (see mrgingham_amd_tiff_layout
- * and _tiff_layout_tiled for what is accepted) and Windows Bitmap (see mrgingham_amd_bmp_layout for what is accepted).
+ * and _tiff_layout_tiled for what is accepted), Windows Bitmap (see mrgingham_amd_bmp_layout for what is accepted) and
+ * binary PBM and PAM (see mrgingham_amd_pnm_header for what is accepted).
  * `out` (may be NULL: sizes only)
  * receives width*height grey bytes.  16-bit samples: cli_scaling = 0 keeps the high byte, what
  * cv::imread(IMREAD_GRAYSCALE) gives the file entry points; 1 rescales by 255/65535 with rounding, what
@@ -618,6 +625,77 @@ void mrgingham_amd_bmp_unpack_geometry(int* lanes_per_workgroup, int* max_workgr
 int mrgingham_amd_read_bmps_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
                                   uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status);
 
+/* Binary Netpbm beyond P5 (PBM "P4", PAM "P7"), host half (host only, no device needed): the one parser of a
+ * Netpbm header, behind mrgingham_amd_read_image, _probe_image (kind 6) and _read_pnms_batch.  `data` is a whole file held
+ * in memory, or its first bytes.  The subset is closed, and everything outside it is unreadable:
+ *   Sides are 1 .. 32767.  Every product is checked in 64 bits against the file size before anything is sized from it.  A
+ *   file shorter than its header promises is unreadable.  Trailing bytes are ignored, as for P5.  Samples are never rescaled
+ *   by maxval, which is the library's P5 rule.
+ *   P4: magic, width, height.  White space and # comments are handled as in mrgingham_amd_pgm_header.  ONE white-space byte
+ *     follows the last number.  Rows are (width + 7) / 8 bytes, most significant bit first.  Bit 1 is black and reads 0.
+ *     Bit 0 reads 255.  Depth is reported as 8.
+ *   P5: exactly mrgingham_amd_pgm_header's verdicts and outputs (kind 1, unchanged; the payload is not measured here).
+ *   P6: unreadable, as before (tests/test_pgm_header.py pins such a file); R G B comes as P7 of depth 3.
+ *   P7: line 1 is "P7".  Then come lines of WIDTH, HEIGHT, DEPTH, MAXVAL, each followed by a decimal number.  Each must
+ *     appear exactly once, in any order.  TUPLTYPE lines may appear any number of times.  # lines and empty lines are
+ *     ignored.  A line ENDHDR closes the header.  The raster begins right behind its newline.  Any other token, a missing
+ *     or repeated field, or a DEPTH outside 1 .. 4 makes the file unreadable.  DEPTH decides the layout: 1 is grey, 2 is
+ *     grey plus an ignored sample, 3 is R G B, 4 is R G B plus an ignored sample.  Alpha is ignored, as PNG's is.  Samples
+ *     are one byte each below maxval 256, big-endian pairs from 256 on.  Grey of R G B is (4899 R + 9617 G + 1868 B + 8192)
+ *     >> 14, at 16 bits on the 16-bit samples, as 16-bit RGB PNG does.  A first
+ *     TUPLTYPE that begins with BLACKANDWHITE is taken only with depth 1 or 2 and maxval 1.  The first sample then reads
+ *     255 when non-zero and 0 otherwise.  With any other depth or maxval such a file is unreadable.  TUPLTYPE is otherwise
+ *     not judged.
+ *   ASCII Netpbm (P1, P2, P3), PAM depths above 4: unreadable.  Of a multi-image stream the first image is read.
+ * Byte identity with cv::imread on colour files is not claimed, as for PNG, TIFF and BMP (its conversion depends on the
+ * codec build).
+ * Returns 0; -1 unreadable; MRGINGHAM_AMD_PNM_HEADER_CUT (-2): the bytes end inside the header (of a whole file:
+ * unreadable; of a file's first bytes: more are needed).  info may be NULL.  Allocates nothing, never throws. */
+typedef struct mrgingham_amd_pnm_info {
+    int32_t width, height;
+    int32_t bits;            /* of a sample in the file: 1 (P4), 8, 16 */
+    int32_t channels;        /* samples per pixel, 1 .. 4; the grey comes from the first (1, 2) or the first three (3, 4) */
+    int32_t black_and_white; /* 1: the first sample reads 255 when non-zero and 0 otherwise (P7 BLACKANDWHITE) */
+    int32_t magic;           /* the digit: 4, 5, 6, 7 */
+    int32_t row_bytes;       /* (width + 7) / 8, or width * channels * bits / 8: rows follow each other without padding */
+    int64_t payload_offset;
+} mrgingham_amd_pnm_info;
+#define MRGINGHAM_AMD_PNM_HEADER_CUT -2
+int mrgingham_amd_pnm_header(const uint8_t* data, size_t nbytes, mrgingham_amd_pnm_info* info);
+
+/* Netpbm rasters to grey frames on the device: frame f's raster as it lies in the file -- height rows of row_bytes bytes,
+ * row y at byte y * row_bytes, whatever its alignment -- at d_payload + f*payload_pitch (BYTES; d_payload 16-byte aligned,
+ * payload_pitch a multiple of 16 and >= row_bytes*height).  bits 1: packed bits (channels 1); bits 8 and 16: channels
+ * 1 .. 4 samples per pixel, big-endian pairs at 16; black_and_white only with bits 8 and channels 1 or 2.  d_out: uint8_t
+ * frames for bits 1 and 8, native uint16_t frames for bits 16; frame f row y at d_out + f*frame_pitch + y*stride (SAMPLES);
+ * only the width x height samples are written, what lies between width and stride stays untouched; d_out may sit at any
+ * byte address (any even address at 16 bits).  One streaming launch sized to the device: a lane produces one 16-byte word
+ * of a destination row per step from the source bytes of its 16 (8 at 16 bits) pixels, read as aligned dwords, each once
+ * and none behind the payload's padded area, with the text the host decoder runs (csrc/pnm_pixels.h).  Asynchronous on
+ * `stream` (NULL = default); allocates nothing.  Arguments are checked like mrgingham_amd_bmp_unpack_batch's
+ * (MRGINGHAM_AMD_ERR_ARG, nothing written). */
+int mrgingham_amd_pnm_unpack_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_payload, int64_t payload_pitch, int nframes,
+                                   int width, int height, int bits, int channels, int black_and_white, void* d_out,
+                                   int64_t frame_pitch, int stride, void* stream);
+
+/* the schedule of that launch: lanes per workgroup, and the workgroups per compute unit the grid is capped at; a row is
+ * taken by the power of two of lanes that covers its 16-byte words, so a launch has
+ * CUs * max_workgroups_per_cu * (lanes_per_workgroup / lanes of a row) row slots and loops over the rows beyond */
+void mrgingham_amd_pnm_unpack_geometry(int* lanes_per_workgroup, int* max_workgroups_per_cu);
+
+/* nfiles binary Netpbm files (P4, P5, P7 in any mix) of ONE size and output depth (bits 8: uint8 frames -- P4 files and
+ * files of maxval below 256; bits 16: uint16 frames) straight into device frames (layout as d_out above).  Per file a host
+ * thread (nthreads of them; <= 0: all cores, at most 32) reads the header bytes, runs mrgingham_amd_pnm_header and reads
+ * the raster from the file straight into page-locked staging, at a 16-byte aligned offset -- no sample is touched on the
+ * host --; a chunk of files goes up in one copy and through one launch of mrgingham_amd_pnm_unpack_batch per run of files
+ * with the same layout while the host threads read the next.  h_status[f]: 0 loaded, -1 unreadable or not Netpbm by
+ * mrgingham_amd_read_image's rules, -2 another size or depth; the frame of a failed file is zero-filled.  SYNCHRONOUS:
+ * d_out is complete on return.  Returns MRGINGHAM_AMD_OK also when files failed.  Completes the find_boards jobs in flight
+ * first and restores the caller's HIP device.  The chunk buffers are those of mrgingham_amd_read_jpegs_batch, within the
+ * same 1 GiB (options "pnm_chunk_frames", "pnm_unpack"). */
+int mrgingham_amd_read_pnms_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
+                                  int bits, void* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status);
+
 /* TIFF, host half (host only, no device needed): the one parser of a TIFF's first image file directory, behind
  * mrgingham_amd_read_image, _probe_image and _read_tiffs_batch.  `data` is a whole file held in memory.  The subset is
  * closed, and everything outside it is unreadable; every field is checked before anything is sized from it:
@@ -854,7 +932,8 @@ int mrgingham_amd_find_boards_submit_ex(mrgingham_amd_ctx* ctx, const mrgingham_
  * is decoded): *width, *height, *bits (8 or 16), *kind (1 binary PGM, 2 PNG, 3 baseline JPEG: the header parse of
  * mrgingham_amd_jpeg_coefficients, up to and including SOS; 4 TIFF: mrgingham_amd_tiff_layout's parse of the directory
  * and the strip table; 5 BMP: mrgingham_amd_bmp_layout's parse of the headers and the palette, from the file's first
- * 4096 bytes and its size -- an RLE8 file is read whole and its stream walked).  Any output pointer may be NULL.  Returns 0; -1 for what
+ * 4096 bytes and its size -- an RLE8 file is read whole and its stream walked; 6 binary PBM or PAM:
+ * mrgingham_amd_pnm_header's parse, bits 8 for P4).  Any output pointer may be NULL.  Returns 0; -1 for what
  * read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut short or
  * breaks a rule (sides above 32767, interlaced PNG, progressive JPEG, ...), a PGM shorter than its header promises.  A
  * file that passes may still fail to decode.  Never sizes anything from an unchecked field. */
@@ -904,8 +983,8 @@ typedef struct mrgingham_amd_files_options {
     int device;       /* -1: the device of the calling thread's context (mrgingham_amd_thread_device) */
 } mrgingham_amd_files_options;
 #define MRGINGHAM_AMD_FILES_CHUNKS 0           /* chunks that went through the ring */
-#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch (PNG_DEVICE) / _read_pgms_batch (DEEP_CHUNKS: 16-bit PGM) / _read_tiffs_batch (TIFF_DEVICE) / _read_bmps_batch (BMP_DEVICE) */
-#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (8-bit PGM / PNG / TIFF, BMP; 16-bit PNG / TIFF with DEEP_CHUNKS alone) */
+#define MRGINGHAM_AMD_FILES_DEVICE_LOADED 1    /* files through mrgingham_amd_read_jpegs_batch (readable JPEG) or, if asked for, _read_pngs_batch (PNG_DEVICE) / _read_pgms_batch (DEEP_CHUNKS: 16-bit PGM) / _read_tiffs_batch (TIFF_DEVICE) / _read_bmps_batch (BMP_DEVICE) / _read_pnms_batch (PNM_DEVICE) */
+#define MRGINGHAM_AMD_FILES_HOST_DECODED 2     /* files decoded on host threads into a chunk (8-bit PGM / PNG / TIFF / PBM / PAM, BMP; 16-bit PNG / TIFF / PAM with DEEP_CHUNKS alone) */
 #define MRGINGHAM_AMD_FILES_ONE_IMAGE 3        /* files through the one-image path */
 #define MRGINGHAM_AMD_FILES_UNREADABLE 4       /* files with status -1 ([1] + [2] + [3] + [4] = nfiles) */
 #define MRGINGHAM_AMD_FILES_DETECTOR_WAIT_MS 5 /* wall ms the calling thread waited for a loaded chunk: the loader bounds the run */
@@ -964,6 +1043,18 @@ int mrgingham_amd_find_boards_files_ex3(const char* const* filenames, int nfiles
  * outputs.  Any bit above the five flags is MRGINGHAM_AMD_ERR_ARG. */
 #define MRGINGHAM_AMD_FILES_BMP_DEVICE 16
 int mrgingham_amd_find_boards_files_ex4(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
+                                        double* h_boards, signed char* h_levels, signed char* h_found_level,
+                                        int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
+                                        double* stats, int nstats, int loader_flags);
+
+/* mrgingham_amd_find_boards_files_ex4 with one more loader flag (which _ex4 goes on refusing).  Without it P4 and P7
+ * files (kind 6) behave as PGM files do: 8-bit files of one size share chunks and are decoded by the loader's host threads
+ * (MRGINGHAM_AMD_FILES_HOST_DECODED); 16-bit ones take the one-image path, or with MRGINGHAM_AMD_FILES_DEEP_CHUNKS the
+ * 16-bit chunks.  MRGINGHAM_AMD_FILES_PNM_DEVICE: runs of consecutive kind-6 slots of a chunk go through
+ * mrgingham_amd_read_pnms_batch on the loader context and are counted under MRGINGHAM_AMD_FILES_DEVICE_LOADED.  P5 files keep
+ * their routes and counters under every flag.  Same outputs.  Any bit above the six flags is MRGINGHAM_AMD_ERR_ARG. */
+#define MRGINGHAM_AMD_FILES_PNM_DEVICE 32
+int mrgingham_amd_find_boards_files_ex5(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* options,
                                         double* h_boards, signed char* h_levels, signed char* h_found_level,
                                         int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie,
                                         double* stats, int nstats, int loader_flags);
@@ -1124,6 +1215,10 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *   "bmp_unpack"          1 (default): mrgingham_amd_read_bmps_batch sends the files' pixel arrays through
  *                         mrgingham_amd_bmp_unpack_batch; 0: its host threads decode every file (the leg to compare
  *                         against).  Same frames and statuses.
+ *   "pnm_chunk_frames"    test hook: the same for mrgingham_amd_read_pnms_batch.
+ *   "pnm_unpack"          1 (default): mrgingham_amd_read_pnms_batch sends the files' rasters through
+ *                         mrgingham_amd_pnm_unpack_batch; 0: its host threads decode every file with
+ *                         mrgingham_amd_read_image (the leg to compare against).  Same frames and statuses.
  *   "tiff_lzw_max_strip"  decoded bytes of an LZW strip, 1 .. 1048576 (the limit of the kernel's table entries; default
  *                         65536): a file with a larger strip keeps the host threads in mrgingham_amd_read_tiffs_batch.  It
  *                         bounds the serial work of one lane: on 64 12 MP files mrgingham_amd_read_tiffs_batch was measured

@@ -42,6 +42,12 @@ class BmpInfo(ctypes.Structure):
         ("payload_offset", ctypes.c_int64), ("lut", ctypes.c_uint8 * 256), ("lut_identity", ctypes.c_int32)]
 
 
+class PnmInfo(ctypes.Structure):
+    """mrgingham_amd_pnm_info"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "bits", "channels", "black_and_white", "magic", "row_bytes")] + [
+        ("payload_offset", ctypes.c_int64)]
+
+
 class Frames(ctypes.Structure):
     """mrgingham_amd_frames"""
     _fields_ = [("frames", ctypes.c_void_p), ("frame_pitch", ctypes.c_int64), ("nframes", ctypes.c_int),
@@ -79,6 +85,8 @@ EXPORTS = [
     "mrgingham_amd_tiff_layout_tiled", "mrgingham_amd_tiff_decode_batch_tiled",
     "mrgingham_amd_bmp_layout", "mrgingham_amd_bmp_unpack_batch", "mrgingham_amd_bmp_unpack_geometry",
     "mrgingham_amd_read_bmps_batch", "mrgingham_amd_find_boards_files_ex4",
+    "mrgingham_amd_pnm_header", "mrgingham_amd_pnm_unpack_batch", "mrgingham_amd_pnm_unpack_geometry",
+    "mrgingham_amd_read_pnms_batch", "mrgingham_amd_find_boards_files_ex5",
 ]
 
 
@@ -221,6 +229,16 @@ def lib():
         L.mrgingham_amd_read_bmps_batch.argtypes = [c_vp, ctypes.POINTER(ctypes.c_char_p), c_int, c_int, c_int, c_vp, ctypes.c_int64,
                                                     c_int, c_int, c_vp]
         L.mrgingham_amd_find_boards_files_ex4.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
+                                                          c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
+    if hasattr(L, "mrgingham_amd_pnm_unpack_batch"):
+        L.mrgingham_amd_pnm_header.argtypes = [c_vp, ctypes.c_size_t, ctypes.POINTER(PnmInfo)]
+        L.mrgingham_amd_pnm_unpack_batch.argtypes = [c_vp, c_vp, ctypes.c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                                     ctypes.c_int64, c_int, c_vp]
+        L.mrgingham_amd_pnm_unpack_geometry.argtypes = [ctypes.POINTER(c_int)] * 2
+        L.mrgingham_amd_pnm_unpack_geometry.restype = None
+        L.mrgingham_amd_read_pnms_batch.argtypes = [c_vp, ctypes.POINTER(ctypes.c_char_p), c_int, c_int, c_int, c_int, c_vp, ctypes.c_int64,
+                                                    c_int, c_int, c_vp]
+        L.mrgingham_amd_find_boards_files_ex5.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
                                                           c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]

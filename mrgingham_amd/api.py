@@ -348,9 +348,48 @@ def bmp_unpack_geometry():
     return a.value, b.value
 
 
+class PnmHeader:
+    """What pnm_header found in a binary Netpbm header: height, width, bits of a sample in the file (1 for P4, 8, 16),
+    channels (samples per pixel, 1 .. 4), black_and_white, magic (the digit: 4 .. 7), row_bytes, payload_offset; depth: of
+    the grey read_image gives (8, or 16 for 16-bit samples)."""
+    FIELDS = ("width", "height", "bits", "channels", "black_and_white", "magic", "row_bytes", "payload_offset")
+
+    def __init__(self, info):
+        for n in self.FIELDS:
+            setattr(self, n, int(getattr(info, n)))
+        self.depth = 16 if self.bits == 16 else 8
+
+    def __repr__(self):
+        return "PnmHeader(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.FIELDS) + ")"
+
+
+def pnm_header(data):
+    """The header of a binary Netpbm file (P4, P5, P7; P6 is not read) held in memory, whole or only its first bytes
+    (mrgingham_amd_pnm_header, which has the subset this library reads; host only): -> PnmHeader; None for what is not such
+    a file, breaks a rule or -- P4, P7 -- holds less than its header promises; PGM_HEADER_CUT where the bytes end inside
+    the header (of a whole file: unreadable; of a file's first bytes: more are needed).  A P5 header gets pgm_header's
+    verdict: its payload is not measured."""
+    buf = bytes(data)
+    info = _lib.PnmInfo()
+    rc = _lib.lib().mrgingham_amd_pnm_header(buf, len(buf), ctypes.byref(info))
+    if rc == PGM_HEADER_CUT:
+        return PGM_HEADER_CUT
+    if rc != 0:
+        return None
+    return PnmHeader(info)
+
+
+def pnm_unpack_geometry():
+    """(lanes_per_workgroup, max_workgroups_per_cu) of the Netpbm unpack launch (mrgingham_amd_pnm_unpack_geometry)."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _lib.lib().mrgingham_amd_pnm_unpack_geometry(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
 def read_image(filename, cli_scaling=False):
     """Decode a binary PGM, non-interlaced PNG, baseline JPEG, strip or tiled TIFF (uncompressed, LZW, PackBits, Deflate; grey or
-    RGB, 8 or 16 bit) or Windows Bitmap (1, 4, 8 bit palette, RLE8, 24 and 32 bit; bmp_layout has the subset) to uint8 [H, W]
+    RGB, 8 or 16 bit), Windows Bitmap (1, 4, 8 bit palette, RLE8, 24 and 32 bit; bmp_layout has the subset) or binary PBM or PAM
+    (pnm_header has the subset; ASCII Netpbm and P6 are not read) to uint8 [H, W]
     with the library's own decoder (host only).
     16-bit files: the high byte (cv::imread(IMREAD_GRAYSCALE)) or, with cli_scaling, the CLI's
     convertTo(255/65535).  None when the file is unreadable, unsupported or malformed."""
@@ -370,7 +409,7 @@ def read_image(filename, cli_scaling=False):
 def probe_image(filename):
     """What read_image would produce for the file, from its header alone (mrgingham_amd_probe_image; host only, nothing is
     decoded): (height, width, bits, kind) with kind 1 binary PGM, 2 PNG, 3 baseline JPEG, 4 TIFF, 5 BMP (always 8 bits: the
-    grey read_image gives; the stream of an RLE8 file is walked); None for a file that is unreadable at header level."""
+    grey read_image gives; the stream of an RLE8 file is walked), 6 binary PBM or PAM (8 bits for PBM); None for a file that is unreadable at header level."""
     w, h, b, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     if _lib.lib().mrgingham_amd_probe_image(os.fsencode(filename), ctypes.byref(w), ctypes.byref(h), ctypes.byref(b),
                                             ctypes.byref(k)) != 0:
@@ -398,8 +437,8 @@ FILES_STATS = ("chunks", "files_device_loader", "files_host_decoded", "files_one
 
 def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_radius=1, refine=True, batch=64, nthreads=0,
                       entropy="host", device=None, progress=None, png="host", deep="one", tiff="host",
-                      tiff_deflate="host", bmp="host"):
-    """A list of image files (binary PGM, PNG, baseline JPEG, TIFF, BMP; any sizes) to boards (mrgingham_amd_find_boards_files): a
+                      tiff_deflate="host", bmp="host", pnm="host"):
+    """A list of image files (binary PGM, PBM and PAM, PNG, baseline JPEG, TIFF, BMP; any sizes) to boards (mrgingham_amd_find_boards_files): a
     loader thread fills chunks of `batch` equally-sized frames on the device -- JPEG through the batch loader,
     entropy="device": Huffman-decoded on the device as well -- while the calling thread preprocesses and searches the
     chunks before them.  Per file the same numbers as read_image + the one-image path with the same options.
@@ -420,7 +459,13 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
     BMP files behave as 8-bit PGM files do: they share chunks and are decoded on the loader's host threads
     (files_host_decoded); bmp="device": the runs of BMP files of a chunk go through the BMP batch loader (Detector.read_bmps:
     the host threads only read the files, the device unpacks the pixel arrays) and count as files_device_loader; same
-    numbers."""
+    numbers.
+    Binary PBM and PAM files behave as PGM files do: 8-bit ones share chunks and are decoded on the loader's host threads
+    (files_host_decoded), 16-bit ones follow `deep`; pnm="device": the runs of such files of a chunk go through the Netpbm
+    batch loader (Detector.read_pnms: the host threads only read the files, the device unpacks the rasters) and count as
+    files_device_loader; same numbers.  PGM files keep their routes."""
+    if pnm not in ("host", "device"):
+        raise ValueError('find_boards_files: pnm is "host" or "device"')
     if bmp not in ("host", "device"):
         raise ValueError('find_boards_files: bmp is "host" or "device"')
     if tiff not in ("host", "device"):
@@ -454,10 +499,10 @@ def find_boards_files(paths, gridn=10, image_pyramid_level=-1, clahe=True, blur_
                 raised.append(e)
     cb = _lib.PROGRESS_F(on_progress)
     arr = (ctypes.c_char_p * max(n, 1))(*names)
-    rc = L.mrgingham_amd_find_boards_files_ex4(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
+    rc = L.mrgingham_amd_find_boards_files_ex5(arr, n, ctypes.byref(o), boards.ctypes.data, levels.ctypes.data, found.ctypes.data,
                                                status.ctypes.data, cb, None, stats.ctypes.data, len(stats),
                                                int(png == "device") | 2 * int(deep == "chunks") | 4 * int(tiff == "device") |
-                                               8 * int(tiff_deflate == "device") | 16 * int(bmp == "device"))
+                                               8 * int(tiff_deflate == "device") | 16 * int(bmp == "device") | 32 * int(pnm == "device"))
     if raised:
         raise raised[0]
     if rc == -1:
@@ -1237,6 +1282,64 @@ class Detector:
         arr = (ctypes.c_char_p * B)(*names)
         t.cuda.current_stream(self.device).synchronize()
         self._check(self.L.mrgingham_amd_read_bmps_batch(self.ctx, arr, B, W, H, frames.data_ptr(), H * W, W, int(nthreads),
+                                                         status.ctypes.data))
+        return frames, status
+
+    def pnm_unpack(self, payload, height, width, bits, channels, black_and_white=False, out=None):
+        """The rasters of binary Netpbm files to grey frames on the device (mrgingham_amd_pnm_unpack_batch), on torch's current
+        stream: payload uint8 [B, P] device tensor, contiguous and 16-byte aligned, P a multiple of 16 and at least
+        row_bytes*height with row_bytes = (width + 7) // 8 for bits 1 and width*channels*bits/8 otherwise -- row f holds file
+        f's raster as it lies behind its header -> uint8 [B, height, width] for bits 1 and 8, uint16 for bits 16.  channels
+        1 .. 4 (1 at bits 1): the grey is the first sample, or the fixed-point BT.601 grey of the first three; a second or
+        fourth sample is ignored.  black_and_white (bits 8, channels 1 or 2): 255 where the first sample is non-zero.
+        `out`: a [B, height, >= width] device tensor of that type (unit column stride, any sample address) to write into;
+        what lies beyond `width` is not touched."""
+        t = self.torch
+        if bits not in (1, 8, 16) or channels not in (1, 2, 3, 4) or (bits == 1 and channels != 1):
+            raise ValueError("pnm_unpack: bits 1 (one channel), 8 or 16 with 1 .. 4 channels")
+        if black_and_white and (bits != 8 or channels > 2):
+            raise ValueError("pnm_unpack: black_and_white with bits 8 and 1 or 2 channels")
+        rowb = (width + 7) // 8 if bits == 1 else width * channels * bits // 8
+        if not (payload.is_cuda and payload.dtype == t.uint8 and payload.dim() == 2 and payload.is_contiguous()
+                and payload.shape[1] % 16 == 0 and payload.shape[1] >= height * rowb and payload.data_ptr() % 16 == 0):
+            raise ValueError("pnm_unpack: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least row_bytes*height")
+        B = payload.shape[0]
+        dtype = t.uint16 if bits == 16 else t.uint8
+        if out is None:
+            out = t.empty((B, height, width), dtype=dtype, device=payload.device)
+        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
+                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
+            raise ValueError("pnm_unpack: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
+        stream = t.cuda.current_stream(payload.device).cuda_stream
+        self._check(self.L.mrgingham_amd_pnm_unpack_batch(
+            self.ctx, payload.data_ptr(), payload.shape[1], B, int(width), int(height), int(bits), int(channels), int(bool(black_and_white)),
+            out.data_ptr(), out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+        return out[:, :, :width]
+
+    def read_pnms(self, paths, nthreads=0):
+        """Binary Netpbm files (P4, P5, P7 in any mix) of one size and output depth straight into device frames
+        (mrgingham_amd_read_pnms_batch): `nthreads` host threads (0: all cores, at most 32) read the rasters from the files
+        into page-locked staging, the device unpacks bits, swaps the bytes of 16-bit samples and reduces colour to grey
+        (option "pnm_unpack" 0: the host threads decode instead).  -> (frames uint8 or uint16 [B,H,W] on the device, status
+        int32 [B] numpy: 0 loaded, -1 unreadable or not Netpbm, -2 another size or depth; failed frames are zero).  Size and
+        depth are those of the first file whose header parses (none does: uint8 frames [B,0,0]).  Synchronous."""
+        t = self.torch
+        names = [os.fsencode(p) for p in paths]
+        B = len(names)
+        status = np.full((B,), -1, dtype=np.int32)
+        H = W = 0
+        bits = 8
+        for name in names:
+            probe = probe_image(name)
+            if probe is not None and probe[3] in (1, 6):
+                H, W, bits = probe[0], probe[1], probe[2]
+                break
+        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
+        if B == 0 or H == 0:
+            return frames, status
+        arr = (ctypes.c_char_p * B)(*names)
+        t.cuda.current_stream(self.device).synchronize()
+        self._check(self.L.mrgingham_amd_read_pnms_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
                                                          status.ctypes.data))
         return frames, status
 

@@ -9,7 +9,7 @@
 //
 // Image decoding: the reference uses cv::imread; OpenCV is not available to this build, so this
 // file reads binary PGM (P5, 8 or 16 bit), non-interlaced PNG (8 or 16 bit; grey, grey+alpha,
-// RGB, RGBA, 8-bit palette) with zlib, baseline JPEG (the luma plane), TIFF and Windows Bitmap (csrc/image_io.h).  Colour is reduced to grey with the fixed-point BT.601
+// RGB, RGBA, 8-bit palette) with zlib, baseline JPEG (the luma plane), TIFF, Windows Bitmap and binary PBM and PAM (csrc/image_io.h).  Colour is reduced to grey with the fixed-point BT.601
 // weights (4899 R + 9617 G + 1868 B + 8192) >> 14 -- OpenCV's own conversion depends on its
 // codec build, so byte-identity with cv::imread on colour files is not claimed.
 //
@@ -50,17 +50,18 @@ struct Options {
     bool tiff_device = false;     // --tiff-lzw device
     bool tiff_deflate_device = false;  // --tiff-deflate device
     bool bmp_device = false;      // --bmp-unpack device
+    bool pnm_device = false;      // --pnm-unpack device
 } opt;
 
 const char* kUsage =
     "Usage: %s [--gridn N] [--noclahe] [--blur radius] [--level l] [--no-refine] [--jobs N]\n"
     "          [--gpus N|all] [--batch N [--jpeg-entropy host|device] [--png-reconstruct host|device]\n"
     "          [--deep-batch one|chunks] [--tiff-lzw host|device [--tiff-deflate host|device]]\n"
-    "          [--bmp-unpack host|device]]\n"
+    "          [--bmp-unpack host|device] [--pnm-unpack host|device]]\n"
     "          [--debug] [--debug-sequence x,y]\n"
     "          imageglobs...\n"
     "\n"
-    "Finds the chessboard in every image (binary PGM, PNG, baseline JPEG, strip or tiled TIFF, BMP) and writes a vnlog table\n"
+    "Finds the chessboard in every image (binary PGM, PBM, PAM, PNG, baseline JPEG, strip or tiled TIFF, BMP) and writes a vnlog table\n"
     "\n"
     "  # filename x y level\n"
     "\n"
@@ -94,6 +95,8 @@ const char* kUsage =
     "  --bmp-unpack host|device   with --batch: where the rows of BMP files are flipped and unpadded, their indices unpacked,\n"
     "                  the palette looked up and colour reduced to grey (default host; device: the --jobs threads only read\n"
     "                  the files)\n"
+    "  --pnm-unpack host|device   with --batch: where the rasters of binary PBM and PAM files are unpacked and colour\n"
+    "                  reduced to grey (default host; device: the --jobs threads only read the files)\n"
     "  --blobs         find a grid of dark circles instead of a chessboard (no --level, no refinement)\n"
     "  --debug         one image only: write the preprocessed image, the level images, the ChESS\n"
     "                  responses and the corner vnlogs to /tmp like the reference does\n"
@@ -288,13 +291,14 @@ int run_batch() {
     o.jpeg_entropy = opt.entropy_device;
     o.device = -1;
     double stats[MRGINGHAM_AMD_FILES_STATS] = {};
-    const int rc = mrgingham_amd_find_boards_files_ex4(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
+    const int rc = mrgingham_amd_find_boards_files_ex5(opt.globbed.gl_pathv, (int)n, &o, B.xy.data(), B.lv.data(), B.found.data(),
                                                        B.status.data(), batch_progress, &B, stats, MRGINGHAM_AMD_FILES_STATS,
                                                        (opt.png_device ? MRGINGHAM_AMD_FILES_PNG_DEVICE : 0) |
                                                            (opt.deep_chunks ? MRGINGHAM_AMD_FILES_DEEP_CHUNKS : 0) |
                                                            (opt.tiff_device ? MRGINGHAM_AMD_FILES_TIFF_DEVICE : 0) |
                                                            (opt.tiff_deflate_device ? MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE : 0) |
-                                                           (opt.bmp_device ? MRGINGHAM_AMD_FILES_BMP_DEVICE : 0));
+                                                           (opt.bmp_device ? MRGINGHAM_AMD_FILES_BMP_DEVICE : 0) |
+                                                           (opt.pnm_device ? MRGINGHAM_AMD_FILES_PNM_DEVICE : 0));
     fflush(stdout);
     if (getenv("MRGINGHAM_AMD_CLI_TIMING"))
         fprintf(stderr, "batch: %.0f chunks; files: %.0f device loader, %.0f host-decoded, %.0f one at a time, %.0f unreadable; "
@@ -323,8 +327,9 @@ int main(int argc, char* argv[]) {
         {"tiff-lzw", required_argument, nullptr, 'Z'},
         {"tiff-deflate", required_argument, nullptr, 'Y'},
         {"bmp-unpack", required_argument, nullptr, 'M'},
+        {"pnm-unpack", required_argument, nullptr, 'U'},
         {nullptr, 0, nullptr, 0}};
-    bool doblobs = false, entropy_given = false, png_given = false, deep_given = false, tiff_given = false, deflate_given = false, bmp_given = false;
+    bool doblobs = false, entropy_given = false, png_given = false, deep_given = false, tiff_given = false, deflate_given = false, bmp_given = false, pnm_given = false;
     int c;
     while ((c = getopt_long(argc, argv, "hj:b:l:", longopts, nullptr)) != -1) {
         switch (c) {
@@ -414,6 +419,15 @@ int main(int argc, char* argv[]) {
                 bmp_given = true;
                 opt.bmp_device = !strcmp(optarg, "device");
                 break;
+            case 'U':
+                if (strcmp(optarg, "host") && strcmp(optarg, "device")) {
+                    fprintf(stderr, "--pnm-unpack takes 'host' or 'device', got '%s'\n", optarg);
+                    fprintf(stderr, kUsage, argv[0]);
+                    return 1;
+                }
+                pnm_given = true;
+                opt.pnm_device = !strcmp(optarg, "device");
+                break;
             default:
                 fprintf(stderr, "Unknown option\n");
                 fprintf(stderr, kUsage, argv[0]);
@@ -442,6 +456,10 @@ int main(int argc, char* argv[]) {
     }
     if (bmp_given && !opt.batch) {
         fprintf(stderr, "--bmp-unpack is only accepted with --batch\n");
+        return 1;
+    }
+    if (pnm_given && !opt.batch) {
+        fprintf(stderr, "--pnm-unpack is only accepted with --batch\n");
         return 1;
     }
     if (opt.tiff_deflate_device && !opt.tiff_device) {

@@ -623,6 +623,16 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
         ctx->bmp_unpack = value;
         return 0;
     }
+    if (!strcmp(name, "pnm_chunk_frames")) {
+        if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "pnm_chunk_frames: 0 (by the scratch budget) or a file count");
+        ctx->pnm_chunk_frames = value;
+        return 0;
+    }
+    if (!strcmp(name, "pnm_unpack")) {
+        if (value != 0 && value != 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "pnm_unpack: 0 (host threads decode) or 1 (the device unpacks)");
+        ctx->pnm_unpack = value;
+        return 0;
+    }
     if (!strcmp(name, "tiff_lzw_max_strip")) {
         if (value < 1 || value > (1 << 20)) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "tiff_lzw_max_strip: decoded bytes per strip, 1 .. 1048576");
         ctx->tiff_lzw_max_strip = value;

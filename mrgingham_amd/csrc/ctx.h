@@ -313,6 +313,11 @@ struct mrgingham_amd_ctx {
     // unpacks the pixel arrays; 0: the host threads decode every file)
     int bmp_chunk_frames = 0;
     int bmp_unpack = 1;
+    // mrgingham_amd_read_pnms_batch (pnm_unpack.hip): on loader_slot within jpeg_coef_budget as well (staging: the files'
+    // rasters); options "pnm_chunk_frames" (test hook, as above) and "pnm_unpack" (1: the device unpacks the rasters; 0: the
+    // host threads decode every file)
+    int pnm_chunk_frames = 0;
+    int pnm_unpack = 1;
     // mrgingham_amd_read_tiffs_batch / _tiff_decode_batch (tiff_decode.hip): the loader runs on loader_slot within
     // jpeg_coef_budget too (staging: the files as they lie on disk, their strip tables); tiff_raw: the decoded strips of an
     // LZW launch, rowbytes x height per frame; tiff_table: 4096 dwords per lane in flight, interleaved by lane;

@@ -1,5 +1,5 @@
 // Host side of libmrgingham_amd.so, a list of image files to boards (mrgingham_amd_find_boards_files): the schedule that
-// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip, png_recon.hip, pgm_unpack.hip, bmp_unpack.hip, tiff_decode.hip), of the preprocessing (preprocess.hip,
+// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip, png_recon.hip, pgm_unpack.hip, bmp_unpack.hip, pnm_unpack.hip, tiff_decode.hip), of the preprocessing (preprocess.hip,
 // preprocess16_batch.hip) and of the board
 // detector (boards.hip) fed from a list of several sizes and formats.  No kernel of its own.
 //
@@ -11,7 +11,8 @@
 //   JPEG runs -> read_jpegs_batch            collect chunk c - k, scatter its results, advance the final prefix
 //   (PNG runs -> read_pngs_batch where the caller set MRGINGHAM_AMD_FILES_PNG_DEVICE,
 //    TIFF runs -> read_tiffs_batch where the caller set MRGINGHAM_AMD_FILES_TIFF_DEVICE,
-//    BMP runs -> read_bmps_batch where the caller set MRGINGHAM_AMD_FILES_BMP_DEVICE)
+//    BMP runs -> read_bmps_batch where the caller set MRGINGHAM_AMD_FILES_BMP_DEVICE,
+//    PBM / PAM runs -> read_pnms_batch where the caller set MRGINGHAM_AMD_FILES_PNM_DEVICE)
 //   (16-bit files, where the caller set MRGINGHAM_AMD_FILES_DEEP_CHUNKS, in chunks of their own: PGM runs ->
 //    read_pgms_batch, PNG as above, as uint16 frames; the detector side runs preprocess16_batch on such a chunk)
 //   chunk c loaded                           (one-image files are processed when the prefix reaches them)
@@ -45,7 +46,8 @@ struct FileInfo {
     bool pgm_device = false;               // a 16-bit PGM that goes through read_pgms_batch (MRGINGHAM_AMD_FILES_DEEP_CHUNKS)
     bool tiff_device = false;              // a TIFF that goes through read_tiffs_batch (MRGINGHAM_AMD_FILES_TIFF_DEVICE)
     bool bmp_device = false;               // a BMP that goes through read_bmps_batch (MRGINGHAM_AMD_FILES_BMP_DEVICE)
-    bool batch_loader() const { return kind == 3 || png_device || pgm_device || tiff_device || bmp_device; }
+    bool pnm_device = false;               // a P4 / P7 file that goes through read_pnms_batch (MRGINGHAM_AMD_FILES_PNM_DEVICE)
+    bool batch_loader() const { return kind == 3 || png_device || pgm_device || tiff_device || bmp_device || pnm_device; }
 };
 
 struct Chunk {
@@ -140,7 +142,7 @@ int load_chunk(Run& R, int c) {
     long nbatch_ok = 0;
     auto route = [&](int k) {
         const FileInfo& f = R.info[(size_t)ch.files[(size_t)k]];
-        return f.kind == 3 ? 1 : f.png_device ? 2 : f.pgm_device ? 3 : f.tiff_device ? 4 : f.bmp_device ? 5 : 0;
+        return f.kind == 3 ? 1 : f.png_device ? 2 : f.pgm_device ? 3 : f.tiff_device ? 4 : f.bmp_device ? 5 : f.pnm_device ? 6 : 0;
     };
     for (int k = 0; k < n;) {
         const int via = route(k);
@@ -156,7 +158,8 @@ int load_chunk(Run& R, int c) {
                        : via == 2 ? mrgingham_amd_read_pngs_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
                        : via == 3 ? mrgingham_amd_read_pgms_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
                        : via == 4 ? mrgingham_amd_read_tiffs_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
-                                  : mrgingham_amd_read_bmps_batch(ctx, run.data(), j - k, ch.w, ch.h, frames, fpitch, ch.w, R.nthreads, st);
+                       : via == 5 ? mrgingham_amd_read_bmps_batch(ctx, run.data(), j - k, ch.w, ch.h, frames, fpitch, ch.w, R.nthreads, st)
+                                  : mrgingham_amd_read_pnms_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st);
         if (rc) return rc;
         for (int i = k; i < j; ++i) {
             if (S.load_status[(size_t)i] == 0) ++nbatch_ok;
@@ -261,8 +264,19 @@ int mrgingham_amd_find_boards_files_ex4(const char* const* filenames, int nfiles
                                         double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
                                         void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
                                         int loader_flags) {
+    if (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE |
+                         MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE | MRGINGHAM_AMD_FILES_BMP_DEVICE))
+        return MRGINGHAM_AMD_ERR_ARG;
+    return mrgingham_amd_find_boards_files_ex5(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
+                                               nstats, loader_flags);
+}
+
+int mrgingham_amd_find_boards_files_ex5(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
+                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
+                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
+                                        int loader_flags) {
     constexpr int kFlags = MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE |
-                           MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE | MRGINGHAM_AMD_FILES_BMP_DEVICE;
+                           MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE | MRGINGHAM_AMD_FILES_BMP_DEVICE | MRGINGHAM_AMD_FILES_PNM_DEVICE;
     // (Deflate strips on the device are a part of the TIFF device route, not a route of their own)
     if ((loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE) && !(loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEVICE)) return MRGINGHAM_AMD_ERR_ARG;
     if (nfiles < 0 || (loader_flags & ~kFlags) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
@@ -307,6 +321,7 @@ int mrgingham_amd_find_boards_files_ex4(const char* const* filenames, int nfiles
             f.pgm_device = deep_chunks && f.kind == 1 && f.bits == 16;
             f.tiff_device = (loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEVICE) && f.kind == 4 && (f.bits == 8 || deep_chunks);
             f.bmp_device = (loader_flags & MRGINGHAM_AMD_FILES_BMP_DEVICE) && f.kind == 5;
+            f.pnm_device = (loader_flags & MRGINGHAM_AMD_FILES_PNM_DEVICE) && f.kind == 6 && (f.bits == 8 || deep_chunks);
         });
     }
     size_t max_frame = 0, max_host_frame = 0;

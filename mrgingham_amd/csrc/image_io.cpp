@@ -3,6 +3,7 @@
 #include "bmp_pixels.h"
 #include "jpeg.h"
 #include "png_filter.h"
+#include "pnm_pixels.h"
 #include "tiff_inflate.h"
 #include "tiff_lzw.h"
 #include "../../include/mrgingham_amd.h"
@@ -623,6 +624,164 @@ static bool decode_bmp(const std::vector<uint8_t>& b, Image& im) {
     return true;
 }
 
+// ---- binary Netpbm beyond P5 (image_io.h: pnm_header; include/mrgingham_amd.h has the subset)
+
+// P7: the lines behind the magic.  A line ends at '\n'; blanks, tabs and a '\r' may surround its words.
+static int pam_header(const uint8_t* b, size_t have, mrgingham_amd_pnm_info& pi) {
+    auto blank = [](uint8_t c) { return c == ' ' || c == '\t' || c == '\r'; };
+    size_t p = 2;
+    long field[4] = {-1, -1, -1, -1};  // WIDTH, HEIGHT, DEPTH, MAXVAL
+    static const char* const kField[4] = {"WIDTH", "HEIGHT", "DEPTH", "MAXVAL"};
+    bool first_line = true, tupltype_seen = false, bw = false;
+    for (;;) {
+        size_t e = p;
+        while (e < have && b[e] != '\n') ++e;
+        if (e >= have) return kPgmHeaderCut;  // (the line may go on)
+        size_t s = p, t = e;
+        while (s < t && blank(b[s])) ++s;
+        while (t > s && blank(b[t - 1])) --t;
+        p = e + 1;
+        if (first_line) {  // nothing but the magic on line 1
+            if (s != t) return -1;
+            first_line = false;
+            continue;
+        }
+        if (s == t || b[s] == '#') continue;
+        size_t k = s;
+        while (k < t && !blank(b[k])) ++k;
+        const size_t nword = k - s;
+        auto word = [&](const char* name) { return nword == strlen(name) && !memcmp(b + s, name, nword); };
+        while (k < t && blank(b[k])) ++k;  // the value: b[k, t)
+        if (word("ENDHDR")) {
+            if (k != t) return -1;
+            break;
+        }
+        if (word("TUPLTYPE")) {
+            if (!tupltype_seen) bw = t - k >= 13 && !memcmp(b + k, "BLACKANDWHITE", 13);
+            tupltype_seen = true;
+            continue;
+        }
+        int which = -1;
+        for (int i = 0; i < 4; ++i)
+            if (word(kField[i])) which = i;
+        if (which < 0 || field[which] >= 0 || k == t) return -1;
+        long x = 0;
+        for (; k < t; ++k) {
+            if (b[k] < '0' || b[k] > '9') return -1;
+            x = x * 10 + (b[k] - '0');
+            if (x > 1 << 30) return -1;
+        }
+        field[which] = x;
+    }
+    for (int i = 0; i < 4; ++i)
+        if (field[i] < 0) return -1;
+    if (field[0] < 1 || field[0] > kMaxSide || field[1] < 1 || field[1] > kMaxSide || field[2] < 1 || field[2] > 4 || field[3] < 1 ||
+        field[3] > 65535)
+        return -1;
+    if (bw && (field[2] > 2 || field[3] != 1)) return -1;
+    pi.width = (int32_t)field[0]; pi.height = (int32_t)field[1]; pi.channels = (int32_t)field[2];
+    pi.bits = field[3] < 256 ? 8 : 16;
+    pi.black_and_white = bw ? 1 : 0;
+    pi.payload_offset = (int64_t)p;
+    return 0;
+}
+
+int pnm_header(const uint8_t* b, size_t have, size_t file_size, mrgingham_amd_pnm_info* info_out) {
+    // (P6 stays unreadable: tests/test_pgm_header.py pins such a file, as tests/test_image_io.py pins P2; PAM depth 3 carries R G B)
+    if (!b || have > file_size || have < 2 || b[0] != 'P' || (b[1] != '4' && b[1] != '5' && b[1] != '7')) return -1;
+    mrgingham_amd_pnm_info pi;
+    memset(&pi, 0, sizeof(pi));
+    pi.magic = b[1] - '0';
+    pi.channels = 1;
+    if (pi.magic == 5) {  // pgm_header's verdicts and outputs: the payload is the caller's to measure
+        size_t off = 0;
+        const int rc = pgm_header(b, have, &pi.width, &pi.height, &pi.bits, &off);
+        if (rc) return rc;
+        pi.payload_offset = (int64_t)off;
+        pi.row_bytes = pi.width * (pi.bits / 8);
+        if (info_out) *info_out = pi;
+        return 0;
+    }
+    if (pi.magic == 7) {
+        const int rc = pam_header(b, have, pi);
+        if (rc) return rc;
+    } else {
+        // P4: two numbers; white space and comments as in pgm_header
+        constexpr int nv = 2;
+        size_t p = 2;
+        long v[2] = {0, 0};
+        for (int k = 0; k < nv; ++k) {
+            for (;;) {
+                while (p < have && (b[p] == ' ' || b[p] == '\t' || b[p] == '\n' || b[p] == '\r')) ++p;
+                if (p < have && b[p] == '#') { while (p < have && b[p] != '\n') ++p; continue; }
+                break;
+            }
+            if (p >= have) return kPgmHeaderCut;
+            if (b[p] < '0' || b[p] > '9') return -1;
+            long x = 0;
+            while (p < have && b[p] >= '0' && b[p] <= '9') { x = x * 10 + (b[p] - '0'); if (x > 1 << 30) return -1; ++p; }
+            v[k] = x;
+        }
+        if (p >= have) return kPgmHeaderCut;  // (the last number may go on, and the single white-space byte after it is part of the header)
+        if (b[p] != ' ' && b[p] != '\t' && b[p] != '\n' && b[p] != '\r') return -1;
+        ++p;
+        if (v[0] < 1 || v[1] < 1 || v[0] > kMaxSide || v[1] > kMaxSide) return -1;
+        pi.width = (int32_t)v[0]; pi.height = (int32_t)v[1];
+        pi.bits = 1;
+        pi.channels = 1;
+        pi.payload_offset = (int64_t)p;
+    }
+    const uint64_t rowb = pi.bits == 1 ? ((uint64_t)pi.width + 7) / 8 : (uint64_t)pi.width * (uint64_t)pi.channels * (uint64_t)(pi.bits / 8);
+    pi.row_bytes = (int32_t)rowb;  // (at most 32767 * 4 * 2)
+    if ((uint64_t)pi.payload_offset > file_size || rowb * (uint64_t)pi.height > file_size - (uint64_t)pi.payload_offset) return -1;
+    if (info_out) *info_out = pi;
+    return 0;
+}
+
+template <int BITS, int CH, bool BW>
+static void pnm_rows(const uint8_t* base, long long limit, const mrgingham_amd_pnm_info& pi, Image& im) {
+    constexpr int NP = PnmSpan<BITS, CH>::kPixels;
+    const int w = pi.width;
+    for (int y = 0; y < pi.height; ++y) {
+        const long long row_off = (long long)y * pi.row_bytes;
+        for (int x0 = 0; x0 < w; x0 += NP) {
+            const int k = w - x0 < NP ? w - x0 : NP;
+            uint32_t d[4];
+            pnm_pixels<BITS, CH, BW>(base, limit, row_off, x0, k, d);
+            if constexpr (BITS == 16) {
+                uint16_t* o = &im.px16[(size_t)w * y + x0];
+                for (int p = 0; p < k; ++p) o[p] = (uint16_t)(d[p >> 1] >> (16 * (p & 1)));
+            } else {
+                uint8_t* o = &im.px8[(size_t)w * y + x0];
+                for (int p = 0; p < k; ++p) o[p] = (uint8_t)(d[p >> 2] >> (8 * (p & 3)));
+            }
+        }
+    }
+}
+
+// P4, P7 (P5 keeps decode_pgm): every word of every row through pnm_pixels.h, the text the device runs
+static bool decode_pnm(const std::vector<uint8_t>& b, Image& im) {
+    mrgingham_amd_pnm_info pi;
+    if (pnm_header(b.data(), b.size(), b.size(), &pi) != 0) return false;
+    const size_t n = (size_t)pi.width * pi.height;
+    im.w = pi.width; im.h = pi.height; im.depth = pi.bits == 16 ? 16 : 8;
+    if (pi.bits == 16) { about_to_hold(im, 0, n); im.px16.resize(n); }
+    else { about_to_hold(im, n, 0); im.px8.resize(n); }
+    const uint8_t* base = b.data() + pi.payload_offset;
+    const long long limit = (long long)(b.size() - (size_t)pi.payload_offset);
+#define MRG_PNM_ROWS(B, C, W)                                                   \
+    if (pi.bits == B && pi.channels == C && (pi.black_and_white != 0) == W) {   \
+        pnm_rows<B, C, W>(base, limit, pi, im);                                 \
+        return true;                                                            \
+    }
+    MRG_PNM_ROWS(1, 1, false)
+    MRG_PNM_ROWS(8, 1, false) MRG_PNM_ROWS(8, 2, false) MRG_PNM_ROWS(8, 3, false) MRG_PNM_ROWS(8, 4, false)
+    MRG_PNM_ROWS(16, 1, false) MRG_PNM_ROWS(16, 2, false) MRG_PNM_ROWS(16, 3, false) MRG_PNM_ROWS(16, 4, false)
+    MRG_PNM_ROWS(8, 1, true) MRG_PNM_ROWS(8, 2, true)
+#undef MRG_PNM_ROWS
+    return false;
+}
+
 // 8-bit binary PGM, the format a calibration run usually feeds the tool: the pixels go from the file straight into
 // px8 -- no copy of the whole file in between (a 12 MB image: one pass over memory less per image).  Returns 1 = done,
 // 0 = not such a file (the general path decides), -1 = such a file, but broken.
@@ -655,6 +814,7 @@ bool read_image(const char* path, Image& im) {
         std::vector<uint8_t>& b = im.file;
         if (!read_file(path, b) || b.size() < 8) return false;
         if (b[0] == 'P' && b[1] == '5') return decode_pgm(b, im);
+        if (b[0] == 'P' && (b[1] == '4' || b[1] == '7')) return decode_pnm(b, im);
         if (b[0] == 0x89 && b[1] == 'P') return decode_png(b, im);
         if (b[0] == 0xFF && b[1] == 0xD8) return decode_jpeg(b, im);
         if ((b[0] == 'I' && b[1] == 'I') || (b[0] == 'M' && b[1] == 'M')) return decode_tiff(b, im);
@@ -665,8 +825,8 @@ bool read_image(const char* path, Image& im) {
     }
 }
 
-// The header checks of decode_pgm / read_pgm8_direct, decode_png, decode_jpeg, decode_tiff and decode_bmp without the decoding.  PGM,
-// PNG and uncompressed BMP keep what they need in front: only the first kProbeBytes of such a file are read (a PGM whose comments push the
+// The header checks of decode_pgm / read_pgm8_direct, decode_pnm, decode_png, decode_jpeg, decode_tiff and decode_bmp without the decoding.  PGM,
+// the other binary Netpbm files, PNG and uncompressed BMP keep what they need in front: only the first kProbeBytes of such a file are read (a PGM whose comments push the
 // header beyond them is read whole); a JPEG is read whole, its tables may lie anywhere before SOS, and so is a TIFF.
 bool probe_image(const char* path, int* width, int* height, int* bits, int* kind) {
     constexpr size_t kProbeBytes = 4096;
@@ -696,6 +856,16 @@ bool probe_image(const char* path, int* width, int* height, int* bits, int* kind
                 if (ok) rc = pgm_header(b.data(), b.size(), &w, &h, &d, &p);
             }
             ok = ok && rc == 0 && (size_t)size - p >= (size_t)w * h * (d / 8);
+        } else if (ok && b[0] == 'P' && (b[1] == '4' || b[1] == '7')) {
+            k = 6;
+            mrgingham_amd_pnm_info pi{};
+            int rc = pnm_header(b.data(), b.size(), (size_t)size, &pi);
+            if (rc == kPgmHeaderCut && b.size() < (size_t)size) {  // the header may go on
+                ok = rest();
+                if (ok) rc = pnm_header(b.data(), b.size(), (size_t)size, &pi);
+            }
+            ok = ok && rc == 0;
+            w = pi.width; h = pi.height; d = pi.bits == 16 ? 16 : 8;
         } else if (ok && b[0] == 0x89 && b[1] == 'P') {
             k = 2;
             static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
@@ -802,6 +972,10 @@ void to_8bit(const Image& im, std::vector<uint8_t>& out) {
 
 extern "C" int mrgingham_amd_pgm_header(const uint8_t* data, size_t nbytes, int* width, int* height, int* bits, size_t* payload_offset) {
     return mrg::pgm_header(data, nbytes, width, height, bits, payload_offset);
+}
+
+extern "C" int mrgingham_amd_pnm_header(const uint8_t* data, size_t nbytes, mrgingham_amd_pnm_info* info) {
+    return mrg::pnm_header(data, nbytes, nbytes, info);
 }
 
 extern "C" int mrgingham_amd_bmp_layout(const uint8_t* data, size_t nbytes, mrgingham_amd_bmp_info* info) {

@@ -4,7 +4,8 @@
 // JPEG (jpeg.h: sequential Huffman, one scan; the luma plane, byte for byte what libjpeg's default
 // decoder gives cv::imread(IMREAD_GRAYSCALE); progressive, arithmetic and multi-scan files are
 // unreadable), strip or tiled TIFF (tiff_layout and tiff_layout_tiled below have the subset; LZW through tiff_lzw.h) and
-// Windows Bitmap (bmp_layout below; the pixels through bmp_pixels.h).  PNG, TIFF and BMP
+// Windows Bitmap (bmp_layout below; the pixels through bmp_pixels.h); binary PBM and PAM (pnm_header below; the pixels
+// through pnm_pixels.h).  PNG, TIFF, BMP and Netpbm
 // colour is reduced to grey with the fixed-point BT.601 weights
 // (4899 R + 9617 G + 1868 B + 8192) >> 14; byte-identity with cv::imread on colour files is not
 // claimed (its conversion depends on the codec build).
@@ -31,7 +32,7 @@ struct Image {
 bool read_image(const char* path, Image& im);
 // What read_image would produce, from the file's header alone (nothing is decoded): width, height, bits (8 or 16) and
 // kind -- 1 binary PGM, 2 PNG, 3 baseline JPEG (jpeg_coefficients' header parse, up to and including SOS), 4 TIFF
-// (tiff_layout_tiled: the IFD and the strip or tile table), 5 BMP (bmp_layout).  false for
+// (tiff_layout_tiled: the IFD and the strip or tile table), 5 BMP (bmp_layout), 6 binary PBM / PAM (pnm_header).  false for
 // whatever read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut
 // short or breaks a rule (sides above 32767 included), a PGM shorter than its header promises.  A file that passes may
 // still fail to decode.  Never throws, never sizes anything from an unchecked field.
@@ -77,6 +78,11 @@ int tiff_layout_tiled(const uint8_t* data, size_t nbytes, int64_t lzw_max_strip,
 // been walked, with fewer bytes only its header is judged; -1 unreadable.  Never throws, allocates nothing.
 constexpr int kBmpNotTaken = -3;
 int bmp_layout(const uint8_t* data, size_t have, size_t file_size, mrgingham_amd_bmp_info* info);
+// The one parser of a binary Netpbm header (P4, P5, P7; P6 stays unreadable), behind read_image, probe_image and the batch loader
+// (mrgingham_amd_pnm_header has the contract and the subset).  `data` holds the file's first `have` bytes, file_size is the
+// size of the whole file, against which the raster of P4 / P7 is checked; P5 gets pgm_header's verdicts and outputs.
+// 0; -1 unreadable; kPgmHeaderCut: the bytes end inside the header.  Never throws, allocates nothing.
+int pnm_header(const uint8_t* data, size_t have, size_t file_size, mrgingham_amd_pnm_info* info);
 // The IHDR fields of a PNG file as they stand, nothing judged (a routing hint: png_scanlines decides what is readable):
 // returns the colour type byte, -1 for a file that does not begin with a PNG signature and a whole IHDR.
 int png_header(const char* path, int* width, int* height, int* bits);
