@@ -82,7 +82,11 @@ extern "C" {
  *      _pnm_unpack_geometry, _read_pnms_batch (colour to grey, big-endian pairs and packed bits on the device); options
  *      "pnm_chunk_frames", "pnm_unpack"; mrgingham_amd_find_boards_files_ex5 (loader flag MRGINGHAM_AMD_FILES_PNM_DEVICE,
  *      which _ex4 goes on refusing).  mrgingham_amd_pgm_header goes on refusing every magic but P5; ASCII Netpbm (P1, P2, P3)
- *      stays unreadable, and so does P6.  The device route of the file list is off unless asked for. */
+ *      stays unreadable, and so does P6.  The device route of the file list is off unless asked for.
+ *      Later, additive (the version stays 4): mrgingham_amd_raw_row_bytes, _raw_unpack_image, _raw_unpack_batch,
+ *      _raw_unpack_geometry and the MRGINGHAM_AMD_RAW_* formats (packed 10 / 12 / 14-bit camera frames -- Mono10p, Mono12p,
+ *      Mono14p, Mono10Packed, Mono12Packed -- to uint16 frames, on the host and on the device).  No earlier call, option
+ *      or default changes; no file reader takes such frames (a headerless frame carries no size). */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -695,6 +699,52 @@ void mrgingham_amd_pnm_unpack_geometry(int* lanes_per_workgroup, int* max_workgr
  * same 1 GiB (options "pnm_chunk_frames", "pnm_unpack"). */
 int mrgingham_amd_read_pnms_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
                                   int bits, void* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status);
+
+/* Packed camera frames: 10, 12 or 14-bit samples as machine-vision cameras and frame grabbers deliver them.  A frame is
+ * `height` rows; row y begins at byte y * row_bytes of the frame's payload; nothing is shared between rows, and row_bytes
+ * may exceed the minimum (row padding).  The layouts, which govern (the names are the common ones):
+ *   MRGINGHAM_AMD_RAW_P10 / _P12 / _P14 (GenICam Mono10p / Mono12p / Mono14p), N = 10 / 12 / 14: a row is one bit stream,
+ *     least significant bit first: stream bit b is bit b % 8 of byte b / 8; sample x is the stream bits [x*N, (x+1)*N),
+ *     least significant first.  Minimum row_bytes: ceil(width*N/8).
+ *   MRGINGHAM_AMD_RAW_GEV10 / _GEV12 (GigE Vision Mono10Packed / Mono12Packed), L = 2 / 4: pixels 2g, 2g+1 are the bytes
+ *     3g .. 3g+2: p0 = byte0 << L | (byte1 & (2^L - 1)), p1 = byte2 << L | ((byte1 >> 4) & (2^L - 1)); with L = 2 the
+ *     bits 2, 3, 6, 7 of byte1 are ignored.  Minimum row_bytes: 3*ceil(width/2).
+ * The output is the sample as it is, 0 .. 2^N - 1, in a native uint16_t -- not left-justified (mrgingham_amd_preprocess16_batch
+ * normalises by min/max).  Every bit pattern is a valid frame; padding bits and bytes are not looked at.  Rows that begin
+ * inside a byte (one bit stream across a whole frame), Bayer mosaics and MSB-first streams are not read. */
+#define MRGINGHAM_AMD_RAW_P10 0
+#define MRGINGHAM_AMD_RAW_P12 1
+#define MRGINGHAM_AMD_RAW_P14 2
+#define MRGINGHAM_AMD_RAW_GEV10 3
+#define MRGINGHAM_AMD_RAW_GEV12 4
+
+/* the minimum row_bytes of the table above; -1 for a format that is none of the five or a width outside 1 .. 32767 */
+int64_t mrgingham_amd_raw_row_bytes(int width, int format);
+
+/* One packed frame to uint16 samples on the HOST (no device needed; the text the kernel runs, csrc/raw_pixels.h): row y of
+ * `out` begins at out + y*stride (ELEMENTS, stride >= width); only the width x height samples are written.  `payload` may
+ * sit at any address; no byte at or beyond payload + nbytes is read.  MRGINGHAM_AMD_ERR_ARG, with nothing written, for a
+ * NULL pointer, a bad format, sides outside 1 .. 32767, row_bytes below the minimum, stride < width or
+ * nbytes < (height-1)*row_bytes + minimum.  This is the route a caller without the device call has; it is not a fallback
+ * of mrgingham_amd_raw_unpack_batch. */
+int mrgingham_amd_raw_unpack_image(const uint8_t* payload, size_t nbytes, int width, int height, int64_t row_bytes, int format,
+                                   uint16_t* out, int stride);
+
+/* Packed frames to uint16 frames on the device: frame f's payload at d_payload + f*payload_pitch (BYTES; d_payload 16-byte
+ * aligned, payload_pitch a multiple of 16 and >= (height-1)*row_bytes + minimum; row_bytes at least the minimum, sides
+ * 1 .. 32767).  d_out, frame_pitch and stride as for mrgingham_amd_pgm_unpack_batch: native uint16_t frames, frame f row y
+ * at d_out + f*frame_pitch + y*stride, ELEMENTS, d_out at any even address; only the width x height samples are written,
+ * what lies between width and stride stays untouched.  Input and output must not overlap.  One streaming launch sized to
+ * the device: a lane produces one 16-byte word (8 samples) of a destination row per step from their 10 / 12 / 14 source
+ * bytes, read as the aligned dwords that cover them, each once, and none beyond d_payload + nframes*payload_pitch.
+ * Asynchronous on `stream` (NULL = default); allocates nothing.  Every violation is MRGINGHAM_AMD_ERR_ARG with nothing
+ * written. */
+int mrgingham_amd_raw_unpack_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_payload, int64_t payload_pitch, int nframes,
+                                   int width, int height, int64_t row_bytes, int format, uint16_t* d_out, int64_t frame_pitch,
+                                   int stride, void* stream);
+
+/* the schedule of that launch, as mrgingham_amd_pnm_unpack_geometry's */
+void mrgingham_amd_raw_unpack_geometry(int* lanes_per_workgroup, int* max_workgroups_per_cu);
 
 /* TIFF, host half (host only, no device needed): the one parser of a TIFF's first image file directory, behind
  * mrgingham_amd_read_image, _probe_image and _read_tiffs_batch.  `data` is a whole file held in memory.  The subset is

@@ -87,6 +87,8 @@ EXPORTS = [
     "mrgingham_amd_read_bmps_batch", "mrgingham_amd_find_boards_files_ex4",
     "mrgingham_amd_pnm_header", "mrgingham_amd_pnm_unpack_batch", "mrgingham_amd_pnm_unpack_geometry",
     "mrgingham_amd_read_pnms_batch", "mrgingham_amd_find_boards_files_ex5",
+    "mrgingham_amd_raw_row_bytes", "mrgingham_amd_raw_unpack_image", "mrgingham_amd_raw_unpack_batch",
+    "mrgingham_amd_raw_unpack_geometry",
 ]
 
 
@@ -240,6 +242,14 @@ def lib():
                                                     c_int, c_int, c_vp]
         L.mrgingham_amd_find_boards_files_ex5.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(FilesOptions), c_vp,
                                                           c_vp, c_vp, c_vp, PROGRESS_F, c_vp, c_vp, c_int, c_int]
+    if hasattr(L, "mrgingham_amd_raw_unpack_batch"):
+        L.mrgingham_amd_raw_row_bytes.argtypes = [c_int, c_int]
+        L.mrgingham_amd_raw_row_bytes.restype = ctypes.c_int64
+        L.mrgingham_amd_raw_unpack_image.argtypes = [c_vp, ctypes.c_size_t, c_int, c_int, ctypes.c_int64, c_int, c_vp, c_int]
+        L.mrgingham_amd_raw_unpack_batch.argtypes = [c_vp, c_vp, ctypes.c_int64, c_int, c_int, c_int, ctypes.c_int64, c_int, c_vp,
+                                                     ctypes.c_int64, c_int, c_vp]
+        L.mrgingham_amd_raw_unpack_geometry.argtypes = [ctypes.POINTER(c_int)] * 2
+        L.mrgingham_amd_raw_unpack_geometry.restype = None
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]
     L.mrgingham_amd_host_alloc.argtypes = [ctypes.c_size_t]

@@ -386,6 +386,49 @@ def pnm_unpack_geometry():
     return a.value, b.value
 
 
+# the packed camera formats (MRGINGHAM_AMD_RAW_*): GenICam Mono10p / Mono12p / Mono14p, GigE Vision Mono10Packed / Mono12Packed
+RAW_FORMATS = {"p10": 0, "p12": 1, "p14": 2, "gev10": 3, "gev12": 4}
+
+
+def _raw_format(fmt, who):
+    if not isinstance(fmt, str) or fmt not in RAW_FORMATS:
+        raise ValueError(f'{who}: fmt is one of "p10", "p12", "p14", "gev10", "gev12"')
+    return RAW_FORMATS[fmt]
+
+
+def raw_row_bytes(width, fmt):
+    """The fewest bytes that hold a row of `width` packed samples (mrgingham_amd_raw_row_bytes): ceil(width*N/8) for the
+    bit streams "p10", "p12", "p14", 3*ceil(width/2) for the pixel pairs "gev10", "gev12".  width 1 .. 32767."""
+    n = _lib.lib().mrgingham_amd_raw_row_bytes(int(width), _raw_format(fmt, "raw_row_bytes"))
+    if n < 0:
+        raise ValueError("raw_row_bytes: width 1 .. 32767")
+    return int(n)
+
+
+def raw_unpack(data, height, width, fmt, row_bytes=None):
+    """One packed 10 / 12 / 14-bit camera frame to np.uint16 [height, width] on the host (mrgingham_amd_raw_unpack_image,
+    no device needed): data is bytes or a uint8 array, row y begins at byte y*row_bytes (None: raw_row_bytes(width, fmt)),
+    the values are the samples as they are, 0 .. 2^N - 1.  Detector.raw_unpack is the device's route for batches."""
+    f = _raw_format(fmt, "raw_unpack")
+    buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data)
+    if buf.dtype != np.uint8:
+        raise ValueError("raw_unpack: data is bytes or a uint8 array")
+    rowb = raw_row_bytes(width, fmt) if row_bytes is None else int(row_bytes)
+    if not (1 <= height <= 32767):
+        raise ValueError("raw_unpack: height 1 .. 32767")
+    out = np.empty((height, width), dtype=np.uint16)
+    if _lib.lib().mrgingham_amd_raw_unpack_image(buf.ctypes.data, buf.size, int(width), int(height), rowb, f, out.ctypes.data, int(width)) != 0:
+        raise ValueError("raw_unpack: row_bytes is at least raw_row_bytes(width, fmt) and data holds (height-1)*row_bytes + raw_row_bytes(width, fmt) bytes")
+    return out
+
+
+def raw_unpack_geometry():
+    """(lanes_per_workgroup, max_workgroups_per_cu) of the packed-frame unpack launch (mrgingham_amd_raw_unpack_geometry)."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _lib.lib().mrgingham_amd_raw_unpack_geometry(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
 def read_image(filename, cli_scaling=False):
     """Decode a binary PGM, non-interlaced PNG, baseline JPEG, strip or tiled TIFF (uncompressed, LZW, PackBits, Deflate; grey or
     RGB, 8 or 16 bit), Windows Bitmap (1, 4, 8 bit palette, RLE8, 24 and 32 bit; bmp_layout has the subset) or binary PBM or PAM
@@ -1314,6 +1357,39 @@ class Detector:
         self._check(self.L.mrgingham_amd_pnm_unpack_batch(
             self.ctx, payload.data_ptr(), payload.shape[1], B, int(width), int(height), int(bits), int(channels), int(bool(black_and_white)),
             out.data_ptr(), out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+        return out[:, :, :width]
+
+    def raw_unpack(self, payload, height, width, fmt, row_bytes=None, out=None):
+        """Packed 10 / 12 / 14-bit camera frames to uint16 frames on the device (mrgingham_amd_raw_unpack_batch), on torch's
+        current stream: payload uint8 [B, P] device tensor, contiguous and 16-byte aligned, P a multiple of 16 and at least
+        (height-1)*row_bytes + raw_row_bytes(width, fmt) -- row f holds frame f as the camera delivered it, row y at byte
+        y*row_bytes (None: raw_row_bytes(width, fmt), rows without padding) -> uint16 [B, height, width], the samples as they
+        are (0 .. 2^N - 1).  fmt: "p10", "p12", "p14" (GenICam Mono10p / Mono12p / Mono14p: an LSB-first bit stream per row),
+        "gev10", "gev12" (GigE Vision Mono10Packed / Mono12Packed: 3-byte pixel pairs).  `out`: a [B, height, >= width]
+        uint16 device tensor (unit column stride) to write into; what lies beyond `width` is not touched; it must not
+        overlap `payload`.
+
+            frames = det.raw_unpack(payload, 3072, 4096, "p12")         # what the grabber wrote, uploaded as it is
+            boards, found = det.find_boards(det.preprocess(frames), gridn=10)"""
+        t = self.torch
+        f = _raw_format(fmt, "raw_unpack")
+        rmin = raw_row_bytes(width, fmt)
+        rowb = rmin if row_bytes is None else int(row_bytes)
+        if not (1 <= height <= 32767) or rowb < rmin:
+            raise ValueError("raw_unpack: height 1 .. 32767, row_bytes at least raw_row_bytes(width, fmt)")
+        if not (payload.is_cuda and payload.dtype == t.uint8 and payload.dim() == 2 and payload.is_contiguous()
+                and payload.shape[1] % 16 == 0 and payload.shape[1] >= (height - 1) * rowb + rmin and payload.data_ptr() % 16 == 0):
+            raise ValueError("raw_unpack: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least (height-1)*row_bytes + raw_row_bytes(width, fmt)")
+        B = payload.shape[0]
+        if out is None:
+            out = t.empty((B, height, width), dtype=t.uint16, device=payload.device)
+        if not (out.is_cuda and out.dtype == t.uint16 and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
+                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
+            raise ValueError("raw_unpack: out is a uint16 [B,height,>=width] tensor on the device with unit column stride")
+        stream = t.cuda.current_stream(payload.device).cuda_stream
+        self._check(self.L.mrgingham_amd_raw_unpack_batch(
+            self.ctx, payload.data_ptr(), payload.shape[1], B, int(width), int(height), rowb, f, out.data_ptr(),
+            out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
         return out[:, :, :width]
 
     def read_pnms(self, paths, nthreads=0):

@@ -4,6 +4,7 @@
 #include "jpeg.h"
 #include "png_filter.h"
 #include "pnm_pixels.h"
+#include "raw_pixels.h"
 #include "tiff_inflate.h"
 #include "tiff_lzw.h"
 #include "../../include/mrgingham_amd.h"
@@ -976,6 +977,32 @@ extern "C" int mrgingham_amd_pgm_header(const uint8_t* data, size_t nbytes, int*
 
 extern "C" int mrgingham_amd_pnm_header(const uint8_t* data, size_t nbytes, mrgingham_amd_pnm_info* info) {
     return mrg::pnm_header(data, nbytes, nbytes, info);
+}
+
+extern "C" int64_t mrgingham_amd_raw_row_bytes(int width, int format) {
+    if (!mrg::raw_format_ok(format) || width < 1 || width > 32767) return -1;
+    return mrg::raw_min_row_bytes(width, format);
+}
+
+// a packed camera frame on the host: every word of every row through raw_pixels.h, the text the device runs
+extern "C" int mrgingham_amd_raw_unpack_image(const uint8_t* payload, size_t nbytes, int width, int height, int64_t row_bytes, int format,
+                                              uint16_t* out, int stride) {
+    if (!payload || !out || !mrg::raw_format_ok(format) || width < 1 || height < 1 || width > 32767 || height > 32767 || stride < width)
+        return MRGINGHAM_AMD_ERR_ARG;
+    const int64_t rmin = mrg::raw_min_row_bytes(width, format);
+    if (row_bytes < rmin || row_bytes > ((int64_t)1 << 40) || (uint64_t)nbytes < (uint64_t)((int64_t)(height - 1) * row_bytes + rmin))
+        return MRGINGHAM_AMD_ERR_ARG;
+    const long long limit = nbytes > (size_t)INT64_MAX ? INT64_MAX : (long long)nbytes;
+    for (int y = 0; y < height; ++y) {
+        uint16_t* o = out + (size_t)y * (size_t)stride;
+        for (int x0 = 0; x0 < width; x0 += 8) {
+            const int k = width - x0 < 8 ? width - x0 : 8;
+            uint32_t d[4];
+            mrg::raw_pixels_any(payload, limit, (long long)y * row_bytes, format, x0, k, d);
+            for (int p = 0; p < k; ++p) o[x0 + p] = (uint16_t)(d[p >> 1] >> (16 * (p & 1)));
+        }
+    }
+    return 0;
 }
 
 extern "C" int mrgingham_amd_bmp_layout(const uint8_t* data, size_t nbytes, mrgingham_amd_bmp_info* info) {
