@@ -1149,6 +1149,38 @@ class Detector:
                                                               status.ctypes.data))
         return frames, status
 
+    def _check_payload(self, who, payload, need_bytes, message):
+        """the [B,P] payload tensor of an *_unpack method; `message`: what P is at least, for the error"""
+        if not (payload.is_cuda and payload.dtype == self.torch.uint8 and payload.dim() == 2 and payload.is_contiguous()
+                and payload.shape[1] % 16 == 0 and payload.shape[1] >= need_bytes and payload.data_ptr() % 16 == 0):
+            raise ValueError(f"{who}: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least {message}")
+
+    def _out_frames(self, who, payload, out, height, width, dtype, message):
+        """`out` of a method that writes [B,height,width] frames for the B rows of `payload`, on its device (None: new
+        frames), checked -> (out, frame_pitch, stride) in samples, as the _batch entry points take them"""
+        B = payload.shape[0]
+        if out is None:
+            out = self.torch.empty((B, height, width), dtype=dtype, device=payload.device)
+        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
+                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
+            raise ValueError(f"{who}: {message}")
+        return out, out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2]
+
+    def _read_files(self, entry, names, H, W, bits, nthreads, pass_bits):
+        """the tail of the read_* methods: `names` (encoded) through the batch loader `entry` into new H x W frames of
+        `bits` bits (pass_bits: the loader takes the depth) -> (frames, status)"""
+        t = self.torch
+        B = len(names)
+        status = np.full((B,), -1, dtype=np.int32)
+        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
+        if B == 0 or H == 0:
+            return frames, status
+        arr = (ctypes.c_char_p * B)(*names)
+        t.cuda.current_stream(self.device).synchronize()
+        self._check(entry(self.ctx, arr, B, W, H, *((bits,) if pass_bits else ()), frames.data_ptr(), H * W, W, int(nthreads),
+                          status.ctypes.data))
+        return frames, status
+
     def png_reconstruct(self, scan, height, width, bits, color_type, out=None):
         """The row filters of inflated PNG scanlines undone and the samples reduced to grey on the device
         (mrgingham_amd_png_reconstruct_batch), on torch's current stream: scan uint8 [B, height, width*bpp + 1] device tensor,
@@ -1162,17 +1194,13 @@ class Detector:
         if not (scan.is_cuda and scan.dtype == t.uint8 and scan.dim() == 3 and scan.is_contiguous()
                 and tuple(scan.shape[1:]) == (height, width * bpp + 1)):
             raise ValueError("png_reconstruct: scan is a contiguous uint8 [B,height,width*bpp+1] tensor on the device")
-        B = scan.shape[0]
-        dtype = t.uint8 if bits == 8 else t.uint16
-        if out is None:
-            out = t.empty((B, height, width), dtype=dtype, device=scan.device)
-        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
-                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
-            raise ValueError("png_reconstruct: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
+        out, frame_pitch, stride = self._out_frames(
+            "png_reconstruct", scan, out, height, width, t.uint8 if bits == 8 else t.uint16,
+            "out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
         stream = t.cuda.current_stream(scan.device).cuda_stream
         self._check(self.L.mrgingham_amd_png_reconstruct_batch(
-            self.ctx, scan.data_ptr(), height * (width * bpp + 1), B, int(width), int(height), int(bits), int(color_type), out.data_ptr(),
-            out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+            self.ctx, scan.data_ptr(), height * (width * bpp + 1), scan.shape[0], int(width), int(height), int(bits), int(color_type),
+            out.data_ptr(), frame_pitch, stride, stream))
         return out[:, :, :width]
 
     def read_pngs(self, paths, nthreads=0):
@@ -1182,10 +1210,7 @@ class Detector:
         malformed, -2 a PNG of another size or depth; failed frames are zero).  Size and depth are those of the first file
         whose header parses (none does: uint8 frames [B,0,0]).  Palette files are decoded by the host threads: same bytes.
         Synchronous."""
-        t = self.torch
         names = [os.fsencode(p) for p in paths]
-        B = len(names)
-        status = np.full((B,), -1, dtype=np.int32)
         H = W = 0
         bits = 8
         for name in names:
@@ -1197,14 +1222,7 @@ class Detector:
             if head is not None:
                 H, W, bits, _ = head
                 break
-        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
-        if B == 0 or H == 0:
-            return frames, status
-        arr = (ctypes.c_char_p * B)(*names)
-        t.cuda.current_stream(self.device).synchronize()
-        self._check(self.L.mrgingham_amd_read_pngs_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
-                                                         status.ctypes.data))
-        return frames, status
+        return self._read_files(self.L.mrgingham_amd_read_pngs_batch, names, H, W, bits, nthreads, True)
 
     def pgm_unpack(self, payload, height, width, bits, out=None):
         """The payloads of binary PGM files to frames on the device (mrgingham_amd_pgm_unpack_batch), on torch's current
@@ -1216,21 +1234,14 @@ class Detector:
         t = self.torch
         if bits not in (8, 16):
             raise ValueError("pgm_unpack: bits 8 or 16")
-        es = bits // 8
-        if not (payload.is_cuda and payload.dtype == t.uint8 and payload.dim() == 2 and payload.is_contiguous()
-                and payload.shape[1] % 16 == 0 and payload.shape[1] >= height * width * es and payload.data_ptr() % 16 == 0):
-            raise ValueError("pgm_unpack: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least height*width*bits/8")
-        B = payload.shape[0]
-        dtype = t.uint8 if bits == 8 else t.uint16
-        if out is None:
-            out = t.empty((B, height, width), dtype=dtype, device=payload.device)
-        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
-                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
-            raise ValueError("pgm_unpack: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
+        self._check_payload("pgm_unpack", payload, height * width * (bits // 8), "height*width*bits/8")
+        out, frame_pitch, stride = self._out_frames(
+            "pgm_unpack", payload, out, height, width, t.uint8 if bits == 8 else t.uint16,
+            "out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
         stream = t.cuda.current_stream(payload.device).cuda_stream
         self._check(self.L.mrgingham_amd_pgm_unpack_batch(
-            self.ctx, payload.data_ptr(), payload.shape[1], B, int(width), int(height), int(bits), out.data_ptr(),
-            out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+            self.ctx, payload.data_ptr(), payload.shape[1], payload.shape[0], int(width), int(height), int(bits), out.data_ptr(), frame_pitch,
+            stride, stream))
         return out[:, :, :width]
 
     def read_pgms(self, paths, nthreads=0):
@@ -1240,10 +1251,7 @@ class Detector:
         status int32 [B] numpy: 0 loaded, -1 unreadable or not a PGM (a file shorter than its header promises included),
         -2 a PGM of another size or depth; failed frames are zero).  Size and depth are those of the first file whose
         header parses (none does: uint8 frames [B,0,0]).  Synchronous."""
-        t = self.torch
         names = [os.fsencode(p) for p in paths]
-        B = len(names)
-        status = np.full((B,), -1, dtype=np.int32)
         H = W = 0
         bits = 8
         for name in names:
@@ -1258,14 +1266,7 @@ class Detector:
             if head is not None and head != PGM_HEADER_CUT:
                 H, W, bits, _ = head
                 break
-        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
-        if B == 0 or H == 0:
-            return frames, status
-        arr = (ctypes.c_char_p * B)(*names)
-        t.cuda.current_stream(self.device).synchronize()
-        self._check(self.L.mrgingham_amd_read_pgms_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
-                                                         status.ctypes.data))
-        return frames, status
+        return self._read_files(self.L.mrgingham_amd_read_pgms_batch, names, H, W, bits, nthreads, True)
 
     def bmp_unpack(self, payload, lut, height, width, bits, top_down=False, out=None):
         """The pixel arrays of Windows Bitmap files to grey frames on the device (mrgingham_amd_bmp_unpack_batch), on torch's
@@ -1280,25 +1281,19 @@ class Detector:
         if bits not in (1, 4, 8, 24, 32):
             raise ValueError("bmp_unpack: bits 1, 4, 8, 24 or 32")
         rowb = (width * bits + 31) // 32 * 4
-        if not (payload.is_cuda and payload.dtype == t.uint8 and payload.dim() == 2 and payload.is_contiguous()
-                and payload.shape[1] % 16 == 0 and payload.shape[1] >= height * rowb and payload.data_ptr() % 16 == 0):
-            raise ValueError("bmp_unpack: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least row_bytes*height")
+        self._check_payload("bmp_unpack", payload, height * rowb, "row_bytes*height")
         B = payload.shape[0]
         need_lut = bits < 8 or (bits == 8 and lut is not None)
         if bits < 8 and lut is None:
             raise ValueError("bmp_unpack: bits 1 and 4 need the grey tables")
         if need_lut and not (lut.is_cuda and lut.dtype == t.uint8 and tuple(lut.shape) == (B, 256) and lut.is_contiguous()):
             raise ValueError("bmp_unpack: lut is a contiguous uint8 [B,256] tensor on the device")
-        if out is None:
-            out = t.empty((B, height, width), dtype=t.uint8, device=payload.device)
-        if not (out.is_cuda and out.dtype == t.uint8 and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
-                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
-            raise ValueError("bmp_unpack: out is a uint8 [B,height,>=width] tensor on the device with unit column stride")
+        out, frame_pitch, stride = self._out_frames("bmp_unpack", payload, out, height, width, t.uint8,
+                                                    "out is a uint8 [B,height,>=width] tensor on the device with unit column stride")
         stream = t.cuda.current_stream(payload.device).cuda_stream
         self._check(self.L.mrgingham_amd_bmp_unpack_batch(
             self.ctx, payload.data_ptr(), payload.shape[1], lut.data_ptr() if need_lut else None, B, int(width), int(height), int(bits),
-            int(bool(top_down)), int(bits == 8 and lut is None), out.data_ptr(), out.stride(0) if B > 1 else height * out.stride(1),
-            out.stride(1) if height > 1 else out.shape[2], stream))
+            int(bool(top_down)), int(bits == 8 and lut is None), out.data_ptr(), frame_pitch, stride, stream))
         return out[:, :, :width]
 
     def read_bmps(self, paths, nthreads=0):
@@ -1309,24 +1304,14 @@ class Detector:
         are decoded by their host thread.  -> (frames uint8 [B,H,W] on the device, status int32 [B] numpy: 0 loaded, -1
         unreadable or not a BMP, -2 a BMP of another size; failed frames are zero).  The size is that of the first file
         whose header parses (none does: frames [B,0,0]).  Synchronous."""
-        t = self.torch
         names = [os.fsencode(p) for p in paths]
-        B = len(names)
-        status = np.full((B,), -1, dtype=np.int32)
         H = W = 0
         for name in names:
             probe = probe_image(name)
             if probe is not None and probe[3] == 5:
                 H, W = probe[0], probe[1]
                 break
-        frames = t.zeros((B, H, W), dtype=t.uint8, device=self.device)
-        if B == 0 or H == 0:
-            return frames, status
-        arr = (ctypes.c_char_p * B)(*names)
-        t.cuda.current_stream(self.device).synchronize()
-        self._check(self.L.mrgingham_amd_read_bmps_batch(self.ctx, arr, B, W, H, frames.data_ptr(), H * W, W, int(nthreads),
-                                                         status.ctypes.data))
-        return frames, status
+        return self._read_files(self.L.mrgingham_amd_read_bmps_batch, names, H, W, 8, nthreads, False)
 
     def pnm_unpack(self, payload, height, width, bits, channels, black_and_white=False, out=None):
         """The rasters of binary Netpbm files to grey frames on the device (mrgingham_amd_pnm_unpack_batch), on torch's current
@@ -1343,20 +1328,14 @@ class Detector:
         if black_and_white and (bits != 8 or channels > 2):
             raise ValueError("pnm_unpack: black_and_white with bits 8 and 1 or 2 channels")
         rowb = (width + 7) // 8 if bits == 1 else width * channels * bits // 8
-        if not (payload.is_cuda and payload.dtype == t.uint8 and payload.dim() == 2 and payload.is_contiguous()
-                and payload.shape[1] % 16 == 0 and payload.shape[1] >= height * rowb and payload.data_ptr() % 16 == 0):
-            raise ValueError("pnm_unpack: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least row_bytes*height")
-        B = payload.shape[0]
-        dtype = t.uint16 if bits == 16 else t.uint8
-        if out is None:
-            out = t.empty((B, height, width), dtype=dtype, device=payload.device)
-        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
-                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
-            raise ValueError("pnm_unpack: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
+        self._check_payload("pnm_unpack", payload, height * rowb, "row_bytes*height")
+        out, frame_pitch, stride = self._out_frames(
+            "pnm_unpack", payload, out, height, width, t.uint16 if bits == 16 else t.uint8,
+            "out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
         stream = t.cuda.current_stream(payload.device).cuda_stream
         self._check(self.L.mrgingham_amd_pnm_unpack_batch(
-            self.ctx, payload.data_ptr(), payload.shape[1], B, int(width), int(height), int(bits), int(channels), int(bool(black_and_white)),
-            out.data_ptr(), out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+            self.ctx, payload.data_ptr(), payload.shape[1], payload.shape[0], int(width), int(height), int(bits), int(channels),
+            int(bool(black_and_white)), out.data_ptr(), frame_pitch, stride, stream))
         return out[:, :, :width]
 
     def raw_unpack(self, payload, height, width, fmt, row_bytes=None, out=None):
@@ -1377,19 +1356,13 @@ class Detector:
         rowb = rmin if row_bytes is None else int(row_bytes)
         if not (1 <= height <= 32767) or rowb < rmin:
             raise ValueError("raw_unpack: height 1 .. 32767, row_bytes at least raw_row_bytes(width, fmt)")
-        if not (payload.is_cuda and payload.dtype == t.uint8 and payload.dim() == 2 and payload.is_contiguous()
-                and payload.shape[1] % 16 == 0 and payload.shape[1] >= (height - 1) * rowb + rmin and payload.data_ptr() % 16 == 0):
-            raise ValueError("raw_unpack: payload is a contiguous, 16-byte aligned uint8 [B,P] tensor on the device, P a multiple of 16 and at least (height-1)*row_bytes + raw_row_bytes(width, fmt)")
-        B = payload.shape[0]
-        if out is None:
-            out = t.empty((B, height, width), dtype=t.uint16, device=payload.device)
-        if not (out.is_cuda and out.dtype == t.uint16 and out.dim() == 3 and out.shape[0] == B and out.shape[1] == height
-                and out.shape[2] >= width and (out.shape[2] <= 1 or out.stride(2) == 1)):
-            raise ValueError("raw_unpack: out is a uint16 [B,height,>=width] tensor on the device with unit column stride")
+        self._check_payload("raw_unpack", payload, (height - 1) * rowb + rmin, "(height-1)*row_bytes + raw_row_bytes(width, fmt)")
+        out, frame_pitch, stride = self._out_frames("raw_unpack", payload, out, height, width, t.uint16,
+                                                    "out is a uint16 [B,height,>=width] tensor on the device with unit column stride")
         stream = t.cuda.current_stream(payload.device).cuda_stream
         self._check(self.L.mrgingham_amd_raw_unpack_batch(
-            self.ctx, payload.data_ptr(), payload.shape[1], B, int(width), int(height), rowb, f, out.data_ptr(),
-            out.stride(0) if B > 1 else height * out.stride(1), out.stride(1) if height > 1 else out.shape[2], stream))
+            self.ctx, payload.data_ptr(), payload.shape[1], payload.shape[0], int(width), int(height), rowb, f, out.data_ptr(), frame_pitch,
+            stride, stream))
         return out[:, :, :width]
 
     def read_pnms(self, paths, nthreads=0):
@@ -1399,10 +1372,7 @@ class Detector:
         (option "pnm_unpack" 0: the host threads decode instead).  -> (frames uint8 or uint16 [B,H,W] on the device, status
         int32 [B] numpy: 0 loaded, -1 unreadable or not Netpbm, -2 another size or depth; failed frames are zero).  Size and
         depth are those of the first file whose header parses (none does: uint8 frames [B,0,0]).  Synchronous."""
-        t = self.torch
         names = [os.fsencode(p) for p in paths]
-        B = len(names)
-        status = np.full((B,), -1, dtype=np.int32)
         H = W = 0
         bits = 8
         for name in names:
@@ -1410,14 +1380,7 @@ class Detector:
             if probe is not None and probe[3] in (1, 6):
                 H, W, bits = probe[0], probe[1], probe[2]
                 break
-        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
-        if B == 0 or H == 0:
-            return frames, status
-        arr = (ctypes.c_char_p * B)(*names)
-        t.cuda.current_stream(self.device).synchronize()
-        self._check(self.L.mrgingham_amd_read_pnms_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
-                                                         status.ctypes.data))
-        return frames, status
+        return self._read_files(self.L.mrgingham_amd_read_pnms_batch, names, H, W, bits, nthreads, True)
 
     def tiff_decode(self, datas, layouts=None, out=None):
         """TIFF files held in memory to grey frames on the device (mrgingham_amd_tiff_decode_batch_tiled), on torch's current
@@ -1448,19 +1411,14 @@ class Detector:
         d_ns = t.tensor([l.nstrips for l in layouts], dtype=t.int32, device=self.device)
         d_status = t.full((B,), -7, dtype=t.int32, device=self.device)
         d_sstatus = t.zeros((B, P), dtype=t.int32, device=self.device)
-        dtype = t.uint8 if lay.bits == 8 else t.uint16
-        if out is None:
-            out = t.empty((B, H, W), dtype=dtype, device=self.device)
-        if not (out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == B and out.shape[1] == H
-                and out.shape[2] >= W and (out.shape[2] <= 1 or out.stride(2) == 1)):
-            raise ValueError("tiff_decode: out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
+        out, frame_pitch, stride = self._out_frames(
+            "tiff_decode", d_files, out, H, W, t.uint8 if lay.bits == 8 else t.uint16,
+            "out is a [B,height,>=width] tensor on the device with unit column stride, uint8 or uint16 by bits")
         info = _lib.TiffInfo(*lay.key())
         stream = t.cuda.current_stream(self.device).cuda_stream
         self._check(self.L.mrgingham_amd_tiff_decode_batch_tiled(
             self.ctx, d_files.data_ptr(), pitch, d_strips.data_ptr(), P, d_ns.data_ptr(), B, ctypes.byref(info), lay.tile_width,
-            lay.tile_length, out.data_ptr(),
-            out.stride(0) if B > 1 else H * out.stride(1), out.stride(1) if H > 1 else out.shape[2], d_status.data_ptr(),
-            d_sstatus.data_ptr(), stream))
+            lay.tile_length, out.data_ptr(), frame_pitch, stride, d_status.data_ptr(), d_sstatus.data_ptr(), stream))
         return out[:, :, :W], d_status.cpu().numpy(), d_sstatus.cpu().numpy()
 
     def read_tiffs(self, paths, nthreads=0, deflate=None):
@@ -1481,10 +1439,7 @@ class Detector:
         if deflate is not None:
             with self._with_options(tiff_deflate=int(deflate == "device")):
                 return self.read_tiffs(paths, nthreads)
-        t = self.torch
         names = [os.fsencode(p) for p in paths]
-        B = len(names)
-        status = np.full((B,), -1, dtype=np.int32)
         H = W = 0
         bits = 8
         for p in paths:
@@ -1492,14 +1447,7 @@ class Detector:
             if head is not None and head[3] == 4:
                 H, W, bits, _ = head
                 break
-        frames = t.zeros((B, H, W), dtype=t.uint8 if bits == 8 else t.uint16, device=self.device)
-        if B == 0 or H == 0:
-            return frames, status
-        arr = (ctypes.c_char_p * B)(*names)
-        t.cuda.current_stream(self.device).synchronize()
-        self._check(self.L.mrgingham_amd_read_tiffs_batch(self.ctx, arr, B, W, H, bits, frames.data_ptr(), H * W, W, int(nthreads),
-                                                          status.ctypes.data))
-        return frames, status
+        return self._read_files(self.L.mrgingham_amd_read_tiffs_batch, names, H, W, bits, nthreads, True)
 
     BLOBS_STATS = ("calls", "chunks", "nodes", "contours", "points", "device_ms", "host_ms", "frames")
 

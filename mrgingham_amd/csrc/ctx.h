@@ -18,7 +18,9 @@
 #include "../../include/mrgingham_amd.h"
 #include "common.h"
 #include "grid.h"
+#include "image_io.h"
 #include "kernels.h"
+#include "unpack_rows.h"
 
 namespace mrg {
 
@@ -269,10 +271,11 @@ struct mrgingham_amd_ctx {
     double blob_stat[8] = {};    // mrgingham_amd_blobs_stats (+ [7]: frames)
     // The two chunk slots of the file loaders (loader.hip: loader_ring): two chunks of files in flight, one being decoded
     // into its page-locked staging while the other uploads into its device image and runs its kernels; `ev` follows the
-    // chunk's last launch.  mrgingham_amd_read_jpegs_batch (jpeg_idct.hip; staging: coefficients | tables) and
-    // mrgingham_amd_read_pngs_batch (png_recon.hip; staging: scanlines) both use them.  Their calls never overlap,
-    // because both are synchronous, and each call sizes and fills what it reads: nothing a call leaves in a slot matters
-    // to the next.  The staging is zero only until its first use (ensure_pinned zeroes it when it grows); that is enough,
+    // chunk's last launch.  Every file-list loader uses them: mrgingham_amd_read_jpegs_batch (jpeg_idct.hip; staging:
+    // coefficients | tables), _read_pngs_batch (png_recon.hip; scanlines), _read_pgms_batch (pgm_unpack.hip; payloads),
+    // _read_tiffs_batch (tiff_decode.hip; files, strip tables), _read_bmps_batch (bmp_unpack.hip; grey tables | pixel
+    // arrays) and _read_pnms_batch (pnm_unpack.hip; rasters).  Their calls never overlap, because all are synchronous,
+    // and each call sizes and fills what it reads: nothing a call leaves in a slot matters to the next.  The staging is zero only until its first use (ensure_pinned zeroes it when it grows); that is enough,
     // because the IDCT kernel never reads a block outside width x height, and every decoded file covers those.
     // Option "jpeg_chunk_frames" (test hook): at most that many frames per chunk, 0 = by jpeg_coef_budget
     struct LoaderSlot {
@@ -280,7 +283,7 @@ struct mrgingham_amd_ctx {
         mrg::PinBuf pin;
         mrg::Event ev;
     } loader_slot[2];
-    size_t jpeg_coef_budget = (size_t)1 << 30;  // both device buffers together, for either loader
+    size_t jpeg_coef_budget = (size_t)1 << 30;  // both device buffers together, for every loader
     int jpeg_chunk_frames = 0;
     // the device entropy path of the loader and mrgingham_amd_jpeg_entropy_batch (jpeg_huff.hip): per chunk slot one
     // staging image (jpeg_stage.h has the layout), page-locked on the host and mirrored on the device, both grown on demand.  Options "jpeg_entropy" (0: host threads
@@ -484,16 +487,22 @@ int check_coef_area(mrgingham_amd_ctx* ctx, const int16_t* d_coef, int64_t coef_
 void launch_jpeg_idct(const int16_t* d_coef, int64_t coef_pitch, const uint16_t* d_quant, int nframes, int width, int height,
                       int blocks_w, uint8_t* d_out, int64_t frame_pitch, int stride, hipStream_t s);
 
-// loader.hip: what the file-list loaders (read_jpegs_batch, its device-entropy route, read_pngs_batch) share
+// loader.hip: what the file-list loaders share -- read_jpegs_batch (jpeg_idct.hip) and its device-entropy route
+// (jpeg_huff.hip), read_pngs_batch (png_recon.hip), read_pgms_batch (pgm_unpack.hip), read_tiffs_batch (tiff_decode.hip),
+// read_bmps_batch (bmp_unpack.hip), read_pnms_batch (pnm_unpack.hip)
 // the descriptor of a file list and its frames: 0, or MRGINGHAM_AMD_ERR_ARG with "bad <format> file batch descriptor"
 // (elem: bytes per sample, 1 or 2; a NULL entry of filenames is refused)
 int check_file_batch(mrgingham_amd_ctx* ctx, const char* format, const char* const* filenames, int nfiles, int width, int height,
                      size_t elem, const void* d_out, int64_t frame_pitch, int stride, const int32_t* h_status);
 // zeroes width x height samples of `elem` bytes of frame `frame` (of a file that failed)
 hipError_t zero_frame(void* d_out, int64_t frame, int64_t frame_pitch, int stride, int width, int height, size_t elem, hipStream_t s);
-// the `after` of a loader whose frames are bytes: zeroes the frames of the chunk's files whose h_status is not 0
-std::function<int(int k, int f0, int n)> zero_failed_frames(mrgingham_amd_ctx* ctx, uint8_t* d_out, int64_t frame_pitch, int stride,
-                                                            int width, int height, const int32_t* h_status);
+// the `after` of a loader: zeroes the frames (samples of `elem` bytes) of the chunk's files whose h_status is not 0
+std::function<int(int k, int f0, int n)> zero_failed_frames(mrgingham_amd_ctx* ctx, void* d_out, int64_t frame_pitch, int stride, int width,
+                                                            int height, size_t elem, const int32_t* h_status);
+// the launch shape (unpack_rows.h) of an unpack kernel over nrows rows of row_bytes_out destination bytes on the context's
+// device; the pitches in bytes
+int unpack_launch_shape(mrgingham_amd_ctx* ctx, const void* d_out, long long frame_pitch_b, long long stride_b, long long row_bytes_out,
+                        long long nrows, UnpackShape* shape);
 // The two-slot chunk ring on ctx->pix: chunks of `chunk` files alternate between the slots (one slot if there is one
 // chunk), whose device buffers are grown to dev_bytes and whose staging to pin_bytes (0: the stage grows it when it
 // needs it).  Per chunk: wait for the event of the slot's previous chunk and, given `finish`, finish(k) behind it; then
@@ -503,6 +512,29 @@ std::function<int(int k, int f0, int n)> zero_failed_frames(mrgingham_amd_ctx* c
 using LoaderStage = std::function<int(int k, int f0, int n)>;
 int loader_ring(mrgingham_amd_ctx* ctx, int nfiles, int chunk, size_t dev_bytes, size_t pin_bytes, const LoaderStage& stage,
                 const LoaderStage& after, const std::function<int(int k)>& finish);
+// The loader of the formats whose raster goes to the device as it lies in the file (read_bmps_batch, read_pnms_batch), a
+// stage of loader_ring: a header pass over all files, one staging area per file of a chunk sized by the largest raster,
+// one upload per chunk, one launch per run of files with the same layout; a file the kernel does not take is decoded by
+// its host thread (read_image) into its area and copied to its frame.  What a format brings (i: index into the list):
+struct StagedThread {  // what a host thread keeps from file to file
+    std::vector<uint8_t> head;
+    Image im;
+};
+struct StagedFormat {
+    size_t front;   // bytes per file in front of a chunk's areas, uploaded with them (BMP: the grey table), or 0
+    int chunk_cap;  // the format's "<format>_chunk_frames" option
+    // the header pass: the file's status (0, -1, -2); with 0, *route = 1 (its raster through the kernel, *raster_bytes of
+    // it) or 2 (decoded by a host thread), and the format's own record of the layout
+    std::function<int32_t(int i, StagedThread& t, int* route, size_t* raster_bytes)> header;
+    // a route-1 file's raster to dst, its front bytes to `front`; false: unreadable
+    std::function<bool(int i, StagedThread& t, uint8_t* dst, uint8_t* front)> stage_raster;
+    std::function<bool(int i, int j)> same_launch;  // files i and j, both route 1, can share a launch
+    // the launch over n files from file i on: rasters at d_payload, payload_pitch apart, front bytes at d_front, into `frame`
+    std::function<int(int i, int n, const uint8_t* d_payload, int64_t payload_pitch, const uint8_t* d_front, uint8_t* frame)> launch;
+};
+// (arguments checked by the caller: check_file_batch; bits 8 or 16 of a frame's samples)
+int read_staged_batch(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height, int bits, void* d_out,
+                      int64_t frame_pitch, int stride, int nthreads, int32_t* h_status, const StagedFormat& fmt);
 // jpeg_huff.hip: mrgingham_amd_read_jpegs_batch with option "jpeg_entropy" 1 (arguments checked, geometry chosen there)
 int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenames, int nfiles, int width, int height,
                               uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status, int bw, int bh,

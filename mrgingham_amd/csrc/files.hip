@@ -1,21 +1,30 @@
 // Host side of libmrgingham_amd.so, a list of image files to boards (mrgingham_amd_find_boards_files): the schedule that
-// keeps the kernels of the loader (jpeg_idct.hip, jpeg_huff*.hip, png_recon.hip, pgm_unpack.hip, bmp_unpack.hip, pnm_unpack.hip, tiff_decode.hip), of the preprocessing (preprocess.hip,
-// preprocess16_batch.hip) and of the board
+// keeps the kernels of the loaders, of the preprocessing (preprocess.hip, preprocess16_batch.hip) and of the board
 // detector (boards.hip) fed from a list of several sizes and formats.  No kernel of its own.
 //
 //   loader thread, LOADER context            calling thread, DETECTOR context
 //   ------------------------------           ---------------------------------------------------------
 //   wait: chunk c - 3 collected              wait: chunk c loaded            (or collect the oldest job meanwhile)
-//   PGM / PNG -> page-locked staging         pix stream waits for the slot's upload event
+//   host files -> page-locked staging        pix stream waits for the slot's upload event
 //     (host threads), upload, event          preprocess_batch on the pix stream, find_boards_submit_ex
-//   JPEG runs -> read_jpegs_batch            collect chunk c - k, scatter its results, advance the final prefix
-//   (PNG runs -> read_pngs_batch where the caller set MRGINGHAM_AMD_FILES_PNG_DEVICE,
-//    TIFF runs -> read_tiffs_batch where the caller set MRGINGHAM_AMD_FILES_TIFF_DEVICE,
-//    BMP runs -> read_bmps_batch where the caller set MRGINGHAM_AMD_FILES_BMP_DEVICE,
-//    PBM / PAM runs -> read_pnms_batch where the caller set MRGINGHAM_AMD_FILES_PNM_DEVICE)
-//   (16-bit files, where the caller set MRGINGHAM_AMD_FILES_DEEP_CHUNKS, in chunks of their own: PGM runs ->
-//    read_pgms_batch, PNG as above, as uint16 frames; the detector side runs preprocess16_batch on such a chunk)
+//   runs of a batch route -> its loader      collect chunk c - k, scatter its results, advance the final prefix
 //   chunk c loaded                           (one-image files are processed when the prefix reaches them)
+//
+// The route of a file (Route below); every run of consecutive files of a chunk with one batch route is one call of its
+// loader, straight into the chunk's frames:
+//
+//   route   files                            loader (kernels)                              where the caller set
+//   -----   ------------------------------   -------------------------------------------   ---------------------------------
+//   host    whatever has no other route      read_image on the host threads
+//   JPEG    JPEG                             read_jpegs_batch (jpeg_idct, jpeg_huff*.hip)   (always)
+//   PNG     PNG without a palette            read_pngs_batch (png_recon.hip)                MRGINGHAM_AMD_FILES_PNG_DEVICE
+//   PGM     16-bit PGM                       read_pgms_batch (pgm_unpack.hip)               MRGINGHAM_AMD_FILES_DEEP_CHUNKS
+//   TIFF    TIFF                             read_tiffs_batch (tiff_decode.hip)             MRGINGHAM_AMD_FILES_TIFF_DEVICE
+//   BMP     BMP                              read_bmps_batch (bmp_unpack.hip)               MRGINGHAM_AMD_FILES_BMP_DEVICE
+//   PNM     PBM / PAM                        read_pnms_batch (pnm_unpack.hip)               MRGINGHAM_AMD_FILES_PNM_DEVICE
+//
+// 16-bit files are in chunks of their own, as uint16 frames, only with MRGINGHAM_AMD_FILES_DEEP_CHUNKS (the PNG, TIFF and
+// PNM routes take them then); the detector side runs preprocess16_batch on such a chunk.
 //
 // The ring has three slots; slot c % 3 holds chunk c from its load to its collect.  What orders the two contexts:
 // loader -> detector, the upload event of the slot (read_jpegs_batch is complete when it returns); detector -> loader,
@@ -40,15 +49,28 @@ constexpr size_t kBufferBytes = (size_t)1 << 30;    // one ring buffer (a chunk'
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+enum class Route : int8_t { host, jpeg, png, pgm, tiff, bmp, pnm };  // (the table at the head of the file)
+
 struct FileInfo {
     int w = 0, h = 0, bits = 0, kind = 0;  // kind 0: the probe rejected the file
-    bool png_device = false;               // a PNG that goes through read_pngs_batch (MRGINGHAM_AMD_FILES_PNG_DEVICE)
-    bool pgm_device = false;               // a 16-bit PGM that goes through read_pgms_batch (MRGINGHAM_AMD_FILES_DEEP_CHUNKS)
-    bool tiff_device = false;              // a TIFF that goes through read_tiffs_batch (MRGINGHAM_AMD_FILES_TIFF_DEVICE)
-    bool bmp_device = false;               // a BMP that goes through read_bmps_batch (MRGINGHAM_AMD_FILES_BMP_DEVICE)
-    bool pnm_device = false;               // a P4 / P7 file that goes through read_pnms_batch (MRGINGHAM_AMD_FILES_PNM_DEVICE)
-    bool batch_loader() const { return kind == 3 || png_device || pgm_device || tiff_device || bmp_device || pnm_device; }
+    Route route = Route::host;
+    bool batch_loader() const { return route != Route::host; }
 };
+
+// the batch loaders behind one signature (the JPEG and BMP loaders take no depth: their frames are bytes)
+int read_run(mrgingham_amd_ctx* ctx, Route via, const char* const* names, int n, int w, int h, int bits, uint8_t* frames, int64_t pitch,
+             int nthreads, int32_t* st) {
+    switch (via) {
+        case Route::jpeg: return mrgingham_amd_read_jpegs_batch(ctx, names, n, w, h, frames, pitch, w, nthreads, st);
+        case Route::png: return mrgingham_amd_read_pngs_batch(ctx, names, n, w, h, bits, frames, pitch, w, nthreads, st);
+        case Route::pgm: return mrgingham_amd_read_pgms_batch(ctx, names, n, w, h, bits, frames, pitch, w, nthreads, st);
+        case Route::tiff: return mrgingham_amd_read_tiffs_batch(ctx, names, n, w, h, bits, frames, pitch, w, nthreads, st);
+        case Route::bmp: return mrgingham_amd_read_bmps_batch(ctx, names, n, w, h, frames, pitch, w, nthreads, st);
+        case Route::pnm: return mrgingham_amd_read_pnms_batch(ctx, names, n, w, h, bits, frames, pitch, w, nthreads, st);
+        case Route::host: break;
+    }
+    return MRGINGHAM_AMD_ERR_ARG;
+}
 
 struct Chunk {
     std::vector<int> files;  // list indices, in slot order
@@ -112,8 +134,8 @@ int load_chunk(Run& R, int c) {
     S.load_status.assign((size_t)n, -1);
     if (S.uploaded) MRG_HIP_CHECK(hipEventSynchronize(S.ev_up));  // (long done: the chunk that recorded it has been collected)
     S.uploaded = false;
-    // PGM / PNG: the host threads decode into the staging of the slot (a 16-bit chunk: native uint16 samples), consecutive
-    // slots go up in one copy
+    // the host route: the host threads decode into the staging of the slot (a 16-bit chunk: native uint16 samples),
+    // consecutive slots go up in one copy
     std::vector<int> host;
     for (int k = 0; k < n; ++k)
         if (!R.info[(size_t)ch.files[(size_t)k]].batch_loader()) host.push_back(k);
@@ -137,29 +159,19 @@ int load_chunk(Run& R, int c) {
         MRG_HIP_CHECK(hipEventRecord(S.ev_up, s));
         S.uploaded = true;
     }
-    // JPEG, and PNG / 16-bit PGM where the caller asked for it: every run of consecutive slots of one of them is one call of
-    // its batch loader, straight into the chunk's frames
+    // the batch routes: every run of consecutive slots of one of them is one call of its loader, straight into the chunk's
+    // frames
     long nbatch_ok = 0;
-    auto route = [&](int k) {
-        const FileInfo& f = R.info[(size_t)ch.files[(size_t)k]];
-        return f.kind == 3 ? 1 : f.png_device ? 2 : f.pgm_device ? 3 : f.tiff_device ? 4 : f.bmp_device ? 5 : f.pnm_device ? 6 : 0;
-    };
+    auto route = [&](int k) { return R.info[(size_t)ch.files[(size_t)k]].route; };
     for (int k = 0; k < n;) {
-        const int via = route(k);
-        if (!via) { ++k; continue; }
+        const Route via = route(k);
+        if (via == Route::host) { ++k; continue; }
         int j = k + 1;
         while (j < n && route(j) == via) ++j;
         std::vector<const char*> run;
         for (int i = k; i < j; ++i) run.push_back(R.names[ch.files[(size_t)i]]);
-        uint8_t* const frames = d_raw + (size_t)k * pitch;
-        const int64_t fpitch = (int64_t)frame_pitch_of(ch.w, ch.h);
-        int32_t* const st = S.load_status.data() + k;
-        const int rc = via == 1   ? mrgingham_amd_read_jpegs_batch(ctx, run.data(), j - k, ch.w, ch.h, frames, fpitch, ch.w, R.nthreads, st)
-                       : via == 2 ? mrgingham_amd_read_pngs_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
-                       : via == 3 ? mrgingham_amd_read_pgms_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
-                       : via == 4 ? mrgingham_amd_read_tiffs_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st)
-                       : via == 5 ? mrgingham_amd_read_bmps_batch(ctx, run.data(), j - k, ch.w, ch.h, frames, fpitch, ch.w, R.nthreads, st)
-                                  : mrgingham_amd_read_pnms_batch(ctx, run.data(), j - k, ch.w, ch.h, ch.bits, frames, fpitch, ch.w, R.nthreads, st);
+        const int rc = read_run(ctx, via, run.data(), j - k, ch.w, ch.h, ch.bits, d_raw + (size_t)k * pitch, (int64_t)frame_pitch_of(ch.w, ch.h),
+                                R.nthreads, S.load_status.data() + k);
         if (rc) return rc;
         for (int i = k; i < j; ++i) {
             if (S.load_status[(size_t)i] == 0) ++nbatch_ok;
@@ -224,62 +236,21 @@ int mrgingham_amd_files_plan(const int32_t* key, int nfiles, int batch_frames, i
     }
 }
 
-int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
-                                    double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
-                                    void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats) {
-    return mrgingham_amd_find_boards_files_ex2(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
-                                               nstats, 0);
-}
+}  // extern "C"
 
-int mrgingham_amd_find_boards_files_ex(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
-                                       double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
-                                       void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
-                                       int loader_flags) {
-    if (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS)) return MRGINGHAM_AMD_ERR_ARG;
-    return mrgingham_amd_find_boards_files_ex2(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
-                                               nstats, loader_flags);
-}
+namespace {
 
-int mrgingham_amd_find_boards_files_ex2(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
-                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
-                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
-                                        int loader_flags) {
-    if (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE)) return MRGINGHAM_AMD_ERR_ARG;
-    return mrgingham_amd_find_boards_files_ex3(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
-                                               nstats, loader_flags);
-}
+constexpr int kFlagsEx = MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS, kFlagsEx2 = kFlagsEx | MRGINGHAM_AMD_FILES_TIFF_DEVICE,
+              kFlagsEx3 = kFlagsEx2 | MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE, kFlagsEx4 = kFlagsEx3 | MRGINGHAM_AMD_FILES_BMP_DEVICE,
+              kFlagsEx5 = kFlagsEx4 | MRGINGHAM_AMD_FILES_PNM_DEVICE;
 
-int mrgingham_amd_find_boards_files_ex3(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
-                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
-                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
-                                        int loader_flags) {
-    if (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE |
-                         MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE))
-        return MRGINGHAM_AMD_ERR_ARG;
-    return mrgingham_amd_find_boards_files_ex4(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
-                                               nstats, loader_flags);
-}
-
-int mrgingham_amd_find_boards_files_ex4(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
-                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
-                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
-                                        int loader_flags) {
-    if (loader_flags & ~(MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE |
-                         MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE | MRGINGHAM_AMD_FILES_BMP_DEVICE))
-        return MRGINGHAM_AMD_ERR_ARG;
-    return mrgingham_amd_find_boards_files_ex5(filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats,
-                                               nstats, loader_flags);
-}
-
-int mrgingham_amd_find_boards_files_ex5(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o,
-                                        double* h_boards, signed char* h_levels, signed char* h_found_level, int32_t* h_status,
-                                        void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats,
-                                        int loader_flags) {
-    constexpr int kFlags = MRGINGHAM_AMD_FILES_PNG_DEVICE | MRGINGHAM_AMD_FILES_DEEP_CHUNKS | MRGINGHAM_AMD_FILES_TIFF_DEVICE |
-                           MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE | MRGINGHAM_AMD_FILES_BMP_DEVICE | MRGINGHAM_AMD_FILES_PNM_DEVICE;
+// every mrgingham_amd_find_boards_files* entry point: `accepted` is the mask of loader flags that the entry point takes
+int find_boards_files(int accepted, const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o, double* h_boards,
+                      signed char* h_levels, signed char* h_found_level, int32_t* h_status, void (*progress)(int nfinal, void* cookie),
+                      void* cookie, double* stats, int nstats, int loader_flags) {
     // (Deflate strips on the device are a part of the TIFF device route, not a route of their own)
     if ((loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEFLATE_DEVICE) && !(loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEVICE)) return MRGINGHAM_AMD_ERR_ARG;
-    if (nfiles < 0 || (loader_flags & ~kFlags) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
+    if (nfiles < 0 || (loader_flags & ~accepted) || !o || o->gridn < 2 || o->gridn > 1024 || o->image_pyramid_level > kMaxLevel || o->blur_radius < 0 ||
         o->blur_radius > 64 || o->device < -1 || nstats < 0 || (nstats > 0 && !stats) ||
         (nfiles > 0 && (!filenames || !h_boards || !h_levels || !h_found_level || !h_status)))
         return MRGINGHAM_AMD_ERR_ARG;
@@ -315,13 +286,17 @@ int mrgingham_amd_find_boards_files_ex5(const char* const* filenames, int nfiles
         for_files(probe_pool, R.nthreads, nfiles, [&](int i) {
             FileInfo& f = R.info[(size_t)i];
             if (!probe_image(filenames[i], &f.w, &f.h, &f.bits, &f.kind)) f = FileInfo{};
-            // (palette files keep the host decoder: read_pngs_batch would hand them to it anyway, one by one)
-            if ((loader_flags & MRGINGHAM_AMD_FILES_PNG_DEVICE) && f.kind == 2 && (f.bits == 8 || deep_chunks))
-                f.png_device = png_header(filenames[i], nullptr, nullptr, nullptr) != 3;
-            f.pgm_device = deep_chunks && f.kind == 1 && f.bits == 16;
-            f.tiff_device = (loader_flags & MRGINGHAM_AMD_FILES_TIFF_DEVICE) && f.kind == 4 && (f.bits == 8 || deep_chunks);
-            f.bmp_device = (loader_flags & MRGINGHAM_AMD_FILES_BMP_DEVICE) && f.kind == 5;
-            f.pnm_device = (loader_flags & MRGINGHAM_AMD_FILES_PNM_DEVICE) && f.kind == 6 && (f.bits == 8 || deep_chunks);
+            const bool depth_ok = f.bits == 8 || deep_chunks;
+            auto asked = [&](int flag) { return (loader_flags & flag) != 0; };
+            // (palette PNGs keep the host decoder: read_pngs_batch would hand them to it anyway, one by one)
+            f.route = f.kind == 3                                                                    ? Route::jpeg
+                      : f.kind == 2 && asked(MRGINGHAM_AMD_FILES_PNG_DEVICE) && depth_ok &&
+                              png_header(filenames[i], nullptr, nullptr, nullptr) != 3               ? Route::png
+                      : f.kind == 1 && deep_chunks && f.bits == 16                                   ? Route::pgm
+                      : f.kind == 4 && asked(MRGINGHAM_AMD_FILES_TIFF_DEVICE) && depth_ok            ? Route::tiff
+                      : f.kind == 5 && asked(MRGINGHAM_AMD_FILES_BMP_DEVICE)                         ? Route::bmp
+                      : f.kind == 6 && asked(MRGINGHAM_AMD_FILES_PNM_DEVICE) && depth_ok             ? Route::pnm
+                                                                                                     : Route::host;
         });
     }
     size_t max_frame = 0, max_host_frame = 0;
@@ -571,5 +546,30 @@ int mrgingham_amd_find_boards_files_ex5(const char* const* filenames, int nfiles
     st[MRGINGHAM_AMD_FILES_LOADER_WAIT_MS] = P.loader_wait_ms;
     return leave(MRGINGHAM_AMD_OK);
 }
+
+}  // namespace
+
+extern "C" {
+
+int mrgingham_amd_find_boards_files(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o, double* h_boards,
+                                    signed char* h_levels, signed char* h_found_level, int32_t* h_status,
+                                    void (*progress)(int nfinal, void* cookie), void* cookie, double* stats, int nstats) {
+    return find_boards_files(0, filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats, nstats, 0);
+}
+
+// the later entry points differ in the loader flags they accept: each takes the flags that existed when it was added
+#define MRG_FILES_ENTRY(name, accepted)                                                                                                \
+    int name(const char* const* filenames, int nfiles, const mrgingham_amd_files_options* o, double* h_boards, signed char* h_levels,  \
+             signed char* h_found_level, int32_t* h_status, void (*progress)(int nfinal, void* cookie), void* cookie, double* stats,   \
+             int nstats, int loader_flags) {                                                                                           \
+        return find_boards_files(accepted, filenames, nfiles, o, h_boards, h_levels, h_found_level, h_status, progress, cookie, stats, \
+                                 nstats, loader_flags);                                                                                \
+    }
+MRG_FILES_ENTRY(mrgingham_amd_find_boards_files_ex, kFlagsEx)
+MRG_FILES_ENTRY(mrgingham_amd_find_boards_files_ex2, kFlagsEx2)
+MRG_FILES_ENTRY(mrgingham_amd_find_boards_files_ex3, kFlagsEx3)
+MRG_FILES_ENTRY(mrgingham_amd_find_boards_files_ex4, kFlagsEx4)
+MRG_FILES_ENTRY(mrgingham_amd_find_boards_files_ex5, kFlagsEx5)
+#undef MRG_FILES_ENTRY
 
 }  // extern "C"

@@ -262,7 +262,7 @@ int read_jpegs_device_entropy(mrgingham_amd_ctx* ctx, const char* const* filenam
         MRG_HIP_CHECK(hipGetLastError());
         return 0;
     };
-    return loader_ring(ctx, nfiles, chunk, slot_bytes, 0, stage, zero_failed_frames(ctx, d_out, frame_pitch, stride, width, height, h_status),
+    return loader_ring(ctx, nfiles, chunk, slot_bytes, 0, stage, zero_failed_frames(ctx, d_out, frame_pitch, stride, width, height, 1, h_status),
                        finish);
 }
 

@@ -210,7 +210,7 @@ int mrgingham_amd_read_jpegs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
         return 0;
     };
     return loader_ring(ctx, nfiles, chunk, slot_bytes, slot_bytes, stage,
-                       zero_failed_frames(ctx, d_out, frame_pitch, stride, width, height, h_status), nullptr);  // failed files: zeros afterwards
+                       zero_failed_frames(ctx, d_out, frame_pitch, stride, width, height, 1, h_status), nullptr);  // failed files: zeros afterwards
 }
 
 }  // extern "C"

@@ -7,12 +7,11 @@
 #include "ctx.h"
 #include "image_io.h"
 #include "loader.h"
+#include "unpack_rows.h"
 
 using namespace mrg;
 
 namespace {
-
-constexpr int kLanes = 256;
 
 // What a lane holds of one 16-byte word of a destination row: bytes [lo, lo + n) of the row, n <= 16, in d from byte 0 on.
 struct PgmGroup {
@@ -80,12 +79,12 @@ __device__ __forceinline__ void pgm_store(uint8_t* dst, const PgmGroup& g) {
 // itself where the two layouts coincide; the words of source and destination are then the same, a lane stores exactly
 // the samples it loaded, and the samples of a word that two rows share are stored by the lane that uses them.
 template <int BITS>
-__global__ __launch_bounds__(kLanes) void pgm_unpack_kernel(const uint8_t* payload, long long payload_pitch, int rowb, int height,
+__global__ __launch_bounds__(kUnpackLanes) void pgm_unpack_kernel(const uint8_t* payload, long long payload_pitch, int rowb, int height,
                                                             long long nrows, uint8_t* out, long long frame_pitch_b,
                                                             long long stride_b, int lpr_shift) {
     const int lanes = 1 << lpr_shift, l = (int)threadIdx.x & (lanes - 1), sub = (int)threadIdx.x >> lpr_shift;
-    const long long rows_per_step = (long long)gridDim.x * (kLanes >> lpr_shift);
-    for (long long row = (long long)blockIdx.x * (kLanes >> lpr_shift) + sub; row < nrows; row += rows_per_step) {
+    const long long rows_per_step = (long long)gridDim.x * (kUnpackLanes >> lpr_shift);
+    for (long long row = (long long)blockIdx.x * (kUnpackLanes >> lpr_shift) + sub; row < nrows; row += rows_per_step) {
         const long long f = row / height;
         const int y = (int)(row - f * height);
         const uint8_t* src = payload + f * payload_pitch + (long long)y * rowb;
@@ -108,23 +107,14 @@ int launch_pgm_unpack(mrgingham_amd_ctx* ctx, const uint8_t* d_payload, int64_t 
                       void* d_out, int64_t frame_pitch, int stride, hipStream_t s) {
     const int es = bits / 8, rowb = width * es;
     const long long nrows = (long long)nframes * height;
-    // the lanes of a row: the power of two that covers its words (one more than rowb / 16 where a row can begin inside a word)
-    const bool aligned = !((uintptr_t)d_out & 15) && !(((long long)frame_pitch * es) & 15) && !(((long long)stride * es) & 15);
-    const int kmax = (rowb + 15) / 16 + (aligned ? 0 : 1);
-    int lpr_shift = 0;
-    while ((1 << lpr_shift) < kmax && (1 << lpr_shift) < kLanes) ++lpr_shift;
-    const int rows_per_block = kLanes >> lpr_shift;
-    int cus = 0;
-    MRG_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    // sized to the device: eight workgroups of 256 lanes fill a CU
-    long long blocks = (nrows + rows_per_block - 1) / rows_per_block;
-    if (blocks > (long long)cus * 8) blocks = (long long)cus * 8;
+    UnpackShape sh;
+    if (int rc = unpack_launch_shape(ctx, d_out, (long long)frame_pitch * es, (long long)stride * es, rowb, nrows, &sh)) return rc;
     if (bits == 8)
-        hipLaunchKernelGGL(pgm_unpack_kernel<8>, dim3((unsigned)blocks), dim3(kLanes), 0, s, d_payload, (long long)payload_pitch, rowb, height,
-                           nrows, (uint8_t*)d_out, (long long)frame_pitch * es, (long long)stride * es, lpr_shift);
+        hipLaunchKernelGGL(pgm_unpack_kernel<8>, dim3((unsigned)sh.blocks), dim3(kUnpackLanes), 0, s, d_payload, (long long)payload_pitch, rowb, height,
+                           nrows, (uint8_t*)d_out, (long long)frame_pitch * es, (long long)stride * es, sh.lpr_shift);
     else
-        hipLaunchKernelGGL(pgm_unpack_kernel<16>, dim3((unsigned)blocks), dim3(kLanes), 0, s, d_payload, (long long)payload_pitch, rowb, height,
-                           nrows, (uint8_t*)d_out, (long long)frame_pitch * es, (long long)stride * es, lpr_shift);
+        hipLaunchKernelGGL(pgm_unpack_kernel<16>, dim3((unsigned)sh.blocks), dim3(kUnpackLanes), 0, s, d_payload, (long long)payload_pitch, rowb, height,
+                           nrows, (uint8_t*)d_out, (long long)frame_pitch * es, (long long)stride * es, sh.lpr_shift);
     MRG_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -202,14 +192,10 @@ int mrgingham_amd_read_pgms_batch(mrgingham_amd_ctx* ctx, const char* const* fil
         return launch_pgm_unpack(ctx, dev, (int64_t)area, n, width, height, bits, (char*)d_out + (size_t)f0 * frame_pitch * es, frame_pitch,
                                  stride, s);
     };
-    // a failed file's area holds whatever the slot held before: its frame is zeroed behind the launch
-    auto after = [&](int, int f0, int n) -> int {
-        for (int i = f0; i < f0 + n; ++i)
-            if (h_status[i] != 0) MRG_HIP_CHECK(zero_frame(d_out, i, frame_pitch, stride, width, height, es, s));
-        return 0;
-    };
-    // the chunk slots are shared with the JPEG and PNG loaders (ctx.h: loader_slot)
-    return loader_ring(ctx, nfiles, chunk, (size_t)chunk * area, (size_t)chunk * area, stage, after, nullptr);
+    // a failed file's area holds whatever the slot held before: its frame is zeroed behind the launch; the chunk slots are
+    // shared with the other loaders (ctx.h: loader_slot)
+    return loader_ring(ctx, nfiles, chunk, (size_t)chunk * area, (size_t)chunk * area, stage,
+                       zero_failed_frames(ctx, d_out, frame_pitch, stride, width, height, es, h_status), nullptr);
 }
 
 }  // extern "C"

@@ -271,7 +271,7 @@ int mrgingham_amd_read_pngs_batch(mrgingham_amd_ctx* ctx, const char* const* fil
         }
         return 0;
     };
-    // the chunk slots are shared with the JPEG loader (ctx.h: loader_slot)
+    // the chunk slots are shared with the other loaders (ctx.h: loader_slot)
     return loader_ring(ctx, nfiles, chunk, (size_t)chunk * area, (size_t)chunk * area, stage, nullptr, nullptr);
 }
 

@@ -5,73 +5,45 @@
 // points and DESIGN.md section 4.20 for the byte model and the numbers.
 #include "ctx.h"
 #include "raw_pixels.h"
+#include "unpack_rows.h"
 
 using namespace mrg;
 
 namespace {
 
-constexpr int kLanes = 256;
-constexpr int kWorkgroupsPerCu = 8;  // eight workgroups of 256 lanes fill a CU
-
-// pnm_unpack_kernel's schedule: a grid-stride loop over the rows of all frames; a row is taken by 2^lpr_shift lanes of a
-// workgroup (256 >> lpr_shift rows side by side), lane l by the words l, l + lanes, ... of the DESTINATION row: consecutive
-// lanes store consecutive 16-byte words.  Word k of a row whose destination begins `ph` bytes behind a 16-byte boundary
-// holds the samples [(16k - ph) / 2, (16k - ph) / 2 + 8) that lie inside the row; a whole word is one 16-byte store (its
-// address is a multiple of 16 by construction), the head and the tail of a row go out sample by sample.  The source row
-// begins at byte y * rowb of the frame's payload, at any phase; word k begins at any bit (streams) or at either sample of
-// a pair.
+// a row of a packed frame: it begins at byte y * rowb of the frame's payload, at any phase; a word begins at any bit
+// (streams) or at either sample of a pair
 template <int FMT>
-__global__ __launch_bounds__(kLanes) void raw_unpack_kernel(const uint8_t* __restrict__ payload, long long payload_pitch, long long rowb, int width,
-                                                            int height, long long nrows, uint8_t* __restrict__ out,
-                                                            long long frame_pitch_b, long long stride_b, int lpr_shift) {
-    const int lanes = 1 << lpr_shift, l = (int)threadIdx.x & (lanes - 1), sub = (int)threadIdx.x >> lpr_shift;
-    const long long rows_per_step = (long long)gridDim.x * (kLanes >> lpr_shift);
-    for (long long row = (long long)blockIdx.x * (kLanes >> lpr_shift) + sub; row < nrows; row += rows_per_step) {
-        const long long f = row / height;
-        const int y = (int)(row - f * height);
-        const uint8_t* base = payload + f * payload_pitch;
-        const long long row_off = (long long)y * rowb;
-        uint8_t* dst = out + f * frame_pitch_b + (long long)y * stride_b;
-        const int ph = (int)((uintptr_t)dst & 15);  // (even)
-        const int K = (ph + width * 2 + 15) >> 4;
-        for (int k = l; k < K; k += lanes) {
-            int x0 = (16 * k - ph) / 2, hi = x0 + 8;  // (16k - ph < 0 only with k == 0: x0 becomes 0 either way)
-            if (x0 < 0) x0 = 0;
-            if (hi > width) hi = width;
-            const int n = hi - x0;
-            uint32_t d[4];
-            raw_pixels<FMT>(base, payload_pitch, row_off, x0, n, d);
-            uint16_t* o = (uint16_t*)dst + x0;
-            if (n == 8) {
-                *(uint4*)o = make_uint4(d[0], d[1], d[2], d[3]);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 7; ++p)
-                    if (p < n) o[p] = (uint16_t)(d[p >> 1] >> (16 * (p & 1)));
-            }
-        }
-    }
+struct RawRows {
+    const uint8_t* __restrict__ payload;
+    long long payload_pitch, rowb;
+    struct Row {
+        const uint8_t* __restrict__ base;
+        long long limit, row_off;
+        __device__ __forceinline__ void pixels(int x0, int n, uint32_t d[4]) const { raw_pixels<FMT>(base, limit, row_off, x0, n, d); }
+    };
+    __device__ __forceinline__ Row row(long long f, int y) const { return Row{payload + f * payload_pitch, payload_pitch, (long long)y * rowb}; }
+};
+
+// unpack_rows.h has the schedule
+template <int FMT>
+__global__ __launch_bounds__(kUnpackLanes) void raw_unpack_kernel(const uint8_t* __restrict__ payload, long long payload_pitch, long long rowb,
+                                                                  int width, int height, long long nrows, uint8_t* __restrict__ out,
+                                                                  long long frame_pitch_b, long long stride_b, int lpr_shift) {
+    unpack_rows<2>(RawRows<FMT>{payload, payload_pitch, rowb}, width, height, nrows, out, frame_pitch_b, stride_b, lpr_shift);
 }
 
 // checked arguments -> the launch (frame_pitch and stride in samples)
 int launch_raw_unpack(mrgingham_amd_ctx* ctx, const uint8_t* d_payload, int64_t payload_pitch, int nframes, int width, int height, int64_t row_bytes,
                       int format, uint16_t* d_out, int64_t frame_pitch, int stride, hipStream_t s) {
     const long long nrows = (long long)nframes * height;
-    // the lanes of a row: the power of two that covers its words (one more where a row can begin inside a word)
-    const bool aligned = !((uintptr_t)d_out & 15) && !((frame_pitch * 2) & 15) && !(((long long)stride * 2) & 15);
-    const int kmax = (width * 2 + 15) / 16 + (aligned ? 0 : 1);
-    int lpr_shift = 0;
-    while ((1 << lpr_shift) < kmax && (1 << lpr_shift) < kLanes) ++lpr_shift;
-    const int rows_per_block = kLanes >> lpr_shift;
-    int cus = 0;
-    MRG_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    long long blocks = (nrows + rows_per_block - 1) / rows_per_block;  // sized to the device
-    if (blocks > (long long)cus * kWorkgroupsPerCu) blocks = (long long)cus * kWorkgroupsPerCu;
+    UnpackShape sh;
+    if (int rc = unpack_launch_shape(ctx, d_out, (long long)frame_pitch * 2, (long long)stride * 2, (long long)width * 2, nrows, &sh)) return rc;
 #define MRG_RAW_LAUNCH(F)                                                                                                                    \
     case F:                                                                                                                                  \
-        hipLaunchKernelGGL((raw_unpack_kernel<F>), dim3((unsigned)blocks), dim3(kLanes), 0, s, d_payload, (long long)payload_pitch,          \
+        hipLaunchKernelGGL((raw_unpack_kernel<F>), dim3((unsigned)sh.blocks), dim3(kUnpackLanes), 0, s, d_payload, (long long)payload_pitch, \
                            (long long)row_bytes, width, height, nrows, (uint8_t*)d_out, (long long)frame_pitch * 2, (long long)stride * 2,   \
-                           lpr_shift);                                                                                                       \
+                           sh.lpr_shift);                                                                                                    \
         break
     switch (format) {
         MRG_RAW_LAUNCH(MRGINGHAM_AMD_RAW_P10);
@@ -90,8 +62,8 @@ int launch_raw_unpack(mrgingham_amd_ctx* ctx, const uint8_t* d_payload, int64_t 
 extern "C" {
 
 void mrgingham_amd_raw_unpack_geometry(int* lanes_per_workgroup, int* max_workgroups_per_cu) {
-    if (lanes_per_workgroup) *lanes_per_workgroup = kLanes;
-    if (max_workgroups_per_cu) *max_workgroups_per_cu = kWorkgroupsPerCu;
+    if (lanes_per_workgroup) *lanes_per_workgroup = kUnpackLanes;
+    if (max_workgroups_per_cu) *max_workgroups_per_cu = kUnpackWorkgroupsPerCu;
 }
 
 int mrgingham_amd_raw_unpack_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_payload, int64_t payload_pitch, int nframes, int width, int height,

@@ -670,7 +670,7 @@ int mrgingham_amd_read_tiffs_batch(mrgingham_amd_ctx* ctx, const char* const* fi
             if (S.file[(size_t)i].kind == 1 && st[i] != 0) h_status[S.f0 + i] = -1;
         return 0;
     };
-    // the chunk slots are shared with the JPEG, PNG and PGM loaders (ctx.h: loader_slot)
+    // the chunk slots are shared with the other loaders (ctx.h: loader_slot)
     return loader_ring(ctx, nfiles, chunk, slot_bytes, slot_bytes, stage, nullptr, finish);
 }
 
