@@ -86,7 +86,10 @@ extern "C" {
  *      Later, additive (the version stays 4): mrgingham_amd_raw_row_bytes, _raw_unpack_image, _raw_unpack_batch,
  *      _raw_unpack_geometry and the MRGINGHAM_AMD_RAW_* formats (packed 10 / 12 / 14-bit camera frames -- Mono10p, Mono12p,
  *      Mono14p, Mono10Packed, Mono12Packed -- to uint16 frames, on the host and on the device).  No earlier call, option
- *      or default changes; no file reader takes such frames (a headerless frame carries no size). */
+ *      or default changes; no file reader takes such frames (a headerless frame carries no size).
+ *      Later, additive (the version stays 4): mrgingham_amd_bayer_grey_image, _bayer_grey_batch, _bayer_grey_geometry and the
+ *      MRGINGHAM_AMD_BAYER_* patterns (Bayer mosaics, uint8 or uint16, to grey frames of the same type, on the host and on
+ *      the device).  No earlier call, option or default changes; no file reader and no tool option takes a mosaic. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -711,7 +714,8 @@ int mrgingham_amd_read_pnms_batch(mrgingham_amd_ctx* ctx, const char* const* fil
  *     bits 2, 3, 6, 7 of byte1 are ignored.  Minimum row_bytes: 3*ceil(width/2).
  * The output is the sample as it is, 0 .. 2^N - 1, in a native uint16_t -- not left-justified (mrgingham_amd_preprocess16_batch
  * normalises by min/max).  Every bit pattern is a valid frame; padding bits and bytes are not looked at.  Rows that begin
- * inside a byte (one bit stream across a whole frame), Bayer mosaics and MSB-first streams are not read. */
+ * inside a byte (one bit stream across a whole frame) and MSB-first streams are not read.  The samples of a colour camera
+ * (BayerRG12p and the like) come out as they are, a mosaic; mrgingham_amd_bayer_grey_batch below takes it to grey. */
 #define MRGINGHAM_AMD_RAW_P10 0
 #define MRGINGHAM_AMD_RAW_P12 1
 #define MRGINGHAM_AMD_RAW_P14 2
@@ -745,6 +749,55 @@ int mrgingham_amd_raw_unpack_batch(mrgingham_amd_ctx* ctx, const uint8_t* d_payl
 
 /* the schedule of that launch, as mrgingham_amd_pnm_unpack_geometry's */
 void mrgingham_amd_raw_unpack_geometry(int* lanes_per_workgroup, int* max_workgroups_per_cu);
+
+/* Bayer mosaics to grey frames, 8 and 16 bit.  The definition, which governs (the names are the common ones):
+ *
+ * Inputs.  A mosaic is height x width samples of one dtype, uint8 or native uint16, any values.  Sides are 2 .. 32767.
+ * The pattern names the colours of pixels (0,0), (0,1), (1,0), (1,1), repeated with period 2 in both directions:
+ *   MRGINGHAM_AMD_BAYER_RGGB 0 (GenICam BayerRG), _GRBG 1 (BayerGR), _GBRG 2 (BayerGB), _BGGR 3 (BayerBG).
+ * Borders.  Samples outside the frame are taken by reflect-101 (index -1 is 1, index n is n-2), which keeps the colour
+ * phase.
+ * Sums.  Let v be the sample at the pixel, and: cross = N + S + W + E; diag = the four diagonal neighbours; hor = W + E;
+ * ver = N + S.
+ * Coefficients.  cR = 4899, cG = 9617, cB = 1868.  They sum to 16384.
+ * Output.  The output has the same dtype as the input.  It is rounded once, in unsigned 32-bit arithmetic:
+ *   red site: (4*cR*v + cG*cross + cB*diag + 32768) >> 16
+ *   blue site: the same with cR and cB exchanged
+ *   green site in a row whose other colour is red: (2*cG*v + cR*hor + cB*ver + 16384) >> 15
+ *   green site in a row whose other colour is blue: the same with cR and cB exchanged
+ * This is bilinear demosaicing followed by the fixed-point luma the colour readers use, folded into one rounding.  The
+ * largest intermediate is 4*16384*65535 + 32768, which is below 2^32.  A constant mosaic comes out unchanged.  Nothing is
+ * edge-aware, white-balanced or colour; 16-bit input gives 16-bit output. */
+#define MRGINGHAM_AMD_BAYER_RGGB 0
+#define MRGINGHAM_AMD_BAYER_GRBG 1
+#define MRGINGHAM_AMD_BAYER_GBRG 2
+#define MRGINGHAM_AMD_BAYER_BGGR 3
+
+/* One mosaic to grey on the HOST (no device needed; the text the kernel runs, csrc/bayer_pixels.h): bits 8 (uint8_t) or 16
+ * (native uint16_t); row y of the mosaic begins at mosaic + y*stride, row y of the output at out + y*out_stride, ELEMENTS,
+ * at any address.  Only the width x height outputs are written.  MRGINGHAM_AMD_ERR_ARG, with nothing written, for a NULL
+ * pointer, a bad pattern, bits outside 8 / 16, sides outside 2 .. 32767 or a stride below the width.  `out` must not
+ * overlap the mosaic.  This is the route a caller without the device call has; it is not a fallback of
+ * mrgingham_amd_bayer_grey_batch. */
+int mrgingham_amd_bayer_grey_image(const void* mosaic, int bits, int width, int height, int64_t stride, int pattern, void* out,
+                                   int64_t out_stride);
+
+/* Mosaics to grey frames on the device: frame f row y at d_in + f*in_frame_pitch + y*in_stride and at
+ * d_out + f*out_frame_pitch + y*out_stride, ELEMENTS of bits / 8 bytes, at any element-aligned address and any stride
+ * >= width (torch views); frames of the output must not overlap each other (out_frame_pitch >= (height-1)*out_stride +
+ * width where nframes > 1), those of the input may.  Only the width x height outputs of a frame are written.  Input and
+ * output must not overlap: the stencil reads its neighbours, so the call cannot work in place.  One streaming launch: a
+ * lane owns a column of 16-byte destination words and rolls down a slab of rows with three source rows in registers;
+ * whole words that are 16-byte aligned leave as one store, the ends of a row and unaligned rows sample by sample.  It reads
+ * the aligned dwords that hold samples of the frames and no others.  Asynchronous on `stream` (NULL = default);
+ * allocates nothing; nframes == 0 is OK.  Every other violation is MRGINGHAM_AMD_ERR_ARG with nothing launched. */
+int mrgingham_amd_bayer_grey_batch(mrgingham_amd_ctx* ctx, const void* d_in, int bits, int nframes, int width, int height,
+                                   int64_t in_frame_pitch, int64_t in_stride, int pattern, void* d_out, int64_t out_frame_pitch,
+                                   int64_t out_stride, void* stream);
+
+/* the schedule of that launch: the lanes of a workgroup (side by side along a row, one 16-byte word each), the rows of a
+ * slab, and the workgroups per CU the grid is capped at (0: it is not capped, one workgroup per slab and span of a row) */
+void mrgingham_amd_bayer_grey_geometry(int* lanes_per_workgroup, int* rows_per_slab, int* max_workgroups_per_cu);
 
 /* TIFF, host half (host only, no device needed): the one parser of a TIFF's first image file directory, behind
  * mrgingham_amd_read_image, _probe_image and _read_tiffs_batch.  `data` is a whole file held in memory.  The subset is

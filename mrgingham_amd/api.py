@@ -429,6 +429,41 @@ def raw_unpack_geometry():
     return a.value, b.value
 
 
+# the Bayer patterns (MRGINGHAM_AMD_BAYER_*): the colours of pixels (0,0), (0,1), (1,0), (1,1); GenICam BayerRG / GR / GB / BG
+BAYER_PATTERNS = {"rggb": 0, "grbg": 1, "gbrg": 2, "bggr": 3}
+
+
+def _bayer_pattern(pattern, who):
+    if not isinstance(pattern, str) or pattern not in BAYER_PATTERNS:
+        raise ValueError(f'{who}: pattern is one of "rggb", "grbg", "gbrg", "bggr"')
+    return BAYER_PATTERNS[pattern]
+
+
+def bayer_grey(image, pattern):
+    """One Bayer mosaic to grey on the host (mrgingham_amd_bayer_grey_image, no device needed): image np.uint8 or np.uint16
+    [H, W], sides 2 .. 32767 -> the same dtype and shape: bilinear demosaicing and the luma 4899 R + 9617 G + 1868 B over
+    16384 in one rounding, borders by reflect-101 (include/mrgingham_amd.h has the definition).  Detector.bayer_grey is
+    the device's route for batches."""
+    p = _bayer_pattern(pattern, "bayer_grey")
+    image = np.asarray(image)
+    if image.dtype not in (np.uint8, np.uint16) or image.ndim != 2:
+        raise ValueError("bayer_grey: image is a uint8 or uint16 [H,W] array")
+    image = np.ascontiguousarray(image)
+    H, W = image.shape
+    out = np.empty((H, W), dtype=image.dtype)
+    if _lib.lib().mrgingham_amd_bayer_grey_image(image.ctypes.data, 8 * image.itemsize, W, H, W, p, out.ctypes.data, W) != 0:
+        raise ValueError("bayer_grey: sides 2 .. 32767")
+    return out
+
+
+def bayer_grey_geometry():
+    """(lanes_per_workgroup, rows_per_slab, max_workgroups_per_cu) of the Bayer launch (mrgingham_amd_bayer_grey_geometry);
+    the last is 0: the grid is not capped."""
+    a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.lib().mrgingham_amd_bayer_grey_geometry(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+    return a.value, b.value, c.value
+
+
 def read_image(filename, cli_scaling=False):
     """Decode a binary PGM, non-interlaced PNG, baseline JPEG, strip or tiled TIFF (uncompressed, LZW, PackBits, Deflate; grey or
     RGB, 8 or 16 bit), Windows Bitmap (1, 4, 8 bit palette, RLE8, 24 and 32 bit; bmp_layout has the subset) or binary PBM or PAM
@@ -1364,6 +1399,36 @@ class Detector:
             self.ctx, payload.data_ptr(), payload.shape[1], payload.shape[0], int(width), int(height), rowb, f, out.data_ptr(), frame_pitch,
             stride, stream))
         return out[:, :, :width]
+
+    def bayer_grey(self, frames, pattern, out=None):
+        """Bayer mosaics to grey frames on the device (mrgingham_amd_bayer_grey_batch), on torch's current stream: frames
+        uint8 or uint16 [B,H,W] device tensor with unit column stride (views with any row and frame stride are taken as
+        they are), sides 2 .. 32767 -> the same dtype and shape.  pattern: "rggb", "grbg", "gbrg", "bggr" (GenICam BayerRG /
+        BayerGR / BayerGB / BayerBG): the colours of pixels (0,0), (0,1), (1,0), (1,1).  Bilinear demosaicing and the luma in
+        one rounding, borders by reflect-101 (include/mrgingham_amd.h has the definition).  `out`: a [B,H,W] device tensor of
+        the same dtype (unit column stride) to write into; it must not overlap `frames`.
+
+            grey = det.bayer_grey(mosaics, "rggb")                      # uint8: straight into find_boards
+            boards, found = det.find_boards(grey, gridn=10)
+            frames = det.raw_unpack(payload, 3072, 4096, "p12")         # BayerRG12p as the grabber wrote it
+            boards, found = det.find_boards(det.preprocess(det.bayer_grey(frames, "rggb")), gridn=10)"""
+        t = self.torch
+        p = _bayer_pattern(pattern, "bayer_grey")
+        if not (t.is_tensor(frames) and frames.is_cuda and frames.dtype in (t.uint8, t.uint16) and frames.dim() == 3
+                and 2 <= frames.shape[1] <= 32767 and 2 <= frames.shape[2] <= 32767 and frames.stride(2) == 1
+                and frames.stride(1) >= frames.shape[2] and frames.stride(0) >= 0):
+            raise ValueError("bayer_grey: frames is a uint8 or uint16 [B,H,W] tensor on the device, sides 2 .. 32767, unit column stride")
+        B, H, W = frames.shape
+        if out is None:
+            out = t.empty((B, H, W), dtype=frames.dtype, device=frames.device)
+        if not (t.is_tensor(out) and out.is_cuda and out.device == frames.device and out.dtype == frames.dtype and tuple(out.shape) == (B, H, W)
+                and out.stride(2) == 1 and out.stride(1) >= W and (B <= 1 or out.stride(0) >= (H - 1) * out.stride(1) + W)):
+            raise ValueError("bayer_grey: out is a [B,H,W] tensor of the frames' dtype on their device with unit column stride, its frames apart")
+        stream = t.cuda.current_stream(frames.device).cuda_stream
+        self._check(self.L.mrgingham_amd_bayer_grey_batch(
+            self.ctx, frames.data_ptr(), 8 * frames.element_size(), B, W, H, frames.stride(0) if B > 1 else 0, frames.stride(1), p,
+            out.data_ptr(), out.stride(0) if B > 1 else 0, out.stride(1), stream))
+        return out
 
     def read_pnms(self, paths, nthreads=0):
         """Binary Netpbm files (P4, P5, P7 in any mix) of one size and output depth straight into device frames

@@ -1,5 +1,6 @@
 // See image_io.h.
 #include "image_io.h"
+#include "bayer_pixels.h"
 #include "bmp_pixels.h"
 #include "jpeg.h"
 #include "png_filter.h"
@@ -1002,6 +1003,19 @@ extern "C" int mrgingham_amd_raw_unpack_image(const uint8_t* payload, size_t nby
             for (int p = 0; p < k; ++p) o[x0 + p] = (uint16_t)(d[p >> 1] >> (16 * (p & 1)));
         }
     }
+    return 0;
+}
+
+// a Bayer mosaic to grey on the host: every word of every row through bayer_pixels.h, the text the device runs
+extern "C" int mrgingham_amd_bayer_grey_image(const void* mosaic, int bits, int width, int height, int64_t stride, int pattern, void* out,
+                                              int64_t out_stride) {
+    if (!mosaic || !out || !mrg::bayer_pattern_ok(pattern) || (bits != 8 && bits != 16) || width < 2 || height < 2 || width > 32767 ||
+        height > 32767 || stride < width || out_stride < width || stride > ((int64_t)1 << 40) || out_stride > ((int64_t)1 << 40))
+        return MRGINGHAM_AMD_ERR_ARG;
+    if (bits == 8)
+        mrg::bayer_grey_rows<1>((const uint8_t*)mosaic, width, height, stride, pattern, (uint8_t*)out, out_stride);
+    else
+        mrg::bayer_grey_rows<2>((const uint8_t*)mosaic, width, height, stride, pattern, (uint8_t*)out, out_stride);
     return 0;
 }
 
