@@ -58,7 +58,7 @@ extern "C" {
  *      Later, additive (the version stays 4: new symbols and a new flag value break no caller): mrgingham_amd_pgm_header,
  *      _pgm_unpack_batch, _read_pgms_batch (binary PGM payloads to frames on the device); option "pgm_chunk_frames"; loader
  *      flag MRGINGHAM_AMD_FILES_DEEP_CHUNKS (16-bit PGM / PNG files in chunks).  Off unless asked for.
- *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (kind 4) read strip TIFF;
+ *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (MRGINGHAM_AMD_KIND_TIFF) read strip TIFF;
  *      mrgingham_amd_tiff_layout, _tiff_decode_batch, _tiff_geometry, _read_tiffs_batch (TIFF: LZW strips, predictor and
  *      grey on the device); options "tiff_chunk_frames", "tiff_lzw_max_strip", "tiff_lzw_lanes";
  *      mrgingham_amd_find_boards_files_ex2 (loader flag MRGINGHAM_AMD_FILES_TIFF_DEVICE).  The device route is off unless
@@ -72,12 +72,12 @@ extern "C" {
  *      LZW and Deflate tiles one lane each, tile rows gathered into image rows on the device); mrgingham_amd_read_image,
  *      _probe_image, _read_tiffs_batch and the file-list entry points read tiled files, which were unreadable before.
  *      mrgingham_amd_tiff_layout and _tiff_layout_ex go on calling any tile tag unreadable, and no option changes.
- *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (kind 5) read Windows Bitmap files,
+ *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (MRGINGHAM_AMD_KIND_BMP) read Windows Bitmap files,
  *      which were unreadable before; mrgingham_amd_bmp_layout, _bmp_unpack_batch, _bmp_unpack_geometry, _read_bmps_batch (BMP:
  *      row order, row padding, sub-byte indices, the palette and grey on the device); options "bmp_chunk_frames",
  *      "bmp_unpack"; mrgingham_amd_find_boards_files_ex4 (loader flag MRGINGHAM_AMD_FILES_BMP_DEVICE, which _ex3 goes on
  *      refusing).  The device route of the file list is off unless asked for.
- *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (kind 6) read binary PBM (P4)
+ *      Later, additive (the version stays 4): mrgingham_amd_read_image and _probe_image (MRGINGHAM_AMD_KIND_PNM) read binary PBM (P4)
  *      and PAM (P7) files, which were unreadable before; mrgingham_amd_pnm_header, _pnm_unpack_batch,
  *      _pnm_unpack_geometry, _read_pnms_batch (colour to grey, big-endian pairs and packed bits on the device); options
  *      "pnm_chunk_frames", "pnm_unpack"; mrgingham_amd_find_boards_files_ex5 (loader flag MRGINGHAM_AMD_FILES_PNM_DEVICE,
@@ -565,7 +565,7 @@ int mrgingham_amd_read_pgms_batch(mrgingham_amd_ctx* ctx, const char* const* fil
                                   int32_t* h_status);
 
 /* Windows Bitmap (BMP), host half (host only, no device needed): the one parser of a BMP's headers and palette, behind
- * mrgingham_amd_read_image, _probe_image (kind 5) and _read_bmps_batch.  `data` is a whole file held in memory.  The subset
+ * mrgingham_amd_read_image, _probe_image (MRGINGHAM_AMD_KIND_BMP) and _read_bmps_batch.  `data` is a whole file held in memory.  The subset
  * is closed, and everything outside it is unreadable; every offset and product is checked in 64 bits against nbytes before
  * anything is sized from it:
  *   a "BM" file header; an info header of 40, 52, 56, 108 or 124 bytes (the 12-byte core header and the 64-byte OS/2 header:
@@ -633,7 +633,7 @@ int mrgingham_amd_read_bmps_batch(mrgingham_amd_ctx* ctx, const char* const* fil
                                   uint8_t* d_out, int64_t frame_pitch, int stride, int nthreads, int32_t* h_status);
 
 /* Binary Netpbm beyond P5 (PBM "P4", PAM "P7"), host half (host only, no device needed): the one parser of a
- * Netpbm header, behind mrgingham_amd_read_image, _probe_image (kind 6) and _read_pnms_batch.  `data` is a whole file held
+ * Netpbm header, behind mrgingham_amd_read_image, _probe_image (MRGINGHAM_AMD_KIND_PNM) and _read_pnms_batch.  `data` is a whole file held
  * in memory, or its first bytes.  The subset is closed, and everything outside it is unreadable:
  *   Sides are 1 .. 32767.  Every product is checked in 64 bits against the file size before anything is sized from it.  A
  *   file shorter than its header promises is unreadable.  Trailing bytes are ignored, as for P5.  Samples are never rescaled
@@ -641,7 +641,7 @@ int mrgingham_amd_read_bmps_batch(mrgingham_amd_ctx* ctx, const char* const* fil
  *   P4: magic, width, height.  White space and # comments are handled as in mrgingham_amd_pgm_header.  ONE white-space byte
  *     follows the last number.  Rows are (width + 7) / 8 bytes, most significant bit first.  Bit 1 is black and reads 0.
  *     Bit 0 reads 255.  Depth is reported as 8.
- *   P5: exactly mrgingham_amd_pgm_header's verdicts and outputs (kind 1, unchanged; the payload is not measured here).
+ *   P5: exactly mrgingham_amd_pgm_header's verdicts and outputs (MRGINGHAM_AMD_KIND_PGM, unchanged; the payload is not measured here).
  *   P6: unreadable, as before (tests/test_pgm_header.py pins such a file); R G B comes as P7 of depth 3.
  *   P7: line 1 is "P7".  Then come lines of WIDTH, HEIGHT, DEPTH, MAXVAL, each followed by a decimal number.  Each must
  *     appear exactly once, in any order.  TUPLTYPE lines may appear any number of times.  # lines and empty lines are
@@ -1032,15 +1032,21 @@ int mrgingham_amd_find_boards_submit_ex(mrgingham_amd_ctx* ctx, const mrgingham_
 
 /* ---- a list of image files to boards ---------------------------------------------------------------------------
  * What mrgingham_amd_read_image would produce for a file, from its header alone (host only, no device needed, nothing
- * is decoded): *width, *height, *bits (8 or 16), *kind (1 binary PGM, 2 PNG, 3 baseline JPEG: the header parse of
- * mrgingham_amd_jpeg_coefficients, up to and including SOS; 4 TIFF: mrgingham_amd_tiff_layout's parse of the directory
- * and the strip table; 5 BMP: mrgingham_amd_bmp_layout's parse of the headers and the palette, from the file's first
+ * is decoded): *width, *height, *bits (8 or 16), *kind (MRGINGHAM_AMD_KIND_*, below: 1 binary PGM, 2 PNG, 3 baseline
+ * JPEG: the header parse of mrgingham_amd_jpeg_coefficients, up to and including SOS; 4 TIFF:
+ * mrgingham_amd_tiff_layout's parse of the directory and the strip table; 5 BMP: mrgingham_amd_bmp_layout's parse of the headers and the palette, from the file's first
  * 4096 bytes and its size -- an RLE8 file is read whole and its stream walked; 6 binary PBM or PAM:
  * mrgingham_amd_pnm_header's parse, bits 8 for P4).  Any output pointer may be NULL.  Returns 0; -1 for what
  * read_image calls unreadable at header level: a missing or empty file, another format, a header that is cut short or
  * breaks a rule (sides above 32767, interlaced PNG, progressive JPEG, ...), a PGM shorter than its header promises.  A
  * file that passes may still fail to decode.  Never sizes anything from an unchecked field. */
 int mrgingham_amd_probe_image(const char* filename, int* width, int* height, int* bits, int* kind);
+#define MRGINGHAM_AMD_KIND_PGM 1
+#define MRGINGHAM_AMD_KIND_PNG 2
+#define MRGINGHAM_AMD_KIND_JPEG 3
+#define MRGINGHAM_AMD_KIND_TIFF 4
+#define MRGINGHAM_AMD_KIND_BMP 5
+#define MRGINGHAM_AMD_KIND_PNM 6
 
 /* How mrgingham_amd_find_boards_files cuts a list into chunks, as a function (host only): key[i] >= 0 -- files of equal
  * key can share a chunk; key[i] < 0 -- the file is not batched (chunk_of_file[i] = slot_in_chunk[i] = -1).  Chunks are
@@ -1151,9 +1157,9 @@ int mrgingham_amd_find_boards_files_ex4(const char* const* filenames, int nfiles
                                         double* stats, int nstats, int loader_flags);
 
 /* mrgingham_amd_find_boards_files_ex4 with one more loader flag (which _ex4 goes on refusing).  Without it P4 and P7
- * files (kind 6) behave as PGM files do: 8-bit files of one size share chunks and are decoded by the loader's host threads
+ * files (MRGINGHAM_AMD_KIND_PNM) behave as PGM files do: 8-bit files of one size share chunks and are decoded by the loader's host threads
  * (MRGINGHAM_AMD_FILES_HOST_DECODED); 16-bit ones take the one-image path, or with MRGINGHAM_AMD_FILES_DEEP_CHUNKS the
- * 16-bit chunks.  MRGINGHAM_AMD_FILES_PNM_DEVICE: runs of consecutive kind-6 slots of a chunk go through
+ * 16-bit chunks.  MRGINGHAM_AMD_FILES_PNM_DEVICE: runs of consecutive MRGINGHAM_AMD_KIND_PNM slots of a chunk go through
  * mrgingham_amd_read_pnms_batch on the loader context and are counted under MRGINGHAM_AMD_FILES_DEVICE_LOADED.  P5 files keep
  * their routes and counters under every flag.  Same outputs.  Any bit above the six flags is MRGINGHAM_AMD_ERR_ARG. */
 #define MRGINGHAM_AMD_FILES_PNM_DEVICE 32

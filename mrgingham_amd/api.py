@@ -484,10 +484,15 @@ def read_image(filename, cli_scaling=False):
     return out
 
 
+# probe_image's kinds (MRGINGHAM_AMD_KIND_* of include/mrgingham_amd.h)
+KIND_PGM, KIND_PNG, KIND_JPEG, KIND_TIFF, KIND_BMP, KIND_PNM = 1, 2, 3, 4, 5, 6
+
+
 def probe_image(filename):
     """What read_image would produce for the file, from its header alone (mrgingham_amd_probe_image; host only, nothing is
-    decoded): (height, width, bits, kind) with kind 1 binary PGM, 2 PNG, 3 baseline JPEG, 4 TIFF, 5 BMP (always 8 bits: the
-    grey read_image gives; the stream of an RLE8 file is walked), 6 binary PBM or PAM (8 bits for PBM); None for a file that is unreadable at header level."""
+    decoded): (height, width, bits, kind) with kind KIND_PGM binary PGM, KIND_PNG, KIND_JPEG baseline JPEG, KIND_TIFF, KIND_BMP
+    (always 8 bits: the grey read_image gives; the stream of an RLE8 file is walked), KIND_PNM binary PBM or PAM (8 bits for
+    PBM); None for a file that is unreadable at header level."""
     w, h, b, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     if _lib.lib().mrgingham_amd_probe_image(os.fsencode(filename), ctypes.byref(w), ctypes.byref(h), ctypes.byref(b),
                                             ctypes.byref(k)) != 0:
@@ -1343,7 +1348,7 @@ class Detector:
         H = W = 0
         for name in names:
             probe = probe_image(name)
-            if probe is not None and probe[3] == 5:
+            if probe is not None and probe[3] == KIND_BMP:
                 H, W = probe[0], probe[1]
                 break
         return self._read_files(self.L.mrgingham_amd_read_bmps_batch, names, H, W, 8, nthreads, False)
@@ -1442,7 +1447,7 @@ class Detector:
         bits = 8
         for name in names:
             probe = probe_image(name)
-            if probe is not None and probe[3] in (1, 6):
+            if probe is not None and probe[3] in (KIND_PGM, KIND_PNM):
                 H, W, bits = probe[0], probe[1], probe[2]
                 break
         return self._read_files(self.L.mrgingham_amd_read_pnms_batch, names, H, W, bits, nthreads, True)
@@ -1509,7 +1514,7 @@ class Detector:
         bits = 8
         for p in paths:
             head = probe_image(p)
-            if head is not None and head[3] == 4:
+            if head is not None and head[3] == KIND_TIFF:
                 H, W, bits, _ = head
                 break
         return self._read_files(self.L.mrgingham_amd_read_tiffs_batch, names, H, W, bits, nthreads, True)

@@ -1,5 +1,5 @@
 // Stand-alone driver of the host half of the Bayer mosaics for tests/test_bayer.py: built with
-// -fsanitize=address,undefined together with csrc/image_io.cpp and csrc/jpeg.cpp.  Every shape, pattern and sample width,
+// -fsanitize=address,undefined together with the host readers (tests/host_program.py).  Every shape, pattern and sample width,
 // the mosaic of random samples in a heap buffer of EXACTLY the bytes the arguments describe -- (height-1)*stride + width
 // samples -- that ends where the allocation ends and begins at each of the four byte phases of a dword (dense rows at the
 // even phases, rows with a stride of their own at the odd ones), and the output in such a buffer too: bayer_pixels.h

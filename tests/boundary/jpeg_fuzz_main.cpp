@@ -1,5 +1,5 @@
 // Stand-alone driver of the host JPEG decoder for tests/test_jpeg_io.py: built with -fsanitize=address,undefined together
-// with csrc/jpeg.cpp and csrc/image_io.cpp, it walks a corpus of truncated and corrupted files
+// with the host readers (tests/host_program.py), it walks a corpus of truncated and corrupted files
 //   corpus file: u32 count, then per case u32 length + bytes (little endian)
 // through mrg::jpeg_coefficients (header only, then into a buffer of exactly the reported size), mrg::jpeg_idct_host and,
 // by way of a scratch file, mrg::read_image.  Prints "cases N readable M"; any sanitizer report ends it with a failure.

@@ -1,5 +1,5 @@
 // Stand-alone driver of the PGM header parser for tests/test_pgm_header.py: built with -fsanitize=address,undefined
-// together with csrc/image_io.cpp and csrc/jpeg.cpp.  From one good 16-bit PGM file it makes every truncation and, for
+// together with the host readers (tests/host_program.py).  From one good 16-bit PGM file it makes every truncation and, for
 // every byte of the header, a handful of single-byte corruptions; each case goes through mrg::pgm_header in a heap
 // buffer of exactly its size (a read behind it is a sanitizer report) and, by way of a scratch file, through
 // mrg::read_image and mrg::probe_image, whose verdicts must be the parser's: readable when the header is good and the

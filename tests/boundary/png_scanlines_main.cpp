@@ -1,5 +1,5 @@
 // Stand-alone driver of the host half of the PNG device route for tests/test_png_scanlines.py: built with
-// -fsanitize=address,undefined together with csrc/image_io.cpp and csrc/jpeg.cpp, it walks a corpus of good, crafted and
+// -fsanitize=address,undefined together with the host readers (tests/host_program.py), it walks a corpus of good, crafted and
 // cut-off PNG files
 //   corpus file: u32 count, then per case u32 length + bytes (little endian)
 // through mrg::png_scanlines -- sizes only, then into a heap buffer of exactly the reported size (one byte more would be

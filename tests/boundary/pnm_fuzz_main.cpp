@@ -1,5 +1,5 @@
 // Stand-alone driver of the host Netpbm reader for tests/test_pnm_io.py: built with -fsanitize=address,undefined together
-// with csrc/image_io.cpp and csrc/jpeg.cpp, it walks a corpus of good, broken and mutated files
+// with the host readers (tests/host_program.py), it walks a corpus of good, broken and mutated files
 //   corpus file: u32 count, then per case u32 length + bytes (little endian)
 // through mrg::pnm_header (the whole file, and its first 4096 bytes with the file's size, as probe_image sees it) and, by
 // way of a scratch file, mrg::read_image and mrg::probe_image, which must agree with it.  Every P4 / P7 file that is

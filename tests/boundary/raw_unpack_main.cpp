@@ -1,5 +1,5 @@
 // Stand-alone driver of the host half of the packed camera formats for tests/test_raw_unpack.py: built with
-// -fsanitize=address,undefined together with csrc/image_io.cpp and csrc/jpeg.cpp.  Every format over a list of shapes, at
+// -fsanitize=address,undefined together with the host readers (tests/host_program.py).  Every format over a list of shapes, at
 // the minimum row_bytes, with 3 bytes of row padding and with a few more, the payload of random bytes in a heap buffer of
 // EXACTLY nbytes = (height-1)*row_bytes + minimum that ends where the allocation ends (and begins at each of the four
 // byte phases of a dword): raw_pixels.h loads aligned dwords, and the guard on the last one -- of which only the bytes

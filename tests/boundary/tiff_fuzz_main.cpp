@@ -1,5 +1,5 @@
 // Stand-alone driver of the host TIFF reader for tests/test_tiff_io.py: built with -fsanitize=address,undefined together
-// with csrc/image_io.cpp and csrc/jpeg.cpp, it walks a corpus of good, broken and mutated files
+// with the host readers (tests/host_program.py), it walks a corpus of good, broken and mutated files
 //   corpus file: u32 count, then per case u32 length + bytes (little endian)
 // through mrg::tiff_layout (counts only, then into an array of exactly the reported size and into one a record short),
 // the shared strip decoder of csrc/tiff_lzw.h -- with the host's table and with the packed table the kernel uses, the

@@ -1,5 +1,5 @@
 // Stand-alone driver of the tiled TIFF reader for tests/test_tiff_tiles.py: built with -fsanitize=address,undefined together
-// with csrc/image_io.cpp and csrc/jpeg.cpp, it walks a corpus of good, broken, truncated and mutated tiled files
+// with the host readers (tests/host_program.py), it walks a corpus of good, broken, truncated and mutated tiled files
 //   corpus file: u32 count, then per case u32 length + bytes (little endian)
 // through mrg::tiff_layout_tiled (counts only, then into an array of exactly the reported size and into one a record short,
 // with the limits of the device route off and on), and, by way of a scratch file, mrg::probe_image and mrg::read_image.

@@ -31,7 +31,7 @@ class CliOptions(ctypes.Structure):
 def decode(path):
     """The decoder's image as the tool hands it to the one-image path: uint8 or uint16 [H, W], or None."""
     probe = mrgingham_amd.probe_image(path)
-    if probe is not None and probe[2] == 16 and probe[3] == 1:            # 16-bit PGM: the samples as they are
+    if probe is not None and probe[2] == 16 and probe[3] == mrgingham_amd.KIND_PGM:            # 16-bit PGM: the samples as they are
         data = open(path, "rb").read()
         h, w = probe[0], probe[1]
         return np.frombuffer(data[len(data) - 2 * h * w:], ">u2").reshape(h, w).astype(np.uint16)

@@ -3,7 +3,6 @@ no GPU: against the numpy yardstick of tests/bayer_cases.py, which is first held
 definition, and through a stand-alone program under the address and undefined-behaviour sanitizers.  The definition is
 integer: np.array_equal everywhere, no tolerance."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -12,9 +11,7 @@ import pytest
 import mrgingham_amd
 from mrgingham_amd import _lib, synth
 from tests import bayer_cases as bc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrgingham_amd", "csrc")
+from tests.host_program import build_sanitized
 
 
 def _image(m, pat, stride=None, out_stride=None):
@@ -110,20 +107,10 @@ def test_patterns_exports_and_abi():
 
 
 def test_host_entry_under_address_and_undefined_sanitizers(tmp_path):
-    """csrc/image_io.cpp + jpeg.cpp built with -fsanitize=address,undefined into a stand-alone program
+    """the host readers (tests/host_program.py) built with -fsanitize=address,undefined into a stand-alone program
     (tests/boundary/bayer_main.cpp), run as a child process: the host entry on heap buffers of exactly the bytes the
     arguments describe, at all four byte phases, against a per-pixel decoder written from the definition."""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
-        pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "bayer")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "bayer_main.cpp"),
-                        os.path.join(CSRC, "jpeg.cpp"), os.path.join(CSRC, "image_io.cpp"), "-lz", "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_sanitized(tmp_path, "bayer_main.cpp")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stderr == "", (r.stdout, r.stderr[-4000:])
     words = r.stdout.split()

@@ -13,9 +13,9 @@ import pytest
 
 import mrgingham_amd
 from tests import bmp_cases as bc
+from tests.host_program import build_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrgingham_amd", "csrc")
 WIDTHS = (1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 33, 65)
 HEIGHTS = (1, 2, 5)
 
@@ -244,20 +244,10 @@ def corpus():
 
 
 def test_corpus_and_pixel_text_under_address_and_undefined_sanitizers(tmp_path):
-    """The corpus through csrc/image_io.cpp + jpeg.cpp built with -fsanitize=address,undefined into a stand-alone program
+    """The corpus through the host readers (tests/host_program.py) built with -fsanitize=address,undefined into a stand-alone program
     (tests/boundary/bmp_fuzz_main.cpp), run as a child process: read_image, probe_image and bmp_layout on every case, and
     bmp_pixels.h on source rows held in buffers of exactly the padded row length."""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
-        pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "bmp_fuzz")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "bmp_fuzz_main.cpp"),
-                        os.path.join(CSRC, "jpeg.cpp"), os.path.join(CSRC, "image_io.cpp"), "-lz", "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_sanitized(tmp_path, "bmp_fuzz_main.cpp")
     items = corpus()
     assert len(items) > 2000
     blob = tmp_path / "corpus.bin"

@@ -7,12 +7,11 @@ import struct
 import subprocess
 
 import numpy as np
-import pytest
 
 import mrgingham_amd
+from tests.host_program import build_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrgingham_amd", "csrc")
 
 
 class Case:
@@ -210,19 +209,9 @@ def test_malformed_jpeg_files_are_unreadable(tmp_path):
 
 
 def test_corpus_under_address_and_undefined_sanitizers(tmp_path):
-    """The same corpus through csrc/jpeg.cpp + image_io.cpp built with -fsanitize=address,undefined into a stand-alone
+    """The same corpus through the host readers (tests/host_program.py) built with -fsanitize=address,undefined into a stand-alone
     program (tests/boundary/jpeg_fuzz_main.cpp), run as a child process."""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
-        pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "jpeg_fuzz")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "jpeg_fuzz_main.cpp"),
-                        os.path.join(CSRC, "jpeg.cpp"), os.path.join(CSRC, "image_io.cpp"), "-lz", "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_sanitized(tmp_path, "jpeg_fuzz_main.cpp")
     items = corpus()
     blob = tmp_path / "corpus.bin"
     with open(blob, "wb") as f:

@@ -13,9 +13,7 @@ import pytest
 import mrgingham_amd
 from mrgingham_amd import _lib
 from tests import files_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrgingham_amd", "csrc")
+from tests.host_program import build_sanitized
 
 
 def test_loader_flags_of_find_boards_files_ex():
@@ -115,18 +113,9 @@ def test_the_offset_is_where_the_samples_begin(tmp_path):
 
 
 def test_header_program_under_sanitizers(tmp_path):
-    """tests/boundary/pgm_header_main.cpp with csrc/image_io.cpp, as a program of its own: every truncation of a good
+    """tests/boundary/pgm_header_main.cpp with the host readers (tests/host_program.py), as a program of its own: every truncation of a good
     16-bit file and several hundred single-byte corruptions of its header."""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
-        pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "pgm_header")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "pgm_header_main.cpp"),
-                        os.path.join(CSRC, "image_io.cpp"), os.path.join(CSRC, "jpeg.cpp"), "-lz", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_sanitized(tmp_path, "pgm_header_main.cpp")
     head = b"P5\n# a comment, then the sizes\n12 7 # and one more\n65535\n"
     good = tmp_path / "good16.pgm"
     good.write_bytes(head + np.arange(12 * 7, dtype=">u2").tobytes())

@@ -2,7 +2,6 @@
 inflated, still filtered scanlines of every pixel size the device takes, the sizes, the palette code, and the files that
 break a rule -- each judged exactly as read_image judges it.  tests/boundary/png_scanlines_main.cpp walks the same files
 under the address and undefined-behaviour sanitizers as a program of its own."""
-import os
 import struct
 import subprocess
 
@@ -11,9 +10,7 @@ import pytest
 
 import mrgingham_amd
 from tests import png_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrgingham_amd", "csrc")
+from tests.host_program import build_sanitized
 
 
 def palette_file():
@@ -91,18 +88,9 @@ def test_unreadable_like_read_image(tmp_path, name):
 
 
 def test_scanlines_program_under_sanitizers(tmp_path):
-    """tests/boundary/png_scanlines_main.cpp with csrc/image_io.cpp, as a program of its own: every file of this module, and
+    """tests/boundary/png_scanlines_main.cpp with the host readers (tests/host_program.py), as a program of its own: every file of this module, and
     the good ones cut off at a spread of lengths."""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
-        pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "png_scanlines")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "png_scanlines_main.cpp"),
-                        os.path.join(CSRC, "image_io.cpp"), os.path.join(CSRC, "jpeg.cpp"), "-lz", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_sanitized(tmp_path, "png_scanlines_main.cpp")
     good = [GOOD, palette_file()[0]]
     for color_type, bits in png_cases.TAKEN:
         good.append(png_cases.encode(png_cases.random_image(21, 13, color_type, bits), color_type, bits, filters=("random", 1), nidat=3)[0])

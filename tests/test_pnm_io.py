@@ -21,9 +21,9 @@ import mrgingham_amd
 from mrgingham_amd import _lib
 from tests import pnm_cases as pc
 from tests.test_pgm_header import _cases as pgm_cases
+from tests.host_program import build_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrgingham_amd", "csrc")
 CUT = mrgingham_amd.PGM_HEADER_CUT
 
 
@@ -307,20 +307,10 @@ def corpus():
 
 
 def test_corpus_and_pixel_text_under_address_and_undefined_sanitizers(tmp_path):
-    """The corpus through csrc/image_io.cpp + jpeg.cpp built with -fsanitize=address,undefined into a stand-alone program
+    """The corpus through the host readers (tests/host_program.py) built with -fsanitize=address,undefined into a stand-alone program
     (tests/boundary/pnm_fuzz_main.cpp), run as a child process: read_image, probe_image and pnm_header on every case, and
     pnm_pixels.h on rasters held in heap buffers of exactly the payload's padded size."""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
-        pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "pnm_fuzz")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "pnm_fuzz_main.cpp"),
-                        os.path.join(CSRC, "jpeg.cpp"), os.path.join(CSRC, "image_io.cpp"), "-lz", "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_sanitized(tmp_path, "pnm_fuzz_main.cpp")
     items = corpus()
     assert len(items) > 2000
     blob = tmp_path / "corpus.bin"

@@ -3,7 +3,6 @@ the text the kernel runs), no GPU: against the numpy packer and yardstick of tes
 against the known answers of the format definitions, and through a stand-alone program under the address and
 undefined-behaviour sanitizers.  The formats are lossless bit layouts: np.array_equal everywhere, no tolerance."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -12,9 +11,7 @@ import pytest
 import mrgingham_amd
 from mrgingham_amd import _lib
 from tests import raw_cases as rc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrgingham_amd", "csrc")
+from tests.host_program import build_sanitized
 
 
 def test_the_packer_gives_the_known_answers():
@@ -133,20 +130,10 @@ def test_geometry_and_abi():
 
 
 def test_host_entry_under_address_and_undefined_sanitizers(tmp_path):
-    """csrc/image_io.cpp + jpeg.cpp built with -fsanitize=address,undefined into a stand-alone program
+    """the host readers (tests/host_program.py) built with -fsanitize=address,undefined into a stand-alone program
     (tests/boundary/raw_unpack_main.cpp), run as a child process: the host entry and the pixel text on payloads held in
     heap buffers of exactly nbytes, against a bit-by-bit decoder."""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
-        pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "raw_unpack")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "raw_unpack_main.cpp"),
-                        os.path.join(CSRC, "jpeg.cpp"), os.path.join(CSRC, "image_io.cpp"), "-lz", "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_sanitized(tmp_path, "raw_unpack_main.cpp")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stderr == "", (r.stdout, r.stderr[-4000:])
     words = r.stdout.split()

@@ -4,7 +4,6 @@ laid out, the return code (0: the device route takes the file) against the state
 writer against Pillow's libtiff, and the corpus with truncations and directory mutations through a stand-alone program
 under the address and undefined-behaviour sanitizers."""
 import io
-import os
 import struct
 import subprocess
 
@@ -14,9 +13,8 @@ import pytest
 import mrgingham_amd
 from tests import tiff_cases as tc
 from tests import tiff_tile_cases as tt
+from tests.host_program import build_sanitized
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mrgingham_amd", "csrc")
 CODECS = (tt.NONE, tt.LZW, tt.PACKBITS, tt.ADOBE_DEFLATE, tt.DEFLATE)
 
 
@@ -228,20 +226,10 @@ def corpus():
 
 
 def test_corpus_under_address_and_undefined_sanitizers(tmp_path):
-    """The corpus through csrc/image_io.cpp + jpeg.cpp built with -fsanitize=address,undefined into a stand-alone program
+    """The corpus through the host readers (tests/host_program.py) built with -fsanitize=address,undefined into a stand-alone program
     (tests/boundary/tiff_tiles_fuzz_main.cpp), run as a child process: tiff_layout_tiled, probe_image and read_image on
     buffers of exact size.  It must not crash, and probe and read agree with the parser at header level."""
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    r = subprocess.run(["g++", *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")]).returncode != 0:
-        pytest.skip("the sanitizer runtime of g++ is not installed")
-    exe = str(tmp_path / "tiff_tiles_fuzz")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", *flags, "-I", CSRC, os.path.join(ROOT, "tests", "boundary", "tiff_tiles_fuzz_main.cpp"),
-                        os.path.join(CSRC, "jpeg.cpp"), os.path.join(CSRC, "image_io.cpp"), "-lz", "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_sanitized(tmp_path, "tiff_tiles_fuzz_main.cpp")
     items = corpus()
     assert len(items) > 4000
     blob = tmp_path / "corpus.bin"

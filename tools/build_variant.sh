@@ -12,5 +12,6 @@ EXTRA=""; [ "$NAME" = chess ] && EXTRA="-mllvm -amdgpu-sched-strategy=max-ilp"
 rm -f $R/mrgingham_amd/csrc/_variant_$NAME.hip
 OBJS=""
 for n in $(make -s -C $R/mrgingham_amd/csrc print-srcs); do n=${n%.hip}; if [ $n = $NAME ]; then OBJS="$OBJS /tmp/_variant_$NAME.o"; else OBJS="$OBJS $B/$n.o"; fi; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJS $B/grid.o $B/image_io.o -lz -ldl
+for n in $(make -s -C $R/mrgingham_amd/csrc print-host-srcs); do OBJS="$OBJS $B/${n%.cpp}.o"; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $OBJS $B/grid.o -lz -ldl
 echo built $OUT
