@@ -1394,8 +1394,10 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
 int mrgingham_amd_sync(mrgingham_amd_ctx* ctx);
 
 /* Device-side alternative to mrgingham_amd_sync for pipelines: makes `stream` (a hipStream_t,
- * NULL = the default stream) wait for the most recently queued detect / refine / chain call,
- * without blocking the host.  Consecutive calls overlap (the pixel kernels of call N+1 run while
+ * NULL = the default stream) wait for EVERY detect / refine / chain call queued so far and not yet
+ * waited for by mrgingham_amd_sync -- consecutive calls finish on different component streams, so the
+ * wait is for each scratch set with a call in flight, not for the last call alone -- without
+ * blocking the host.  Consecutive calls overlap (the pixel kernels of call N+1 run while
  * the component kernels of call N finish, on alternating scratch sets), so give each call in
  * flight its own output buffers. */
 int mrgingham_amd_stream_wait(mrgingham_amd_ctx* ctx, void* stream);

@@ -876,14 +876,18 @@ class Detector:
         self._check(self.L.mrgingham_amd_sync(self.ctx))
 
     def stream_wait(self, stream=None):
-        """Make a torch stream (default: the current one) wait for the last queued call, on the device."""
+        """Make a torch stream (default: the current one) wait, on the device, for every call queued so far (all of
+        them, not the last alone: consecutive calls finish on different streams of the context)."""
         t = self.torch
         st = t.cuda.current_stream(self.device) if stream is None else stream
         self._check(self.L.mrgingham_amd_stream_wait(self.ctx, st.cuda_stream))
 
     def after_stream(self, stream=None):
         """The next queued call starts after what is queued so far on a torch stream (default: the
-        current one), e.g. the upload of its frames; on the device, the host is not blocked."""
+        current one), e.g. the upload of its frames; on the device, the host is not blocked.  Several calls, one per
+        stream, before one queued call are all honoured.  The calls that do not wait for torch's stream themselves --
+        detect(out=) and chain(out=) -- need this whenever torch work still queued wrote their frames or touches
+        their buffers."""
         t = self.torch
         st = t.cuda.current_stream(self.device) if stream is None else stream
         self._check(self.L.mrgingham_amd_after_stream(self.ctx, st.cuda_stream))
@@ -946,7 +950,15 @@ class Detector:
     def detect(self, frames, level, capacity=4096, sync=True, retry=True, out=None):
         """-> (xy int32 [B,capacity,2], counts int32 [B]) on the device.  sync=True waits for the result and, with
         retry, repeats the call when a frame overflowed the (self-growing) component tables.  `out` = (xy, counts) of an
-        earlier call to write into (a pipelined caller rotates a few: no allocation, no stream synchronisation per call)."""
+        earlier call to write into (a pipelined caller rotates a few: no allocation, no stream synchronisation per call).
+
+        The caller's duty on the `out=` path: the call runs on the context's own streams and does NOT wait for torch's.
+        Frames that torch work still queued produces (a non-blocking upload, preprocessing), and `out` buffers such work
+        still reads or writes, need `after_stream()` (for each torch stream involved) BEFORE this call; it is not made
+        here because a pipelined step has just told torch's stream to wait for the step before (stream_wait), and a wait
+        for that stream would queue this step behind it.  With sync=False, whoever reads xy / counts needs
+        `stream_wait()` (a torch stream, on the device) or `sync()` (the host) first.  Calls queued on one Detector
+        that share a buffer run in the order they were made."""
         t = self.torch
         fr, B, H, W = self._frames(frames)
         if out is None:
@@ -968,7 +980,12 @@ class Detector:
         return xy, counts
 
     def refine(self, frames, level, points, levels, npoints, sync=True, retry=True):
-        """In-place refine of points f64 [B,P,2], levels int8 [B,P], npoints int32 [B]; -> nrefined int32 [B]."""
+        """In-place refine of points f64 [B,P,2], levels int8 [B,P], npoints int32 [B]; -> nrefined int32 [B].
+
+        The call waits (on the host) for torch's CURRENT stream before it is queued: frames and points written there are
+        complete.  What another torch stream still writes needs `after_stream(that stream)` first.  With sync=False the
+        points, levels and nrefined are final only behind `stream_wait()` or `sync()`; a later queued call on the same
+        buffers (the next level's refine, a chain into them) is ordered behind this one by the library."""
         t = self.torch
         fr, B, H, W = self._frames(frames)
         assert points.dtype == t.float64 and points.is_contiguous() and levels.dtype == t.int8
@@ -991,7 +1008,12 @@ class Detector:
         return nref
 
     def chain(self, frames, start_level=3, max_points=1024, out=None, sync=True, retry=True):
-        """detect at start_level, refine down to 0 -> (points f64 [B,P,2], levels int8 [B,P], npoints int32 [B])."""
+        """detect at start_level, refine down to 0 -> (points f64 [B,P,2], levels int8 [B,P], npoints int32 [B]).
+
+        `out` = (points, levels, npoints) to write into.  As for detect(out=): that path does not wait for torch's stream,
+        so frames or `out` buffers that queued torch work still writes or reads need `after_stream()` before the call
+        (it is not made here: in a pipelined step torch's stream already waits for the step before, and this step would
+        queue behind it); with sync=False a consumer needs `stream_wait()` or `sync()` before it reads the outputs."""
         t = self.torch
         fr, B, H, W = self._frames(frames)
         if out is None:

@@ -71,8 +71,9 @@ void begin_op(mrgingham_amd_ctx* ctx, int max_level) {
     // and clears them.)
 }
 // Registers the caller-owned device buffers this call writes (w) and reads (r) and makes its
-// component stream wait for the previous call (which runs on the OTHER component stream) when
-// they overlap anything that call wrote or read-then-we-write.  Call after begin_op.
+// component stream wait for every earlier call still pending on ANOTHER scratch set (each set has a
+// component stream of its own; the set's own earlier call is ordered by the stream) whose written
+// spans overlap what this call reads or writes, or whose read spans overlap what it writes.  Call after begin_op.
 void order_after_previous(mrgingham_amd_ctx* ctx, std::initializer_list<mrgingham_amd_ctx::Span> w,
                           std::initializer_list<mrgingham_amd_ctx::Span> r) {
     const int cur = ctx->cur;

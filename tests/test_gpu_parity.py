@@ -473,7 +473,9 @@ def test_dependent_calls_without_sync_are_ordered(det):
         torch.cuda.synchronize()
         det.refine(frames, 1, p, l, npts, sync=False)
         det.refine(frames, 0, p, l, npts, sync=False)       # reads what the call before wrote
-        out2 = det.chain(frames, 2, 256, out=(p.clone(), l.clone(), npts.clone()), sync=False)  # unrelated buffers
+        fresh = (p.clone(), l.clone(), npts.clone())        # unrelated buffers, written by torch's stream:
+        det.after_stream()                                  # the chain starts behind those writes
+        out2 = det.chain(frames, 2, 256, out=fresh, sync=False)
         det.sync()
         for f in range(4):
             k = int(rn[f])
