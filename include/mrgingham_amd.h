@@ -1377,12 +1377,21 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         _process_image_ex): 1 = three passes over the pixels (extrema, raw-value tile histograms,
  *                         blend + blur), 0 = the one-image kernels (normalised 16-bit copy, 65 536-bin tables per tile,
  *                         then the box blur as its own kernel).  Same bytes.
+ *   "scratch_fill"        test hook: -1 (default) = off; 0..255: every new allocation of context memory (device and page-locked)
+ *                         is filled with that byte before it is used.  A context starts with the value of the environment
+ *                         variable MRGINGHAM_AMD_SCRATCH_FILL (decimal or 0x..; unset, empty or no byte: off) -- the way to
+ *                         reach the contexts behind the reference's own names and inside mrgingham_amd_find_boards_files.
+ *                         Results never depend on it: no call reads scratch it has not written.
+ *   "scratch_fill_now"    test hook, a one-shot: completes what is in flight, then fills every scratch buffer the context
+ *                         owns with the byte given (0..255) -- not the few words that are state between calls (status
+ *                         and hot-count words, the sparse-fallback counter, the clock probe's sums).  Results never depend on it.
  * Builds made with -DMRG_EXPERIMENT (make -C mrgingham_amd/csrc EXPERIMENT=1 -> libmrgingham_amd_experiment.so)
  * additionally accept the timing ablations and phase clocks of tools/ ("cc_lds" bits 2, 4, 8, 16, 128, 512,
  * "cc_schedule", "chess_stage", "chess_multi_min_blocks", "chess_v0" = the reference-shaped ChESS kernel as an on-device
  * cross-check, the MRGINGHAM_AMD_PYR_SKIP / _CC_LDS_PAD / _CC_CUS /
  * _PIX_COMPLEMENT / _CHESS_V0 environment variables): some of them produce wrong results on purpose, which is why the
- * shipped library has none of them and reads no environment variable except MRGINGHAM_AMD_DEVICE. */
+ * shipped library has none of them and reads no environment variable except MRGINGHAM_AMD_DEVICE and the test hook
+ * MRGINGHAM_AMD_SCRATCH_FILL, which changes no result. */
 int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value);
 
 /* Wait for everything queued on the context's streams; returns the first

@@ -27,6 +27,14 @@ int fail_hip(mrgingham_amd_ctx* ctx, hipError_t e, const char* what, const char*
     return fail(ctx, MRGINGHAM_AMD_ERR_DEVICE, "%s:%d: %s failed: %s", file, line, what, hipGetErrorString(e));
 }
 
+int scratch_fill_from_env() {
+    const char* e = getenv("MRGINGHAM_AMD_SCRATCH_FILL");
+    if (!e || !*e) return -1;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 0);
+    return (end == e || *end || v < 0 || v > 255) ? -1 : (int)v;
+}
+
 int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes) {
     if (bytes <= b.bytes) return 0;
     if (b.p) {
@@ -42,6 +50,14 @@ int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes) {
     MRG_HIP_CHECK(hipMalloc(&b.p, want));
     b.bytes = want;
     ctx->scratch_total += (long long)want;
+    // (what set_option "scratch_fill_now" walks: a buffer is noted once, its address is a member's)
+    bool noted = false;
+    for (const DevBuf* q : ctx->scratch_bufs) noted = noted || q == &b;
+    if (!noted) ctx->scratch_bufs.push_back(&b);
+    if (ctx->scratch_fill >= 0) {  // (complete before whatever the caller queues on the context's streams, which do not wait for the null stream)
+        MRG_HIP_CHECK(hipMemset(b.p, ctx->scratch_fill, want));
+        MRG_HIP_CHECK(hipDeviceSynchronize());
+    }
     return 0;
 }
 
@@ -54,7 +70,7 @@ void release(mrgingham_amd_ctx* ctx, DevBuf& b) {
 }
 
 // (the step of ensure_pinned, for the one caller that goes on without the memory: ensure_level_set)
-static hipError_t grow_pinned(PinBuf& b, size_t bytes, int slack_divisor, bool zero_on_growth) {
+static hipError_t grow_pinned(mrgingham_amd_ctx* ctx, PinBuf& b, size_t bytes, int slack_divisor, bool zero_on_growth) {
     if (bytes <= b.bytes) return hipSuccess;
     if (b.p) {
         const hipError_t e = hipHostFree(b.p);
@@ -69,12 +85,16 @@ static hipError_t grow_pinned(PinBuf& b, size_t bytes, int slack_divisor, bool z
         return e;
     }
     b.bytes = want;
-    if (zero_on_growth) memset(b.p, 0, want);
+    bool noted = false;
+    for (const PinBuf* q : ctx->pinned_bufs) noted = noted || q == &b;
+    if (!noted) ctx->pinned_bufs.push_back(&b);
+    if (ctx->scratch_fill >= 0) memset(b.p, ctx->scratch_fill, want);
+    else if (zero_on_growth) memset(b.p, 0, want);
     return hipSuccess;
 }
 
 int ensure_pinned(mrgingham_amd_ctx* ctx, PinBuf& b, size_t bytes, int slack_divisor, bool zero_on_growth) {
-    MRG_HIP_CHECK(grow_pinned(b, bytes, slack_divisor, zero_on_growth));
+    MRG_HIP_CHECK(grow_pinned(ctx, b, bytes, slack_divisor, zero_on_growth));
     return 0;
 }
 
@@ -153,7 +173,7 @@ int ensure_level_set(mrgingham_amd_ctx* ctx, int set, int level, int nframes, in
         // device is idle and nothing is queued.  A mirror that cannot be had stays away until the next growth (the sync
         // then makes a blocking copy: harvest_set)
         for (int k = 0; k < kMaxSets; ++k)
-            if (grow_pinned(ctx->status_pin[k], (size_t)(kMaxLevel + 1) * cnf * sizeof(int32_t), 0, false) != hipSuccess) (void)hipGetLastError();
+            if (grow_pinned(ctx, ctx->status_pin[k], (size_t)(kMaxLevel + 1) * cnf * sizeof(int32_t), 0, false) != hipSuccess) (void)hipGetLastError();
         ctx->counters_nf = cnf;
     }
     if ((rc = ensure(ctx, L.hot_xy, nf * (size_t)cap * 4))) return rc;
@@ -386,6 +406,7 @@ mrgingham_amd_ctx* mrgingham_amd_create(int device_ordinal) {
     mrgingham_amd_ctx* ctx = new mrgingham_amd_ctx();
     ctx->device = device_ordinal;
     for (int& g : ctx->grown_shift) g = 31;
+    ctx->scratch_fill = scratch_fill_from_env();  // (test hook, ctx.h: off unless the variable holds a byte)
 #ifdef MRG_EXPERIMENT
     const char* v0 = getenv("MRGINGHAM_AMD_CHESS_V0");
     ctx->use_v0 = v0 && atoi(v0) != 0;
@@ -395,7 +416,8 @@ mrgingham_amd_ctx* mrgingham_amd_create(int device_ordinal) {
     // Experiment hooks (tools/interference_ab.py): MRGINGHAM_AMD_CC_CUS = k confines the component
     // streams to k CUs per XCD (CU-mask bit i is XCD i % 8, CU i / 8: probed with
     // tools/ubench/cu_mask.hip); MRGINGHAM_AMD_PIX_COMPLEMENT = 1 keeps the pixel stream off them.
-    // (only in -DMRG_EXPERIMENT builds: the shipped library reads no environment variable but MRGINGHAM_AMD_DEVICE)
+    // (only in -DMRG_EXPERIMENT builds: the shipped library reads no environment variable but MRGINGHAM_AMD_DEVICE and the
+    // test hook MRGINGHAM_AMD_SCRATCH_FILL)
 #ifdef MRG_EXPERIMENT
     const char* ecc = getenv("MRGINGHAM_AMD_CC_CUS");
     const int cc_cus = ecc ? atoi(ecc) : 0;
@@ -520,10 +542,44 @@ double mrgingham_amd_sclk_mhz(mrgingham_amd_ctx* ctx) {
     return c[1] ? (double)c[0] / (double)c[1] * khz * 1e-3 : 0.;
 }
 
+// set_option "scratch_fill_now" (test hook, ctx.h): with nothing of the context in flight, every scratch buffer it owns
+// gets `byte` over its whole size -- but for the state ctx.h lists
+static int fill_scratch_now(mrgingham_amd_ctx* ctx, int byte) {
+    MRG_HIP_CHECK(hipSetDevice(ctx->device));
+    const int rc = mrgingham_amd_sync(ctx);
+    MRG_HIP_CHECK(hipDeviceSynchronize());
+    ctx->pixel_stage.valid = false;  // (mrgingham_amd_debug_pixel_products reads scratch)
+    for (DevBuf* b : ctx->scratch_bufs) {
+        if (!b->p || b == &ctx->sparse_stat || b == &ctx->clk) continue;
+        size_t skip = 0;  // counters2: the hot-count and status words stay, the path words behind them go
+        for (const DevBuf& c : ctx->counters2)
+            if (b == &c) skip = (size_t)(kMaxLevel + 1) * 2 * (size_t)ctx->counters_nf * sizeof(int32_t);
+        if (skip < b->bytes) MRG_HIP_CHECK(hipMemset((char*)b->p + skip, byte, b->bytes - skip));
+    }
+    for (PinBuf* b : ctx->pinned_bufs)
+        if (b->p) memset(b->p, byte, b->bytes);
+    MRG_HIP_CHECK(hipDeviceSynchronize());
+    if (ctx->one) {
+        const int r1 = fill_scratch_now(ctx->one, byte);
+        if (r1) return r1;
+    }
+    return rc;
+}
+
 /* tunables (not part of the reference surface) */
 int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value) {
     if (!ctx || !name) return MRGINGHAM_AMD_ERR_ARG;
     fb_drain(ctx);
+    if (!strcmp(name, "scratch_fill")) {  // test hook (ctx.h): what new allocations of this context are filled with, -1 = nothing
+        if (value < -1 || value > 255) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "scratch_fill: -1 (off) or a byte");
+        ctx->scratch_fill = value;
+        if (ctx->one) ctx->one->scratch_fill = value;
+        return 0;
+    }
+    if (!strcmp(name, "scratch_fill_now")) {
+        if (value < 0 || value > 255) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "scratch_fill_now: a byte");
+        return fill_scratch_now(ctx, value);
+    }
     if (!strcmp(name, "hot_capacity_shift")) {
         if (value < 0 || value > 10) return MRGINGHAM_AMD_ERR_ARG;
         ctx->cap_shift = value;

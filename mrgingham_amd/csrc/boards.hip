@@ -21,6 +21,7 @@ static mrgingham_amd_ctx* same_device_ctx(mrgingham_amd_ctx* ctx) {
     if (!ctx->one) {
         ctx->one = mrgingham_amd_create(ctx->device);
         if (ctx->one) ctx->one->cap_shift = ctx->cap_shift;
+        if (ctx->one) ctx->one->scratch_fill = ctx->scratch_fill;
         hipSetDevice(ctx->device);
     }
     if (!ctx->one) fail(ctx, MRGINGHAM_AMD_ERR_DEVICE, "no single-frame context");

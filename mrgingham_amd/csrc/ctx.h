@@ -236,7 +236,7 @@ struct mrgingham_amd_ctx {
     // around the points it refines there (chain.hip: chain_pixels_sparse, queue_sparse_levels)
     int sparse_refine = 1;     // (default: where it pays)
     bool sparse_seen = false;  // a chain has taken the sparse schedule (choose_sets)
-    mrg::DevBuf sparse_stat;   // [0]: frames the sparse schedule reported and the library repeated densely (mrgingham_amd_sparse_fallbacks)
+    mrg::DevBuf sparse_stat;   // [0]: frames the sparse schedule reported and the library repeated densely (mrgingham_amd_sparse_fallbacks); STATE: see scratch_fill
     int fuse_pyramid = 1;   // option "fuse_pyramid": chain calls take the level images 1..3 out of the level-0 response kernel
     // component-chain schedule of chain_batch: 0 = every level's component kernels start as soon as
     // that level's response is done; 1 (default) = levels 1 and 0 wait for the level-0 response (they then
@@ -248,8 +248,32 @@ struct mrgingham_amd_ctx {
     // device bytes of this context's scratch (mrgingham_amd_scratch_bytes), kept by ensure and release: atomic, because a
     // shard of mrgingham_amd_chain_multi grows its context's scratch on the submit thread
     std::atomic<long long> scratch_total{0};
+    // TEST HOOK "scratch_fill" (DESIGN.md section 3.3): -1 = off; 0 .. 255: every new allocation of context memory -- ensure,
+    // ensure_pinned, the ring slots of find_boards_files -- is filled with that byte over its whole allocated size before
+    // anyone uses it, so that a kernel which reads scratch nobody has written reads something loud instead of the zero
+    // of fresh memory.  From MRGINGHAM_AMD_SCRATCH_FILL when the context is created (so that it reaches the contexts no
+    // caller holds), or set_option("scratch_fill").  set_option("scratch_fill_now", byte) fills, once and at rest, every
+    // buffer in scratch_bufs / pinned_bufs: the buffers ensure and ensure_pinned have served, all of them members of this
+    // context, its jobs or its slots (stable addresses; p == nullptr: given back).  Everything is scratch and is filled,
+    // except the STATE listed here, which a call leaves for the next one by design:
+    //   counters2[set], hot-count words [0, (kMaxLevel + 1) * counters_nf): zero between calls.  ensure_level_set zeroes
+    //     them at allocation, the response kernels count them up, end_op zeroes them again behind the component kernels that
+    //     consumed them (begin_op relies on it: no memset on the pixel stream).
+    //   counters2[set], status words [(kMaxLevel + 1) * counters_nf, 2 * ...): zero unless a call reported.  Zeroed at
+    //     allocation; the kernels only ever OR into them; inspect_status (mrgingham_amd_sync, harvest_status) clears what it
+    //     has read.  The PATH words behind them are scratch (the classify kernel writes a frame's word before any kernel of
+    //     that call reads it) and are filled.
+    //   sparse_stat: word 0 counts the sparse fallbacks since mrgingham_amd_sparse_fallbacks last read it.  Zeroed where it
+    //     is allocated (chain.hip, boards.hip), added to by the kernels, zeroed again by the read-out.
+    //   clk: two counters that add up over the probed launches until mrgingham_amd_sclk_mhz reads and zeroes them; zeroed
+    //     where they are allocated (mrgingham_amd_set_kernel_timing).
+    // No page-locked buffer is state: status_pin is read only behind the copy end_op queues (status_copied), a job's pin
+    // only while the job is in flight, and the fill completes every job first.
+    int scratch_fill = -1;
+    std::vector<mrg::DevBuf*> scratch_bufs;
+    std::vector<mrg::PinBuf*> pinned_bufs;
     mrg::LevelScratch lvs[kMaxSets][mrg::kMaxLevel + 1];
-    mrg::DevBuf counters2[kMaxSets];  // per scratch set: hot_cnt words [level][counters_nf], then status words, then path words
+    mrg::DevBuf counters2[kMaxSets];  // per scratch set: hot_cnt words [level][counters_nf], then status words, then path words (STATE but for the path words: see scratch_fill)
     int counters_nf = 0;
     struct PointScratch { mrg::DevBuf leader, need, nseeds, seeds, sroot, cand_xy, cand_counts, cell_list, cell_cnt, flag_list; } pts[kMaxSets];  // per scratch set
     mrg::DevBuf aux_img, io_frame, io_out, io_counts;
@@ -261,7 +285,7 @@ struct mrgingham_amd_ctx {
     bool status_copied[kMaxSets] = {};  // the LAST op on the set left its words in status_pin
     mrg::PinBuf io_pin;  // page-locked staging of mrgingham_ChESS_response_5's way back
     mrg::Event io_ev[4];
-    mrg::DevBuf clk;  // two u64: shader cycles and constant-rate ticks of the probed workgroups (mrgingham_amd_sclk_mhz)
+    mrg::DevBuf clk;  // two u64: shader cycles and constant-rate ticks of the probed workgroups (mrgingham_amd_sclk_mhz); STATE: see scratch_fill
     mrg::DevBuf pre_scratch, pre_tmp, pre_out, pre16_scratch, io_frame16, dbg_img, dbg_resp, blob_scratch, blob_nodes, blob_out;
     // blob detector (blobs.hip): a batch is worked through in chunks of frames whose plane scratch (blob_scratch) stays
     // within the budget; option "blob_chunk_frames" (test hook): at most that many frames per chunk, 0 = by budget
@@ -276,7 +300,8 @@ struct mrgingham_amd_ctx {
     // _read_tiffs_batch (tiff_decode.hip; files, strip tables), _read_bmps_batch (bmp_unpack.hip; grey tables | pixel
     // arrays) and _read_pnms_batch (pnm_unpack.hip; rasters).  Their calls never overlap, because all are synchronous,
     // and each call sizes and fills what it reads: nothing a call leaves in a slot matters to the next.  The staging is zero only until its first use (ensure_pinned zeroes it when it grows); that is enough,
-    // because the IDCT kernel never reads a block outside width x height, and every decoded file covers those.
+    // because the IDCT kernel never reads a block outside width x height, and every decoded file covers those
+    // (tests/test_gpu_scratch_fill.py runs every loader on staging filled with 0x7F and 0xFF).
     // Option "jpeg_chunk_frames" (test hook): at most that many frames per chunk, 0 = by jpeg_coef_budget
     struct LoaderSlot {
         mrg::DevBuf dev;
@@ -419,10 +444,14 @@ constexpr int kCellsPerPoint = 9;  // sparse refinement: distinct cells the 3 x 
 
 // api.hip: errors, buffers, level scratch
 int fail(mrgingham_amd_ctx* ctx, int code, const char* fmt, ...);
-// at least `bytes` of device memory: the only place that allocates context scratch (and counts it)
+// at least `bytes` of device memory: the only place that allocates context scratch (and counts it, and notes the buffer
+// in ctx->scratch_bufs, and fills what it allocates while ctx->scratch_fill is on)
 int ensure(mrgingham_amd_ctx* ctx, DevBuf& b, size_t bytes);
 void release(mrgingham_amd_ctx* ctx, DevBuf& b);  // gives it back now
+// MRGINGHAM_AMD_SCRATCH_FILL as a fill byte (decimal or 0x..), -1 where it is unset, empty or no number in 0 .. 255
+int scratch_fill_from_env();
 // at least `bytes` of page-locked memory; growth allocates bytes + bytes / slack_divisor (0: no slack), zeroed if asked
+// (while ctx->scratch_fill is on: filled with that byte, asked or not)
 int ensure_pinned(mrgingham_amd_ctx* ctx, PinBuf& b, size_t bytes, int slack_divisor, bool zero_on_growth);
 hipError_t copy_rows_async(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows,
                            hipMemcpyKind kind, hipStream_t s);

@@ -361,6 +361,12 @@ int find_boards_files(int accepted, const char* const* filenames, int nfiles, co
             if ((preprocess || any_deep) && hipMalloc(&S.d_pre.p, bytes) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
             if (max_host_frame && hipHostMalloc(&S.pin.p, (size_t)R.batch * max_host_frame, hipHostMallocDefault) != hipSuccess)
                 return MRGINGHAM_AMD_ERR_DEVICE;
+            if (const int fill = R.loader->scratch_fill; fill >= 0) {  // test hook (ctx.h, scratch_fill): the slots are scratch like a context's
+                if (hipMemset(S.d_raw.p, fill, bytes) != hipSuccess || (S.d_pre.p && hipMemset(S.d_pre.p, fill, bytes) != hipSuccess) ||
+                    hipDeviceSynchronize() != hipSuccess)
+                    return MRGINGHAM_AMD_ERR_DEVICE;
+                if (S.pin.p) memset(S.pin.p, fill, (size_t)R.batch * max_host_frame);
+            }
             if (S.ev_up.create(hipEventDisableTiming) != hipSuccess) return MRGINGHAM_AMD_ERR_DEVICE;
             S.boards.resize((size_t)R.batch * N * 2);
             S.levels.resize((size_t)R.batch * N);

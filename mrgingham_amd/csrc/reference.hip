@@ -357,6 +357,8 @@ int mrgingham_amd_thread_device(void) {
 void* mrgingham_amd_host_alloc(size_t bytes) {
     void* p = nullptr;
     if (bytes == 0 || hipHostMalloc(&p, bytes, hipHostMallocPortable) != hipSuccess) return nullptr;
+    static const int fill = scratch_fill_from_env();  // test hook (ctx.h, scratch_fill): no context here, the variable alone
+    if (fill >= 0) memset(p, fill, bytes);
     return p;
 }
 void mrgingham_amd_host_free(void* p) {

@@ -113,7 +113,8 @@ def test_shipped_library_has_no_experiment_hooks():
                  b"MRGINGHAM_AMD_PIX_COMPLEMENT", b"MRGINGHAM_AMD_CHESS_V0", b"MRG_DBG_FB", b"chess_variant_hot",
                  b"chess_v16_pyr_kernel", b"chess_v16_multi_kernel", b"chess_v16_pair_kernel", b"chess16_pair"):
         assert name not in blob, name
-    assert b"MRGINGHAM_AMD_DEVICE" in blob                  # the one variable it does read
+    assert b"MRGINGHAM_AMD_DEVICE" in blob                  # the one variable it does read ...
+    assert b"MRGINGHAM_AMD_SCRATCH_FILL" in blob            # ... besides the test hook that may change no result (test_gpu_scratch_fill.py)
     csrc = os.path.join(here, "mrgingham_amd", "csrc")
     srcs = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")))
     assert {"api.hip", "chain.hip", "boards.hip", "chess.hip", "cc.hip"} <= set(srcs)
@@ -121,7 +122,7 @@ def test_shipped_library_has_no_experiment_hooks():
         text = open(os.path.join(csrc, src)).read()
         lines = text.split("\n")
         depth = 0
-        for ln in lines:                                    # every getenv outside MRGINGHAM_AMD_DEVICE sits in #ifdef MRG_EXPERIMENT
+        for ln in lines:                                    # every getenv outside those two sits in #ifdef MRG_EXPERIMENT
             st = ln.strip()
             if st.startswith("#ifdef MRG_EXPERIMENT"):
                 depth += 1
@@ -131,7 +132,7 @@ def test_shipped_library_has_no_experiment_hooks():
                 depth = -1                                   # the release branch of an experiment block
             elif st.startswith("#endif") and depth:
                 depth = 0 if depth in (1, -1) else depth - 1
-            if "getenv(" in ln and "MRGINGHAM_AMD_DEVICE" not in ln:
+            if "getenv(" in ln and "MRGINGHAM_AMD_DEVICE" not in ln and 'getenv("MRGINGHAM_AMD_SCRATCH_FILL")' not in ln:
                 assert depth > 0, (src, ln)
 
 
