@@ -89,7 +89,11 @@ extern "C" {
  *      or default changes; no file reader takes such frames (a headerless frame carries no size).
  *      Later, additive (the version stays 4): mrgingham_amd_bayer_grey_image, _bayer_grey_batch, _bayer_grey_geometry and the
  *      MRGINGHAM_AMD_BAYER_* patterns (Bayer mosaics, uint8 or uint16, to grey frames of the same type, on the host and on
- *      the device).  No earlier call, option or default changes; no file reader and no tool option takes a mosaic. */
+ *      the device).  No earlier call, option or default changes; no file reader and no tool option takes a mosaic.
+ *      Later, additive (the version stays 4): mrgingham_amd_colour_grey_image, _colour_grey_batch, _colour_grey_geometry and
+ *      the MRGINGHAM_AMD_COLOUR_* formats (colour frames -- interleaved RGB / BGR with 3 or 4 samples, planar, packed YUV
+ *      4:2:2 -- to grey frames of the same sample type, on the host and on the device).  No earlier call, option or default
+ *      changes; no file reader and no tool option takes such frames. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -798,6 +802,81 @@ int mrgingham_amd_bayer_grey_batch(mrgingham_amd_ctx* ctx, const void* d_in, int
 /* the schedule of that launch: the lanes of a workgroup (side by side along a row, one 16-byte word each), the rows of a
  * slab, and the workgroups per CU the grid is capped at (0: it is not capped, one workgroup per slab and span of a row) */
 void mrgingham_amd_bayer_grey_geometry(int* lanes_per_workgroup, int* rows_per_slab, int* max_workgroups_per_cu);
+
+/* Colour frames to grey frames, 8 and 16 bit.  The definition, which governs:
+ *
+ * Inputs.
+ * - Frames of `height` x `width` pixels, sides 1 .. 32767.
+ * - Samples are `uint8`, or native-endian `uint16` where the format allows it.
+ * - Formats (`MRGINGHAM_AMD_COLOUR_*`, Python names in brackets):
+ *
+ *   value  name                          layout                                                       bits
+ *   0      RGB ("rgb")                   interleaved, 3 samples per pixel, R G B                      8, 16
+ *   1      BGR ("bgr")                   interleaved, 3 samples per pixel, B G R                      8, 16
+ *   2      RGBA ("rgba")                 interleaved, 4 samples, the fourth ignored                   8, 16
+ *   3      BGRA ("bgra")                 interleaved, 4 samples, the fourth ignored                   8, 16
+ *   4      RGB_PLANAR ("rgb_planar")     three planes R, G, B, `plane_pitch` elements apart           8, 16
+ *   5      BGR_PLANAR ("bgr_planar")     three planes B, G, R, `plane_pitch` elements apart           8, 16
+ *   6      YUYV ("yuyv")                 2 bytes per pixel, Y of pixel x at byte 2x                   8
+ *   7      UYVY ("uyvy")                 2 bytes per pixel, Y of pixel x at byte 2x+1                 8
+ *
+ * Output.
+ * - A grey frame of the input's sample type.
+ * - Formats 0-5: `grey = (4899 R + 9617 G + 1868 B + 8192) >> 14`, unsigned 32-bit.  The largest intermediate is
+ *   `65535*16384 + 8192 < 2^32`.  This is `png_grey` itself, called, not restated.
+ * - The fourth sample of formats 2 and 3 is never looked at.  There is no compositing and no premultiplication, as in the
+ *   PNG type 6 and PAM depth 4 readers.
+ * - Formats 6 and 7: the Y byte as it is.  There is no range expansion, and the chroma bytes are never looked at.  Any
+ *   width is allowed, odd ones included.
+ * - Known answers:
+ *   - 8 bit: pure R, G, B at 255 give 76, 150, 29.
+ *   - 16 bit: pure R, G, B at 65535 give 19596, 38467, 7472.
+ *   - Equal samples v in all three channels give v.
+ *
+ * (The expression is png_grey's -- csrc/png_filter.h, the one formula of the colour file readers -- written in
+ * csrc/colour_pixels.h with the weights of the first and the third sample as two values that change places between the
+ * R G B and the B G R orders; the tests hold it equal to png_grey through the PNG and PAM readers.)
+ *
+ * Not done: YUV to RGB or chroma of any kind; 4:2:0 / NV12 / P010 (their Y plane is already a [B,H,W] view that the existing
+ * calls take); 10-bit packed YUV; XRGB / ARGB orders; float samples; 8-bit output from 16-bit input; a file or tool route. */
+#define MRGINGHAM_AMD_COLOUR_RGB 0
+#define MRGINGHAM_AMD_COLOUR_BGR 1
+#define MRGINGHAM_AMD_COLOUR_RGBA 2
+#define MRGINGHAM_AMD_COLOUR_BGRA 3
+#define MRGINGHAM_AMD_COLOUR_RGB_PLANAR 4
+#define MRGINGHAM_AMD_COLOUR_BGR_PLANAR 5
+#define MRGINGHAM_AMD_COLOUR_YUYV 6
+#define MRGINGHAM_AMD_COLOUR_UYVY 7
+
+/* One colour frame to grey on the HOST (no device needed; the text the kernel runs, csrc/colour_pixels.h): bits 8 (uint8_t)
+ * or 16 (native uint16_t); row y of the image begins at image + y*stride (planar: plane k's at image + k*plane_pitch +
+ * y*stride), row y of the output at out + y*out_stride, ELEMENTS of the sample type.  stride >= samples per pixel x width
+ * (3, 4, or 2 for the 4:2:2 forms; planar: >= width); plane_pitch >= 0 is read for formats 4 and 5 only.  It reads and
+ * writes bytewise, at any address, and no byte outside the samples of the frame; only the width x height outputs are
+ * written.  MRGINGHAM_AMD_ERR_ARG, with nothing written, for a NULL pointer, a bad format, bits outside 8 / 16, 16 bits with
+ * formats 6 / 7, sides outside 1 .. 32767, a stride below a row or a negative plane_pitch.  `out` must not overlap the
+ * image.  This is the route a caller without the device call has; it is not a fallback of mrgingham_amd_colour_grey_batch. */
+int mrgingham_amd_colour_grey_image(const void* image, int bits, int format, int width, int height, int64_t stride,
+                                    int64_t plane_pitch, void* out, int64_t out_stride);
+
+/* Colour frames to grey frames on the device: frame f row y at d_in + f*in_frame_pitch + y*in_stride (planar: plane k's at
+ * + k*in_plane_pitch) and at d_out + f*out_frame_pitch + y*out_stride, ELEMENTS of bits / 8 bytes, at any element-aligned
+ * address (torch views).  in_stride >= samples per pixel x width (planar: >= width), out_stride >= width; in_plane_pitch
+ * >= 0 is read for formats 4 and 5 only (planes may lie further apart than frames); an in_frame_pitch of 0 (an expanded
+ * view) is allowed.  Only the width x height outputs of a frame are written.  One streaming launch on the row schedule of
+ * the unpack kernels: a lane produces one 16-byte word of a destination row per step from the source bytes of its
+ * pixels, read as 16-byte loads where their address allows it, else as the aligned dwords that hold them; it reads the
+ * aligned dwords that hold samples of the frames and no others.  Asynchronous on `stream` (NULL = default); allocates
+ * nothing; nframes == 0 is OK.  MRGINGHAM_AMD_ERR_ARG with nothing launched and nothing written for: a NULL pointer or
+ * context; a bad format, bits outside 8 / 16, or 16 bits with formats 6 / 7; sides outside 1 .. 32767; strides below a row,
+ * negative pitches, an odd uint16 address; output frames that overlap each other; output that overlaps any byte of the
+ * input's extent (first to last sample of all frames), with "overlap" in mrgingham_amd_last_error. */
+int mrgingham_amd_colour_grey_batch(mrgingham_amd_ctx* ctx, const void* d_in, int bits, int format, int nframes, int width,
+                                    int height, int64_t in_frame_pitch, int64_t in_plane_pitch, int64_t in_stride, void* d_out,
+                                    int64_t out_frame_pitch, int64_t out_stride, void* stream);
+
+/* the schedule of that launch, as mrgingham_amd_pnm_unpack_geometry's */
+void mrgingham_amd_colour_grey_geometry(int* lanes_per_workgroup, int* max_workgroups_per_cu);
 
 /* TIFF, host half (host only, no device needed): the one parser of a TIFF's first image file directory, behind
  * mrgingham_amd_read_image, _probe_image and _read_tiffs_batch.  `data` is a whole file held in memory.  The subset is

@@ -464,6 +464,46 @@ def bayer_grey_geometry():
     return a.value, b.value, c.value
 
 
+# the colour formats (MRGINGHAM_AMD_COLOUR_*): interleaved with 3 or 4 samples per pixel, three planes, packed YUV 4:2:2
+COLOUR_FORMATS = {"rgb": 0, "bgr": 1, "rgba": 2, "bgra": 3, "rgb_planar": 4, "bgr_planar": 5, "yuyv": 6, "uyvy": 7}
+# the samples of a pixel along the last axis of a frame (the planar formats: 1, the three planes lie on an axis of their own)
+_COLOUR_SAMPLES = {0: 3, 1: 3, 2: 4, 3: 4, 4: 1, 5: 1, 6: 2, 7: 2}
+
+
+def _colour_format(format, who):
+    if not isinstance(format, str) or format not in COLOUR_FORMATS:
+        raise ValueError(f'{who}: format is one of "rgb", "bgr", "rgba", "bgra", "rgb_planar", "bgr_planar", "yuyv", "uyvy"')
+    return COLOUR_FORMATS[format]
+
+
+def colour_grey(image, format):
+    """One colour frame to grey on the host (mrgingham_amd_colour_grey_image, no device needed): image np.uint8 or np.uint16
+    [H, W, C] with C = 3 ("rgb", "bgr"), 4 ("rgba", "bgra": the fourth sample is ignored) or 2 ("yuyv", "uyvy": uint8 only,
+    the Y byte as it is), or [3, H, W] for "rgb_planar" and "bgr_planar"; sides 1 .. 32767 -> [H, W] of the same dtype:
+    (4899 R + 9617 G + 1868 B + 8192) >> 14, the grey of the colour file readers (include/mrgingham_amd.h has the
+    definition).  Detector.colour_grey is the device's route for batches."""
+    f = _colour_format(format, "colour_grey")
+    image = np.asarray(image)
+    C = _COLOUR_SAMPLES[f]
+    planar = C == 1
+    if (image.dtype not in (np.uint8, np.uint16) or image.ndim != 3 or (image.shape[0] if planar else image.shape[2]) != (3 if planar else C)
+            or (f >= 6 and image.dtype != np.uint8)):
+        raise ValueError("colour_grey: image is a uint8 or uint16 [H,W,C] array with C = 3, 4, or 2 (4:2:2, uint8), or [3,H,W] for the planar formats")
+    image = np.ascontiguousarray(image)
+    H, W = image.shape[1:] if planar else image.shape[:2]
+    out = np.empty((H, W), dtype=image.dtype)
+    if _lib.lib().mrgingham_amd_colour_grey_image(image.ctypes.data, 8 * image.itemsize, f, W, H, C * W, H * W, out.ctypes.data, W) != 0:
+        raise ValueError("colour_grey: sides 1 .. 32767")
+    return out
+
+
+def colour_grey_geometry():
+    """(lanes_per_workgroup, max_workgroups_per_cu) of the colour launch (mrgingham_amd_colour_grey_geometry)."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _lib.lib().mrgingham_amd_colour_grey_geometry(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
 def read_image(filename, cli_scaling=False):
     """Decode a binary PGM, non-interlaced PNG, baseline JPEG, strip or tiled TIFF (uncompressed, LZW, PackBits, Deflate; grey or
     RGB, 8 or 16 bit), Windows Bitmap (1, 4, 8 bit palette, RLE8, 24 and 32 bit; bmp_layout has the subset) or binary PBM or PAM
@@ -1455,6 +1495,44 @@ class Detector:
         self._check(self.L.mrgingham_amd_bayer_grey_batch(
             self.ctx, frames.data_ptr(), 8 * frames.element_size(), B, W, H, frames.stride(0) if B > 1 else 0, frames.stride(1), p,
             out.data_ptr(), out.stride(0) if B > 1 else 0, out.stride(1), stream))
+        return out
+
+    def colour_grey(self, frames, format, out=None):
+        """Colour frames to grey frames on the device (mrgingham_amd_colour_grey_batch), on torch's current stream: frames
+        uint8 or uint16 device tensor, [B,H,W,C] with stride(3) == 1 and stride(2) == C -- C = 3 for "rgb" / "bgr", 4 for
+        "rgba" / "bgra" (the fourth sample is ignored), 2 for "yuyv" / "uyvy" (uint8 only: the Y byte as it is) -- or
+        [B,3,H,W] with stride(3) == 1 for "rgb_planar" / "bgr_planar" (torch's own layout for images); any row, plane and
+        frame stride is taken as it is; sides 1 .. 32767 -> [B,H,W] of the same dtype:
+        (4899 R + 9617 G + 1868 B + 8192) >> 14, the grey of the colour file readers (include/mrgingham_amd.h has the
+        definition).  `out`: a [B,H,W] device tensor of the same dtype (unit column stride) to write into; it must not
+        overlap `frames`.  The Y plane of an NV12 / 4:2:0 frame is a [B,H,W] view already: find_boards takes it as it is.
+
+            boards, found = det.find_boards(det.colour_grey(rgb, "rgb_planar"), gridn=10)        # uint8 [B,3,H,W]
+            boards, found = det.find_boards(det.preprocess(det.colour_grey(rgb16, "rgb")), gridn=10)   # uint16 [B,H,W,3]"""
+        t = self.torch
+        f = _colour_format(format, "colour_grey")
+        C = _COLOUR_SAMPLES[f]
+        planar = C == 1
+        if not (t.is_tensor(frames) and frames.is_cuda and frames.dtype in (t.uint8, t.uint16) and frames.dim() == 4
+                and (f < 6 or frames.dtype == t.uint8) and frames.stride(3) == 1 and frames.stride(0) >= 0
+                and (frames.shape[1] == 3 and frames.stride(1) >= 0 if planar else frames.shape[3] == C and frames.stride(2) == C)):
+            raise ValueError("colour_grey: frames is a uint8 or uint16 tensor on the device, [B,H,W,C] with strides (.., .., C, 1), C = 3, 4, or 2 "
+                             "(4:2:2, uint8), or [B,3,H,W] with unit column stride for the planar formats")
+        B = frames.shape[0]
+        H, W = frames.shape[2:] if planar else frames.shape[1:3]
+        row_stride = frames.stride(2) if planar else frames.stride(1)
+        if not (1 <= H <= 32767 and 1 <= W <= 32767 and (H == 1 or row_stride >= C * W)):
+            raise ValueError("colour_grey: sides 1 .. 32767, rows at least a row apart")
+        if out is None:
+            out = t.empty((B, H, W), dtype=frames.dtype, device=frames.device)
+        if not (t.is_tensor(out) and out.is_cuda and out.device == frames.device and out.dtype == frames.dtype and tuple(out.shape) == (B, H, W)
+                and out.stride(2) == 1 and (H == 1 or out.stride(1) >= W) and (B <= 1 or out.stride(0) >= (H - 1) * out.stride(1) + W)):
+            raise ValueError("colour_grey: out is a [B,H,W] tensor of the frames' dtype on their device with unit column stride, its frames apart")
+        stream = t.cuda.current_stream(frames.device).cuda_stream
+        self._check(self.L.mrgingham_amd_colour_grey_batch(
+            self.ctx, frames.data_ptr(), 8 * frames.element_size(), f, B, W, H, frames.stride(0) if B > 1 else 0,
+            frames.stride(1) if planar else 0, row_stride if H > 1 else C * W, out.data_ptr(), out.stride(0) if B > 1 else 0,
+            out.stride(1) if H > 1 else W, stream))
         return out
 
     def read_pnms(self, paths, nthreads=0):

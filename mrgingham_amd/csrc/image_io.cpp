@@ -2,6 +2,7 @@
 #include "image_io.h"
 #include "bayer_pixels.h"
 #include "bmp_pixels.h"
+#include "colour_pixels.h"
 #include "jpeg.h"
 #include "png_filter.h"
 #include "pnm_pixels.h"
@@ -1016,6 +1017,21 @@ extern "C" int mrgingham_amd_bayer_grey_image(const void* mosaic, int bits, int 
         mrg::bayer_grey_rows<1>((const uint8_t*)mosaic, width, height, stride, pattern, (uint8_t*)out, out_stride);
     else
         mrg::bayer_grey_rows<2>((const uint8_t*)mosaic, width, height, stride, pattern, (uint8_t*)out, out_stride);
+    return 0;
+}
+
+// a colour frame to grey on the host: every word of every row through colour_pixels.h, the text the device runs
+extern "C" int mrgingham_amd_colour_grey_image(const void* image, int bits, int format, int width, int height, int64_t stride, int64_t plane_pitch,
+                                               void* out, int64_t out_stride) {
+    if (!image || !out || (bits != 8 && bits != 16) || !mrg::colour_format_ok(format, bits) || width < 1 || height < 1 || width > 32767 ||
+        height > 32767)
+        return MRGINGHAM_AMD_ERR_ARG;
+    const int layout = mrg::colour_layout(format);
+    if (layout != mrg::kColourPlanar) plane_pitch = 0;  // (read for the planar formats only)
+    if (stride < (int64_t)mrg::colour_row_samples(layout) * width || out_stride < width || stride > ((int64_t)1 << 40) ||
+        out_stride > ((int64_t)1 << 40) || plane_pitch < 0 || plane_pitch > ((int64_t)1 << 40))
+        return MRGINGHAM_AMD_ERR_ARG;
+    mrg::colour_grey_rows_any((const uint8_t*)image, bits, format, width, height, stride, plane_pitch, (uint8_t*)out, out_stride);
     return 0;
 }
 
