@@ -173,8 +173,11 @@ bool mrgingham_amd_find_grid_from_points_traced(const int* xy_scaled, int npoint
 
 /* TEST HOOK: the same with the parts of the visiting order that cannot be checked against the
  * reference's boost::polygon graph perturbed -- ring_seed != 0 starts every site's neighbour ring at a
- * pseudo-random position, last_match != 0 takes the last neighbour that continues a sequence instead of
- * the first (find_grid.cc:216-222).  tests/test_grid.py asserts the results do not change. */
+ * pseudo-random position, bit 0 of last_match takes the last neighbour that continues a sequence instead of
+ * the first (find_grid.cc:216-222).  tests/test_grid.py asserts the results do not change.  Bit 1 of last_match
+ * is the canonical start: every site's ring begins at its first neighbour counter-clockwise from +x (and ring_seed
+ * rotates it from there), the rule of the stand-in Voronoi diagram under which tests/test_oracle_grid.py holds this
+ * finder to the reference's own find_grid.cc bit for bit. */
 bool mrgingham_amd_find_grid_from_points_perturbed(const int* xy_scaled, int npoints, int gridn, double* xy_out,
                                                    unsigned ring_seed, int last_match);
 

@@ -753,13 +753,16 @@ def find_grid_from_points_traced(points_scaled, gridn=10, debug_sequence=(-1, -1
     return out if ok else None
 
 
-def find_grid_from_points_perturbed(points_scaled, gridn=10, ring_seed=0, last_match=False):
+def find_grid_from_points_perturbed(points_scaled, gridn=10, ring_seed=0, last_match=False, canonical_start=False):
     """Test hook: find_grid_from_points with the neighbour-ring start of every site randomised (ring_seed != 0)
-    and / or the last instead of the first matching neighbour taken along a sequence."""
+    and / or the last instead of the first matching neighbour taken along a sequence.  canonical_start: every
+    site's ring starts at its first neighbour counter-clockwise from +x (ring_seed then rotates it from there),
+    the rule of the stand-in Voronoi diagram that the parity tests run upstream's find_grid.cc on."""
     pts = np.ascontiguousarray(points_scaled, dtype=np.int32).reshape(-1, 2)
     out = np.empty((gridn * gridn, 2), dtype=np.float64)
     ok = _lib.lib().mrgingham_amd_find_grid_from_points_perturbed(pts.ctypes.data, len(pts), int(gridn),
-                                                                 out.ctypes.data, int(ring_seed), int(bool(last_match)))
+                                                                 out.ctypes.data, int(ring_seed),
+                                                                 int(bool(last_match)) | (int(bool(canonical_start)) << 1))
     return out if ok else None
 
 

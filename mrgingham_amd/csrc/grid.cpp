@@ -8,17 +8,27 @@
 // :953-1003 equal-and-opposite cycles, :1025-1190 clockwise cycle and top edge,
 // :1192-1214 sequence lookup), written from the algorithm, not copied.
 //
-// PARITY UNPINNED.  The reference reads its neighbour structure off boost::polygon's Voronoi
-// diagram (find_grid.cc:7, :1226-1227); boost is absent here and the reference has no test for this
-// file, so nothing executable pins this restatement.  The neighbour structure below is the Delaunay
-// triangulation of the same integer points (the dual of that Voronoi diagram) with exact integer
-// predicates; neighbours of a site are visited counter-clockwise (in the x,y plane as numbers) like
-// boost's edge->next(), sites in boost's cell order (sorted by x, then y).  Where the reference takes
-// "the first neighbour that matches" (find_grid.cc:216-222) the starting neighbour of the rotation is
-// an implementation detail of boost that is not reproduced; on clean boards exactly one neighbour
-// matches, and the final grid is fixed by geometry (unique 4-cycles, clockwise test, top edge), not by
-// visiting order.  Exactly cocircular quadruples (a degenerate Voronoi vertex) get one of their two
-// diagonals here and none in boost.
+// PARITY: pinned to the reference's own find_grid.cc through a stand-in Voronoi diagram.  The reference
+// reads its neighbour structure off boost::polygon's Voronoi diagram (find_grid.cc:7, :1226-1227); the tests
+// compile the unmodified find_grid.cc against a stand-in boost/polygon/voronoi.hpp of their own, an exact diagram of
+// the same integer sites built by another method than the one below, and tests/test_oracle_grid.py requires this file
+// to return upstream's answer bit for bit -- 500 clean and 300 ambiguous candidate sets, exact and jittered
+// lattices, boards at the limits of the sequence tests, duplicates, collinear and tiny sets, outliers inside the
+// lattice -- with both sides starting every neighbour ring at the same neighbour (GridPerturbation::
+// canonical_start below); tests/test_gpu_grid_reference.py does the same for the device's candidates.
+// The neighbour structure below is the Delaunay triangulation of the integer points (the dual of that Voronoi
+// diagram) with exact integer predicates; neighbours of a site are visited counter-clockwise (in the x,y plane as
+// numbers) like boost's edge->next(), sites in boost's cell order (sorted by x, then y).  Not pinned: boost's own
+// construction of the diagram, and where boost starts a cell's ring (incident_edge()), which decides "the first
+// neighbour that matches" (find_grid.cc:216-222) on ambiguous sets; on clean boards exactly one neighbour matches,
+// and the final grid is fixed by geometry (unique 4-cycles, clockwise test, top edge), not by visiting order.
+// Exactly cocircular quadruples (a degenerate Voronoi vertex) have NO neighbourhood across the circle in the Voronoi
+// diagram; the triangulation has to put a diagonal there, and build_site_graph leaves it out of the rings.  "This
+// neighbour and the next close a triangle" and "the site beyond it" are read as find_grid.cc:123 and :127 read them,
+// off the neighbour's own ring, closed on the hull like boost's: off the triangulation where both faces are plain
+// triangles (the same answer, cheaper), off the rings where a flat edge or the hull is involved.  Pinned by the
+// cocircular_* family (outcomes: a finder that keeps the diagonals fails it) and, site by site, by the comparison of
+// the adjacency lists with the reference's iteration over the stand-in's rings (tests/test_oracle_grid.py).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -36,14 +46,16 @@
 
 namespace mrg {
 
-// Test hook (mrgingham_amd_find_grid_from_points_perturbed): the two things about the reference's visiting
-// order that cannot be checked against boost here.  ring_seed != 0 starts every site's neighbour ring at a
-// pseudo-random position (boost's incident_edge() start is an implementation detail); last_match takes the
-// LAST neighbour that continues a sequence instead of the first (find_grid.cc:216-222).  The tests assert
-// that neither changes any result.
+// Test hook (mrgingham_amd_find_grid_from_points_perturbed): the visiting order.  ring_seed != 0 starts every
+// site's neighbour ring at a pseudo-random position (boost's incident_edge() start is an implementation detail);
+// last_match takes the LAST neighbour that continues a sequence instead of the first (find_grid.cc:216-222):
+// tests/test_grid.py asserts that neither changes any result on clean candidate sets.  canonical_start starts
+// every ring at the first neighbour counter-clockwise from +x (+x included; ring_seed then rotates from there),
+// the rule of the stand-in diagram that the parity tests run the reference's find_grid.cc on: with it both sides
+// visit in the same order and are compared bit for bit (tests/test_oracle_grid.py).  Off unless the hook sets it.
 thread_local GridDebugSequence g_grid_debug_sequence = {false, 0, 0};
 thread_local bool g_grid_debug = false;
-thread_local GridPerturbation g_grid_perturbation{0u, false};
+thread_local GridPerturbation g_grid_perturbation{0u, false, false};
 thread_local GridPhaseClock g_grid_clock = {0, 0, 0, 0, 0, 0};
 
 namespace {
@@ -266,64 +278,110 @@ private:
 struct SiteGraph {
     std::vector<int> order;  // sites in cell order
     std::vector<int> off;    // n + 1
-    std::vector<int> nbr;    // neighbour sites, counter-clockwise
-    std::vector<char> tri;   // tri[k]: (site, nbr[k], nbr[k+1]) is a triangle
-    std::vector<int> far;    // far[k]: the site opposite `site` across edge (nbr[k], nbr[k+1]), or -1
+    std::vector<int> nbr;    // neighbour sites, counter-clockwise; the ring is closed, on the hull too (boost links
+                             // the two infinite edges of a hull cell to each other)
+    std::vector<char> tri;   // tri[k]: nbr[k+1] is also what precedes `site` in the ring of nbr[k] (:123)
+    std::vector<int> far;    // far[k]: what precedes nbr[k+1] in the ring of nbr[k] (:127), where tri[k]
 };
 
 bool build_site_graph(const std::vector<PointI>& pts, SiteGraph& g) {
     Delaunay dt(pts);
     if (!dt.build()) return false;
     const int n = (int)pts.size();
+    const int ntri = (int)dt.tris.size();
     g.order = dt.order;
     g.off.assign((size_t)n + 1, 0);
     const size_t guess = 3 * dt.tris.size() + (size_t)n;
     g.nbr.clear(); g.tri.clear(); g.far.clear();
     g.nbr.reserve(guess); g.tri.reserve(guess); g.far.reserve(guess);
+    // Two sites are neighbours in the Voronoi diagram when their edge has positive length: the edge between two
+    // triangles whose four sites lie on one circle is a degenerate Voronoi vertex, not a neighbourhood.  A
+    // triangulation has to put a diagonal there; the rings leave it out, like boost's diagram.
+    std::vector<char> flat((size_t)3 * ntri, 0);  // flat[3 t + k]: the edge of t opposite its slot k is such a diagonal
+    for (int t = 0; t < ntri; ++t)
+        for (int k = 0; k < 3; ++k) {
+            const int u = dt.tris[t].n[k];
+            if (u < t) continue;  // hull, or looked at from the other side
+            int ku = -1;
+            for (int j = 0; j < 3; ++j)
+                if (dt.tris[u].n[j] == t && dt.tris[u].v[(j + 1) % 3] == dt.tris[t].v[(k + 2) % 3]) ku = j;
+            if (ku < 0) continue;
+            if (incircle(pts[dt.tris[t].v[0]], pts[dt.tris[t].v[1]], pts[dt.tris[t].v[2]], pts[dt.tris[u].v[ku]]) == 0)
+                flat[3 * t + k] = flat[3 * u + ku] = 1;
+        }
     // one incident triangle per vertex, preferring one whose clockwise side is open (hull start)
     std::vector<int> inc(n, -1);
-    for (int t = 0; t < (int)dt.tris.size(); ++t)
+    for (int t = 0; t < ntri; ++t)
         for (int k = 0; k < 3; ++k) {
             const int v = dt.tris[t].v[k];
             // the edge (v, v_next) is opposite slot (k+2)%3; the edge (v_prev, v) opposite (k+1)%3.
             // rotating clockwise around v crosses edge (v, v[k+1]) -> neighbour n[(k+2)%3]
             if (inc[v] < 0 || dt.tris[t].n[(k + 2) % 3] < 0) inc[v] = t;
         }
+    // tri / far of an entry are read off the triangulation where the faces on both sides are plain triangles, and
+    // off the rings (below) where a flat edge or the hull is involved: `later` lists those entries
+    std::vector<int> later;
+    auto push = [&](int site) { g.nbr.push_back(site); g.tri.push_back(0); g.far.push_back(-1); };
     for (int v = 0; v < n; ++v) {
         g.off[v] = (int)g.nbr.size();
         if (inc[v] < 0) continue;  // duplicate of another point: no cell of its own
-        const size_t first = g.nbr.size();
         // walk counter-clockwise around v starting at inc[v]
         int t = inc[v];
         const int t_first = t;
-        bool closed = false;
+        int open = -1;    // the entry whose step to the next neighbour is being walked
+        int open_t = -1;  // the triangle that step crosses, -1 once it has crossed more than one (a face of flat edges)
         while (true) {
             int k = 0;
             while (dt.tris[t].v[k] != v) ++k;
-            const int b = dt.tris[t].v[(k + 1) % 3], c = dt.tris[t].v[(k + 2) % 3];
-            if (g.nbr.size() == first) g.nbr.push_back(b);
-            g.tri.push_back(1);
-            // far vertex across (b,c): the triangle opposite v
-            const int u = dt.tris[t].n[k];
-            int d = -1;
-            if (u >= 0)
-                for (int j = 0; j < 3; ++j)
-                    if (dt.tris[u].v[j] != b && dt.tris[u].v[j] != c) d = dt.tris[u].v[j];
-            g.far.push_back(d);
-            // next triangle counter-clockwise: across edge (v, c), which is opposite slot (k+1)%3
+            // the edge (v, b) is opposite slot (k+2)%3, the edge (v, c) opposite (k+1)%3, the edge (b, c) opposite k
+            const bool eb = !flat[3 * t + (k + 2) % 3], ec = !flat[3 * t + (k + 1) % 3];
+            if (t == t_first && open < 0 && eb && g.nbr.size() == (size_t)g.off[v]) push(dt.tris[t].v[(k + 1) % 3]);
+            if (eb) { open = (int)g.nbr.size() - 1; open_t = t; }
+            else open_t = -1;
+            if (ec && open >= 0 && open_t == t && !flat[3 * t + k]) {
+                // the step from b to c crosses this triangle alone, and b and c are neighbours
+                g.tri[open] = 1;
+                const int u = dt.tris[t].n[k];
+                int j = -1;
+                if (u >= 0)
+                    for (int q = 0; q < 3; ++q)
+                        if (dt.tris[u].n[q] == t && dt.tris[u].v[(q + 1) % 3] == dt.tris[t].v[(k + 2) % 3]) j = q;
+                // u = (d, c, b): d precedes c in the ring of b when (b, d), opposite c, is no flat edge
+                if (j >= 0 && !flat[3 * u + (j + 1) % 3]) g.far[open] = dt.tris[u].v[j];
+                else later.push_back(open);
+            }
+            // next triangle counter-clockwise: across edge (v, c)
             const int nx = dt.tris[t].n[(k + 1) % 3];
-            if (nx == t_first) { closed = true; break; }
-            g.nbr.push_back(c);
+            if (nx == t_first) break;
+            if (ec) push(dt.tris[t].v[(k + 2) % 3]);
             if (nx < 0) break;
             t = nx;
         }
-        if (!closed) {
-            // hull site: the step from the last neighbour back to the first has no triangle
-            g.tri.push_back(0);
-            g.far.push_back(-1);
-        }
+        // (hull site: the step from the last neighbour back to the first keeps tri = 0.  The reference's closed
+        // ring would have it looked up, but that step turns by half a turn or more: a longer one fails :118, and at
+        // exactly half a turn the site lies between the two neighbours, which therefore are none of each other)
     }
     g.off[n] = (int)g.nbr.size();
+    // what the reference reads off the twin's ring (:123, :127)
+    {
+        std::vector<int> site_of_entry;
+        if (!later.empty()) {
+            site_of_entry.resize(g.nbr.size());
+            for (int v = 0; v < n; ++v)
+                for (int e = g.off[v]; e < g.off[v + 1]; ++e) site_of_entry[e] = v;
+        }
+        for (int e : later) {
+            const int v = site_of_entry[e];
+            const int deg = g.off[v + 1] - g.off[v], k = e - g.off[v];
+            const int b = g.nbr[e], c = g.nbr[g.off[v] + (k + 1) % deg];
+            const int* rb = g.nbr.data() + g.off[b];
+            const int degb = g.off[b + 1] - g.off[b];
+            int p = 0;
+            while (rb[p] != v) ++p;
+            g.tri[e] = rb[(p + degb - 1) % degb] == c;
+            g.far[e] = g.tri[e] ? rb[(p + 2 * degb - 2) % degb] : -1;
+        }
+    }
     return true;
 }
 
@@ -337,10 +395,20 @@ bool for_each_adjacent(const SiteGraph& g, const std::vector<PointI>& pts, int c
     const int deg = g.off[c + 1] - g.off[c];
     const PointI& pt = pts[c];
     int start = 0;
+    if (g_grid_perturbation.canonical_start) {
+        // the neighbour with the smallest direction angle in [0, 2 pi) from +x
+        auto lower_half = [](i64 dx, i64 dy) { return !(dy > 0 || (dy == 0 && dx > 0)); };
+        for (int k = 1; k < deg; ++k) {
+            const i64 ax = pts[r.nbr[k]].x - pt.x, ay = pts[r.nbr[k]].y - pt.y;
+            const i64 bx = pts[r.nbr[start]].x - pt.x, by = pts[r.nbr[start]].y - pt.y;
+            const bool ha = lower_half(ax, ay), hb = lower_half(bx, by);
+            if (ha != hb ? hb : ax * by - ay * bx > 0) start = k;
+        }
+    }
     if (g_grid_perturbation.ring_seed && deg > 0) {
         uint32_t hsh = (uint32_t)c * 2654435761u ^ g_grid_perturbation.ring_seed;
         hsh ^= hsh >> 15; hsh *= 0x2c1b3c6du; hsh ^= hsh >> 12;
-        start = (int)(hsh % (uint32_t)deg);
+        start = (start + (int)(hsh % (uint32_t)deg)) % deg;
     }
     for (int kk = 0; kk < deg; ++kk) {
         const int k = (kk + start) % deg;

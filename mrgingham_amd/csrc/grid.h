@@ -33,8 +33,8 @@ struct GridPhaseClock { double graph_t, adjacency_t, sequences_t, cycles_t; long
 extern thread_local GridPhaseClock g_grid_clock;
 double grid_clock_tick_us();
 
-// visiting-order perturbations for the insensitivity tests (see grid.cpp); thread-local, default off
-struct GridPerturbation { unsigned ring_seed; bool last_match; };
+// visiting order for the insensitivity and the parity tests (see grid.cpp); thread-local, default off
+struct GridPerturbation { unsigned ring_seed; bool last_match; bool canonical_start; };
 extern thread_local GridPerturbation g_grid_perturbation;
 
 }  // namespace mrg

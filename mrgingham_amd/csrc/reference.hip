@@ -527,9 +527,9 @@ bool mrgingham_amd_find_grid_from_points_traced(const int* xy_scaled, int npoint
 /* Test hook: the same with the visiting order perturbed (grid.h, GridPerturbation). */
 bool mrgingham_amd_find_grid_from_points_perturbed(const int* xy_scaled, int npoints, int gridn, double* xy_out,
                                                    unsigned ring_seed, int last_match) {
-    g_grid_perturbation = GridPerturbation{ring_seed, last_match != 0};
+    g_grid_perturbation = GridPerturbation{ring_seed, (last_match & 1) != 0, (last_match & 2) != 0};
     const bool ok = mrgingham_amd_find_grid_from_points(xy_scaled, npoints, gridn, xy_out);
-    g_grid_perturbation = GridPerturbation{0u, false};
+    g_grid_perturbation = GridPerturbation{0u, false, false};
     return ok;
 }
 

@@ -33,6 +33,18 @@
  *     cv::resize computes nothing and hands upstream the level image the caller
  *     supplies, so the pin covers the component search and the coordinate
  *     scaling at every level, and the whole path at level 0 only.
+ *   - grid finder (find_grid.cc): no restatement in this file -- the product's
+ *     own host code (mrgingham_amd/csrc/grid.cpp) is held to the upstream file
+ *     directly.  PINNED through a stand-in Voronoi diagram: oracle/Makefile
+ *     (target `ref`) compiles find_grid.cc unmodified, where it lies, against
+ *     oracle/ref_stub/boost/polygon/voronoi.hpp (our own exact diagram of
+ *     integer sites; only the names upstream uses) behind
+ *     oracle/grid_ref_harness.cc into oracle/_ref/libgrid_ref.so;
+ *     tests/test_oracle_grid.py compares boards and refusals bit for bit and
+ *     tests/golden/grid_kat.npz holds upstream's recorded answers
+ *     (tests/golden/make_grid_golden.py).  NOT part of this pin: boost's own
+ *     construction of the diagram (the stand-in is checked against Qhull and
+ *     hand-written rings), boost's choice of incident_edge(), the debug dumps.
  *   - level decimation (cv::resize INTER_LINEAR) and box blur (cv::blur):
  *     PARITY UNPINNED.  The arithmetic lives in OpenCV (un-vendored, version
  *     unpinned by upstream: "opencv >= 3.2", packaging/mrgingham.spec:12).  The

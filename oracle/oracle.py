@@ -16,6 +16,7 @@ _LIB = os.path.join(_HERE, "liboracle.so")
 _REF = os.path.join(_HERE, "_ref", "libchess_ref.so")
 _REF_FCC = os.path.join(_HERE, "_ref", "libfcc_ref.so")
 _REF_FCC_RESP = os.path.join(_HERE, "_ref", "libfcc_resp_ref.so")
+_REF_GRID = os.path.join(_HERE, "_ref", "libgrid_ref.so")
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _i16p = ctypes.POINTER(ctypes.c_int16)
@@ -29,7 +30,7 @@ def build(force=False):
     if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(
             os.path.getmtime(os.path.join(_HERE, f)) for f in ("mrgingham_oracle.c", "blobs_oracle.c", "cpu_bench.c")):
         subprocess.check_call(["make", "-s", "-C", _HERE, "all"], stdout=sys.stderr)
-    elif not all(os.path.exists(p) for p in (_REF, _REF_FCC, _REF_FCC_RESP)) and os.path.exists("/root/reference/ChESS.c"):
+    elif not all(os.path.exists(p) for p in (_REF, _REF_FCC, _REF_FCC_RESP, _REF_GRID)) and os.path.exists("/root/reference/ChESS.c"):
         subprocess.check_call(["make", "-s", "-C", _HERE, "ref"], stdout=sys.stderr)
 
 
@@ -343,6 +344,70 @@ def ref_chain(image, start_level=3, level_images=None):
         if n <= 0:
             break
     return pts, lv
+
+
+# ---- the upstream find_grid.cc itself (oracle/_ref/libgrid_ref.so) ---------------------------------------------
+# Compiled against oracle/ref_stub/boost/polygon/voronoi.hpp: the sequence, cycle and ordering logic is upstream's,
+# the Voronoi diagram it walks is this project's stand-in (exact, built cell by cell; tests/test_oracle_grid.py checks it
+# against Qhull and against answers written out by hand).  ring_start chooses where every cell's neighbour ring
+# begins: 0 = at the first neighbour counter-clockwise from +x, else rotated from there by the hash of the product's
+# ring_seed.
+
+def have_reference_grid():
+    """The build of the upstream find_grid.cc (oracle/Makefile, target `ref`) is present."""
+    return os.path.exists(_REF_GRID)
+
+
+_grid = None
+
+
+def _grid_lib():
+    global _grid
+    if _grid is None:
+        R = ctypes.CDLL(_REF_GRID)
+        R.grid_ref_find.argtypes = [_f64p, _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
+        R.grid_ref_rings.argtypes = [_i32p, ctypes.c_int, ctypes.c_uint, ctypes.POINTER(ctypes.c_int), _i32p, _i32p,
+                                     ctypes.c_int] + [_i32p] * 5 + [ctypes.c_int]
+        _grid = R
+    return _grid
+
+
+def ref_find_grid(points, gridn, ring_start=0):
+    """mrgingham::find_grid_from_points(points, gridn, debug = false) by upstream's own code: int (N,2) candidates
+    x1000 -> float64 (gridn*gridn, 2) in board order, or None."""
+    pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)
+    out = np.empty((gridn * gridn, 2), dtype=np.float64)
+    rc = _grid_lib().grid_ref_find(out.ctypes.data_as(_f64p), pts.ctypes.data_as(_i32p), len(pts), int(gridn),
+                                   int(ring_start) & 0xffffffff)
+    if rc < 0:
+        raise ValueError("grid_ref_find: bad arguments (gridn < 2, or a coordinate beyond +-2^28)")
+    return out if rc == 1 else None
+
+
+def ref_grid_rings(points, ring_start=0):
+    """The stand-in Voronoi diagram of `points` by itself -> dict of int arrays:
+    cell_source[c] (source_index of cell c, cells in diagram order), cell_first[c] (its incident edge, -1 = none),
+    and per edge, numbered in ring order from each cell's incident edge: edge_cell, edge_nbr (the cell across),
+    edge_twin, edge_next, edge_prev (indices; -1 = a null pointer)."""
+    pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)
+    n = len(pts)
+    ecap = max(16, 8 * n)
+    while True:
+        nc = ctypes.c_int(0)
+        cells = [np.full(max(n, 1), -1, np.int32) for _ in range(2)]
+        edges = [np.full(ecap, -1, np.int32) for _ in range(5)]
+        ne = _grid_lib().grid_ref_rings(pts.ctypes.data_as(_i32p), n, int(ring_start) & 0xffffffff, ctypes.byref(nc),
+                                        cells[0].ctypes.data_as(_i32p), cells[1].ctypes.data_as(_i32p), max(n, 1),
+                                        *[e.ctypes.data_as(_i32p) for e in edges], ecap)
+        if ne < 0:
+            raise ValueError("grid_ref_rings: a coordinate beyond +-2^28")
+        if ne <= ecap:
+            break
+        ecap = ne
+    out = {"cell_source": cells[0][:nc.value], "cell_first": cells[1][:nc.value]}
+    for k, e in zip(("edge_cell", "edge_nbr", "edge_twin", "edge_next", "edge_prev"), edges):
+        out[k] = e[:ne]
+    return out
 
 
 def find_blobs(image):

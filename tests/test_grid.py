@@ -1,35 +1,15 @@
 """CPU tests of the host-side grid finder (mrgingham_amd/csrc/grid.cpp, the restatement of
-find_grid.cc).  The reference ships no test for it and needs boost to build, so these are
-geometric ground-truth tests: known boards in, the same corners in board order out."""
+find_grid.cc).  These are the geometric ground-truth tests: known boards in, the same corners in
+board order out, under every visiting order.  Parity with the reference's own find_grid.cc (compiled
+against a stand-in Voronoi diagram) is tests/test_oracle_grid.py; the board generators, shared with it,
+are in tests/grid_cases.py."""
 import numpy as np
 import pytest
 
 import mrgingham_amd
 from mrgingham_amd import synth
 from oracle import oracle
-
-
-def _board(gridn, H, jitter=0.0, seed=0, outliers=0, shuffle=True, origin=(400.0, 300.0), pitch=60.0):
-    """gridn x gridn corners through a homography (mild perspective + rotation), as x1000 ints."""
-    rng = np.random.RandomState(seed)
-    ii, jj = np.meshgrid(np.arange(gridn), np.arange(gridn), indexing="ij")       # ii = row, jj = column
-    p = np.stack([jj.ravel() * pitch, ii.ravel() * pitch, np.ones(gridn * gridn)])
-    q = H @ p
-    xy = (q[:2] / q[2]).T + np.array(origin)
-    xy = xy + rng.normal(0, jitter, xy.shape)
-    truth = np.round(xy * 1000).astype(np.int64)
-    pts = truth.copy()
-    if outliers:
-        lo, hi = truth.min(0) - 200000, truth.max(0) + 200000
-        pts = np.concatenate([pts, np.stack([rng.randint(lo[0], hi[0], outliers), rng.randint(lo[1], hi[1], outliers)], 1)])
-    if shuffle:
-        pts = pts[rng.permutation(len(pts))]
-    return pts.astype(np.int32), truth
-
-
-def _rot(deg):
-    a = np.deg2rad(deg)
-    return np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1.0]])
+from tests.grid_cases import _board, _random_board, _rot
 
 
 @pytest.mark.parametrize("gridn", [3, 6, 10, 14])
@@ -113,36 +93,6 @@ def _perturbed_equal(pts, gridn, base):
     return True
 
 
-def _random_board(rng, trial, clean):
-    gridn = int(rng.choice([4, 6, 10, 10, 14]))
-    Hm = _rot(rng.uniform(-35, 35))
-    Hm[2, 0], Hm[2, 1] = rng.uniform(-3e-4, 3e-4), rng.uniform(-3e-4, 3e-4)
-    jitter = float(rng.choice([0.0, 0.2, 0.5, 1.0]))
-    pts, truth = _board(gridn, Hm, jitter=jitter, seed=10000 + trial, outliers=int(rng.choice([0, 5, 30, 60])),
-                        origin=(2000.0, 2000.0))
-    # local pitch: distance to the nearest other lattice point
-    d = np.sqrt(((truth[:, None, :] - truth[None, :, :]).astype(np.float64) ** 2).sum(-1))
-    np.fill_diagonal(d, np.inf)
-    pitch = d.min(1)
-    is_truth = (pts[:, None, :] == truth[None, :, :]).all(-1).any(1)
-    if clean:
-        # keep only the outliers that are at least 1.5 local pitches away from every lattice point
-        dist = np.sqrt(((pts[:, None, :] - truth[None, :, :]).astype(np.float64) ** 2).sum(-1))
-        far = (dist > 1.5 * pitch[None, :]).all(1)
-        pts = pts[is_truth | far]
-        if trial % 3 == 1:                                     # exact duplicates of a few candidates
-            pts = np.concatenate([pts, pts[:5]])
-    else:
-        kind = trial % 3
-        if kind == 0:                                          # split blobs: a twin 3-8 % of the pitch away
-            k = rng.randint(0, len(truth), 3)
-            pts = np.concatenate([pts, (truth[k] + rng.randint(2000, 5000, (3, 2))).astype(np.int32)])
-        elif kind == 1:                                        # near-duplicates a fraction of a pixel away
-            pts = np.concatenate([pts, pts[:5] + rng.randint(-300, 300, (5, 2)).astype(np.int32)])
-        # kind 2: the outliers inside the lattice are the ambiguity
-    return gridn, jitter, pts.astype(np.int32), truth, pitch
-
-
 def test_visiting_order_does_not_matter_on_clean_candidate_sets():
     """500 randomised boards (rotation, perspective, jitter up to 1.7 % of the pitch, up to 60 outliers kept
     at least 1.5 pitches away from the lattice, exact duplicates): the board is found, equals the generating
@@ -168,8 +118,8 @@ def test_visiting_order_does_not_matter_on_clean_candidate_sets():
 def test_ambiguous_candidate_sets_are_order_dependent_but_never_wrong():
     """Split blobs, near-duplicates and outliers INSIDE the lattice: here the reference's own answer depends
     on boost's visiting order ("the first neighbour that matches", find_grid.cc:216-222), so does this one's
-    (measured below: a few percent of such sets), and parity for them is unpinned by construction.  What
-    must hold under every order: a reported board is the right board -- every corner within a quarter of
+    (measured below: a few percent of such sets); parity for them is pinned with both sides visiting in the same
+    order (tests/test_oracle_grid.py), never across orders.  What must hold under every order: a reported board is the right board -- every corner within a quarter of
     the local pitch of the generating lattice point (it may be the twin of a split blob or an outlier that
     fell next to a corner), in board order."""
     rng = np.random.RandomState(77)
