@@ -93,7 +93,11 @@ extern "C" {
  *      Later, additive (the version stays 4): mrgingham_amd_colour_grey_image, _colour_grey_batch, _colour_grey_geometry and
  *      the MRGINGHAM_AMD_COLOUR_* formats (colour frames -- interleaved RGB / BGR with 3 or 4 samples, planar, packed YUV
  *      4:2:2 -- to grey frames of the same sample type, on the host and on the device).  No earlier call, option or default
- *      changes; no file reader and no tool option takes such frames. */
+ *      changes; no file reader and no tool option takes such frames.
+ *      Later, additive (the version stays 4): mrgingham_amd_find_grids_batch, _find_grids_host, _find_grids_geometry,
+ *      _find_grids_stats, the MRGINGHAM_AMD_GRID_DECLINE_* statuses and the options "find_boards_grid" and
+ *      "find_grids_guard_bits" (the grid finder on the device: candidate lists to board indices).  No earlier call or
+ *      default changes: find_boards keeps the host finder unless the option asks for the device's. */
 #define MRGINGHAM_AMD_ABI_VERSION 4
 
 /* ------------------------------------------------------------------------ */
@@ -1271,6 +1275,55 @@ int mrgingham_amd_find_boards_stats(mrgingham_amd_ctx* ctx, double* out, int n, 
  * out6 = calls, found, then the four microsecond sums. */
 int mrgingham_amd_grid_clock(double* out6, int reset);
 
+/* THE GRID FINDER ON THE DEVICE.  Candidate lists that lie in device memory -- what mrgingham_amd_detect_batch leaves:
+ * d_xy = nlists blocks of `capacity` interleaved (x, y) * 1000 int pairs, d_counts[l] = candidates of list l -- to boards
+ * as INDICES: d_index = nlists blocks of gridn * gridn candidate indices in board order (rows top to bottom, each left to
+ * right; -1 throughout where the status is not 1), d_status[l] =
+ *    1  board found          0  the host finder would find none          < 0  declined: the list is the host finder's
+ *   MRGINGHAM_AMD_GRID_DECLINE_COUNT (-1)  more candidates than the device takes (mrgingham_amd_find_grids_geometry),
+ *                                          or count > capacity, or count < 0
+ *   MRGINGHAM_AMD_GRID_DECLINE_RING  (-2)  a degenerate neighbour structure the kernel does not resolve
+ *   MRGINGHAM_AMD_GRID_DECLINE_GUARD (-3)  a floating-point decision of the sequence walk inside the guard band
+ *   MRGINGHAM_AMD_GRID_DECLINE_TABLE (-4)  a table or a loop bound of the kernel was exceeded
+ *   MRGINGHAM_AMD_GRID_DECLINE_COORD (-5)  a coordinate with |x| or |y| >= 2^24
+ * The corners of a board are xy[index] / 1000.0 (find_grid.cc:353-354): the device makes decisions and no double that
+ * anyone sees.  THE RULE: an answer (1 or 0, and the indices) is the one mrgingham_amd_find_grid_from_points_perturbed
+ * gives with canonical_start -- every neighbour ring started at the first neighbour counter-clockwise from +x, the one
+ * ring rule this finder has, under which the host finder is pinned to upstream's find_grid.cc; where the device cannot be
+ * sure of that it declines, and never answers differently.  The guard band: every comparison of the walk against 0.984,
+ * 0.7, 1.4 and +-0.35 (find_grid.cc:204-207) is made with a band of 2^-bits, option "find_grids_guard_bits" (8 .. 45,
+ * default 33: 1.2e-10 where the host's hypot and the device's sqrt move a quotient by some 1e-16); a value inside the band
+ * declines the whole list.  gridn 2 .. 16.  One workgroup of 256 lanes per list, one launch.
+ * Queued like mrgingham_amd_detect_batch: on the context's streams, behind what mrgingham_amd_after_stream has named and
+ * behind earlier calls of the context that touch the same buffers; mrgingham_amd_stream_wait / _sync wait for it.  Grows
+ * context scratch (a slot of rings and adjacency lists per workgroup).  Completes find_boards jobs in flight first.
+ * MRGINGHAM_AMD_ERR_ARG, nothing queued: a NULL pointer, gridn outside 2 .. 16, a negative nlists or capacity. */
+enum {
+    MRGINGHAM_AMD_GRID_DECLINE_COUNT = -1,
+    MRGINGHAM_AMD_GRID_DECLINE_RING = -2,
+    MRGINGHAM_AMD_GRID_DECLINE_GUARD = -3,
+    MRGINGHAM_AMD_GRID_DECLINE_TABLE = -4,
+    MRGINGHAM_AMD_GRID_DECLINE_COORD = -5
+};
+int mrgingham_amd_find_grids_batch(mrgingham_amd_ctx* ctx, const int32_t* d_xy, const int32_t* d_counts, int nlists, int capacity,
+                                   int gridn, int32_t* d_index, int32_t* d_status);
+/* The same text (csrc/grid_phases.h) run serially on the host, over lists in host memory: no device, no context.  It equals
+ * the kernel list for list, every status and decline reason included -- both make the same IEEE operations --, and is what
+ * a debugger steps through when the two disagree.  guard_bits 8 .. 45.  Returns 0 or MRGINGHAM_AMD_ERR_ARG. */
+int mrgingham_amd_find_grids_host(const int32_t* xy, const int32_t* counts, int nlists, int capacity, int gridn, int guard_bits,
+                                  int32_t* index, int32_t* status);
+/* The caps of the kernel (each pointer may be NULL): lanes of a workgroup, candidates per list it takes, the gridn range,
+ * the workgroups of a launch (more lists take turns) and the bytes of context scratch each of them uses. */
+void mrgingham_amd_find_grids_geometry(int* lanes_per_workgroup, int* max_candidates, int* min_gridn, int* max_gridn,
+                                       int* max_workgroups, int64_t* scratch_bytes_per_workgroup);
+/* Lists the device finder of this context has answered since the last reset, in mrgingham_amd_find_grids_batch and in
+ * find_boards under option "find_boards_grid": out[0 .. n) receives up to MRGINGHAM_AMD_FIND_GRIDS_STATS doubles:
+ *   [0] lists   [1] found   [2] none   [3] .. [7] declined with -1 .. -5
+ *   [8] lists of find_boards jobs that the host finder answered because the device had declined them
+ * Synchronises; completes find_boards jobs in flight first.  Returns MRGINGHAM_AMD_FIND_GRIDS_STATS, or an error code. */
+#define MRGINGHAM_AMD_FIND_GRIDS_STATS 9
+int mrgingham_amd_find_grids_stats(mrgingham_amd_ctx* ctx, double* out, int n, int reset);
+
 /* find_blobs_from_image_array (find_blobs.cc:14-46) for every frame of a device-resident batch.
  * HOST outputs (the last stage of the detector runs on the host): h_xy = nframes blocks of capacity_per_frame
  * interleaved (x,y)*1000 int pairs in SimpleBlobDetector's output order, h_counts[f] = keypoints of frame f
@@ -1447,6 +1500,17 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         rounds, 3 the scan, 4 the write pass.  Results never depend on it.
  *   "find_boards_pipeline" 1 (default): mrgingham_amd_find_boards_batch / _submit / _collect as described there; 0: the
  *                         synchronous schedule (one level at a time for the whole batch, dense refinement) -- same results
+ *   "find_boards_grid"    0 (default): the grid finder of find_boards runs on the context's host threads; 1: the pipelined
+ *                         schedule orders the candidate lists of levels 3, 2 and 1 on the device, right behind their
+ *                         detection (mrgingham_amd_find_grids_batch), and the host threads take, per frame and level in the
+ *                         reference's order, the board from the indices (status 1), go on to the next level (0), or run
+ *                         the host finder on a list the device declined.  Frames re-detected at full capacity and the
+ *                         synchronous schedule ("find_boards_pipeline" 0) keep the host finder.  Under 1 EVERY host finder
+ *                         call of the job starts its neighbour rings at the canonical neighbour (the first one
+ *                         counter-clockwise from +x), so that one call has one ring rule: on clean candidate sets this
+ *                         changes no board (tests/test_grid.py), on ambiguous ones the ring start was never pinned.
+ *   "find_grids_guard_bits"  8 .. 45 (default 33): the guard band of the device grid finder is 2^-bits
+ *                         (mrgingham_amd_find_grids_batch); a wider band declines more lists and changes no answer.
  *   "chess_seg", "chess16_seg"  rows per workgroup of the ChESS kernels of THIS context (chess_v1* / chess_v16; 0 = cost model,
  *                         the default): the frame is cut into ceil(height / value) row segments of equal height (whole
  *                         8- / 16-row groups); results do not depend on it
@@ -1466,7 +1530,7 @@ int mrgingham_amd_chain_info(const mrgingham_amd_ctx* ctx, int* fused_pyramid, i
  *                         Results never depend on it: no call reads scratch it has not written.
  *   "scratch_fill_now"    test hook, a one-shot: completes what is in flight, then fills every scratch buffer the context
  *                         owns with the byte given (0..255) -- not the few words that are state between calls (status
- *                         and hot-count words, the sparse-fallback counter, the clock probe's sums).  Results never depend on it.
+ *                         and hot-count words, the sparse-fallback counter, the clock probe's sums, the grid finder's counters).  Results never depend on it.
  * Builds made with -DMRG_EXPERIMENT (make -C mrgingham_amd/csrc EXPERIMENT=1 -> libmrgingham_amd_experiment.so)
  * additionally accept the timing ablations and phase clocks of tools/ ("cc_lds" bits 2, 4, 8, 16, 128, 512,
  * "cc_schedule", "chess_stage", "chess_multi_min_blocks", "chess_v0" = the reference-shaped ChESS kernel as an on-device

@@ -91,6 +91,8 @@ EXPORTS = [
     "mrgingham_amd_raw_unpack_geometry",
     "mrgingham_amd_bayer_grey_image", "mrgingham_amd_bayer_grey_batch", "mrgingham_amd_bayer_grey_geometry",
     "mrgingham_amd_colour_grey_image", "mrgingham_amd_colour_grey_batch", "mrgingham_amd_colour_grey_geometry",
+    "mrgingham_amd_find_grids_batch", "mrgingham_amd_find_grids_host", "mrgingham_amd_find_grids_geometry",
+    "mrgingham_amd_find_grids_stats",
 ]
 
 
@@ -264,6 +266,12 @@ def lib():
                                                       ctypes.c_int64, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]
         L.mrgingham_amd_colour_grey_geometry.argtypes = [ctypes.POINTER(c_int)] * 2
         L.mrgingham_amd_colour_grey_geometry.restype = None
+    if hasattr(L, "mrgingham_amd_find_grids_batch"):
+        L.mrgingham_amd_find_grids_batch.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]
+        L.mrgingham_amd_find_grids_host.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]
+        L.mrgingham_amd_find_grids_geometry.argtypes = [ctypes.POINTER(c_int)] * 5 + [ctypes.POINTER(ctypes.c_int64)]
+        L.mrgingham_amd_find_grids_geometry.restype = None
+        L.mrgingham_amd_find_grids_stats.argtypes = [c_vp, c_vp, c_int, c_int]
     L.mrgingham_amd_device_for_thread.argtypes = [c_int, c_int, ctypes.c_char_p]
     L.mrgingham_amd_set_thread_device.argtypes = [c_int]
     L.mrgingham_amd_host_alloc.argtypes = [ctypes.c_size_t]

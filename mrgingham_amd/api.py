@@ -766,6 +766,48 @@ def find_grid_from_points_perturbed(points_scaled, gridn=10, ring_seed=0, last_m
     return out if ok else None
 
 
+# statuses below 0 of the device grid finder and its host model: the list is the host finder's (include/mrgingham_amd.h)
+GRID_DECLINES = {-1: "count", -2: "ring", -3: "guard", -4: "table", -5: "coordinate"}
+
+
+def find_grids_host(xy, counts, gridn=10, guard_bits=33):
+    """The host model of the device grid finder (mrgingham_amd_find_grids_host; no device): candidate lists xy int32
+    [nlists, capacity, 2] (pixel coordinates * 1000) with counts int32 [nlists] -> (index int32 [nlists, gridn * gridn]
+    candidate indices in board order, -1 where there is no board; status int32 [nlists]: 1 board, 0 none, below 0
+    declined, GRID_DECLINES).  It answers what Detector.find_grids answers, list for list."""
+    xy = np.ascontiguousarray(xy, dtype=np.int32)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if xy.ndim != 3 or xy.shape[2] != 2 or xy.shape[0] != len(counts):
+        raise ValueError("find_grids_host: xy is [nlists, capacity, 2], counts is [nlists]")
+    nlists, capacity = xy.shape[0], xy.shape[1]
+    index = np.full((nlists, gridn * gridn), -1, dtype=np.int32)
+    status = np.zeros((nlists,), dtype=np.int32)
+    rc = _lib.lib().mrgingham_amd_find_grids_host(xy.ctypes.data, counts.ctypes.data, nlists, capacity, int(gridn), int(guard_bits),
+                                                  index.ctypes.data, status.ctypes.data)
+    if rc != 0:
+        raise ValueError("find_grids_host: gridn 2 .. 16, guard_bits 8 .. 45")
+    return index, status
+
+
+def find_grids_geometry():
+    """mrgingham_amd_find_grids_geometry as a dict: the caps of the device grid finder."""
+    v = [ctypes.c_int() for _ in range(5)]
+    b = ctypes.c_int64()
+    _lib.lib().mrgingham_amd_find_grids_geometry(*[ctypes.byref(x) for x in v], ctypes.byref(b))
+    names = ("lanes_per_workgroup", "max_candidates", "min_gridn", "max_gridn", "max_workgroups")
+    return dict(zip(names, (x.value for x in v)), scratch_bytes_per_workgroup=b.value)
+
+
+def boards_of_indices(xy, index, status):
+    """What find_grids / find_grids_host answered, as corners: float64 [nlists, gridn * gridn, 2] = xy[index] / 1000.0
+    (find_grid.cc:353-354) where status is 1, NaN rows elsewhere.  numpy arrays, or torch tensors (copied to the host)."""
+    xy, index, status = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (xy, index, status))
+    boards = np.full(index.shape + (2,), np.nan, dtype=np.float64)
+    for l in np.nonzero(status == 1)[0]:
+        boards[l] = xy[l][index[l]].astype(np.float64) / 1000.0
+    return boards
+
+
 def preprocess(image, clahe=True, blur_radius=1):
     """The CLI's preprocessing of an 8-bit image on the GPU (mrgingham-from-image.cc:71-111; the cv2
     recipe of find_board.docstring:8-10): normalize + CLAHE(8) when `clahe`, then a box blur of
@@ -1697,6 +1739,45 @@ class Detector:
         finally:
             self._fb_live.pop(job[0], None)
         return (job[1], job[2], job[4]) if len(job) > 4 else (job[1], job[2])
+
+    def find_grids(self, xy, counts, gridn=10, out=None, sync=True):
+        """The grid finder on the device (mrgingham_amd_find_grids_batch): candidate lists as detect() leaves them -- xy
+        int32 [nlists, capacity, 2], counts int32 [nlists], on the device -- to (index int32 [nlists, gridn * gridn],
+        status int32 [nlists]) on the device: candidate indices in board order (-1 where there is no board) and 1 = board
+        found, 0 = none, below 0 = declined (GRID_DECLINES): the list is the host finder's.  boards_of_indices turns them
+        into corners.  One launch, one workgroup per list.  `out` = (index, status) to write into; queued and ordered like
+        detect(out=): after_stream() in front where torch work still queued produces the lists, and with sync=False
+        stream_wait() or sync() before anybody reads the results."""
+        t = self.torch
+        assert xy.dtype == t.int32 and counts.dtype == t.int32 and xy.is_cuda and counts.is_cuda
+        assert xy.dim() == 3 and xy.shape[2] == 2 and xy.is_contiguous() and counts.is_contiguous() and counts.shape == (xy.shape[0],)
+        nlists, capacity = xy.shape[0], xy.shape[1]
+        if out is None:
+            index = t.empty((nlists, gridn * gridn), dtype=t.int32, device=xy.device)
+            status = t.empty((nlists,), dtype=t.int32, device=xy.device)
+            t.cuda.current_stream(xy.device).synchronize()  # inputs/outputs ready before the ctx streams run
+        else:
+            index, status = out
+            assert index.dtype == t.int32 and status.dtype == t.int32 and index.is_contiguous() and status.is_contiguous()
+            assert index.shape == (nlists, gridn * gridn) and status.shape == (nlists,)
+        self._check(self.L.mrgingham_amd_find_grids_batch(self.ctx, xy.data_ptr(), counts.data_ptr(), nlists, capacity, int(gridn),
+                                                          index.data_ptr(), status.data_ptr()))
+        if sync:
+            self.sync()
+        return index, status
+
+    FIND_GRIDS_STATS = ("lists", "found", "none", "declined_count", "declined_ring", "declined_guard", "declined_table",
+                        "declined_coordinate", "host_fallbacks")
+
+    def find_grids_stats(self, reset=True):
+        """mrgingham_amd_find_grids_stats as a dict: lists the device grid finder has answered since the last reset (in
+        find_grids and in find_boards under option "find_boards_grid"), by status, and the lists of find_boards jobs the
+        host finder answered because the device had declined them.  Synchronises."""
+        out = np.zeros(len(self.FIND_GRIDS_STATS), dtype=np.float64)
+        n = self.L.mrgingham_amd_find_grids_stats(self.ctx, out.ctypes.data, len(out), int(bool(reset)))
+        if n < 0:
+            self._check(n)
+        return dict(zip(self.FIND_GRIDS_STATS, out.tolist()))
 
     FB_STATS = ("batches", "host_threads", "ms_submit_checks", "ms_submit_prev_host_begin", "ms_submit_device_queued",
                 "ms_grid_finder_joined", "ms_refinement_queued", "ms_collect_wait_refinement", "ms_collect_boards_copied",

@@ -550,7 +550,7 @@ static int fill_scratch_now(mrgingham_amd_ctx* ctx, int byte) {
     MRG_HIP_CHECK(hipDeviceSynchronize());
     ctx->pixel_stage.valid = false;  // (mrgingham_amd_debug_pixel_products reads scratch)
     for (DevBuf* b : ctx->scratch_bufs) {
-        if (!b->p || b == &ctx->sparse_stat || b == &ctx->clk) continue;
+        if (!b->p || b == &ctx->sparse_stat || b == &ctx->clk || b == &ctx->grid_stat) continue;
         size_t skip = 0;  // counters2: the hot-count and status words stay, the path words behind them go
         for (const DevBuf& c : ctx->counters2)
             if (b == &c) skip = (size_t)(kMaxLevel + 1) * 2 * (size_t)ctx->counters_nf * sizeof(int32_t);
@@ -644,6 +644,16 @@ int mrgingham_amd_set_option(mrgingham_amd_ctx* ctx, const char* name, int value
     }
     if (!strcmp(name, "fuse_pyramid")) { ctx->fuse_pyramid = value != 0; return 0; }
     if (!strcmp(name, "find_boards_pipeline")) { ctx->fb_pipeline = value != 0; return 0; }
+    if (!strcmp(name, "find_boards_grid")) {
+        if (value != 0 && value != 1) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "find_boards_grid: 0 (the host grid finder) or 1 (the device's)");
+        ctx->fb_grid_device = value;
+        return 0;
+    }
+    if (!strcmp(name, "find_grids_guard_bits")) {
+        if (value < 8 || value > 45) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "find_grids_guard_bits: 8 .. 45");
+        ctx->find_grids_guard_bits = value;
+        return 0;
+    }
     if (!strcmp(name, "blob_chunk_frames")) {
         if (value < 0) return fail(ctx, MRGINGHAM_AMD_ERR_ARG, "blob_chunk_frames: 0 (by the scratch budget) or a frame count");
         ctx->blob_chunk_frames = value;

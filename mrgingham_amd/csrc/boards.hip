@@ -7,6 +7,7 @@
 #include <chrono>
 
 #include "ctx.h"
+#include "grid_phases.h"
 
 namespace mrg {
 
@@ -76,6 +77,14 @@ bool grid_of_candidates(const int32_t* xy, int n, int gridn, double* out, GridSc
     return true;
 }
 
+// Option "find_boards_grid" 1: every host finder call of such a job starts its neighbour rings at the canonical neighbour
+// (grid.cpp: GridPerturbation::canonical_start), the one ring rule of the device finder -- on this thread, while this lives
+struct CanonicalRings {
+    const bool saved = g_grid_perturbation.canonical_start;
+    explicit CanonicalRings(bool on) { if (on) g_grid_perturbation.canonical_start = true; }
+    ~CanonicalRings() { g_grid_perturbation.canonical_start = saved; }
+};
+
 static double fb_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static void add_elapsed_ms(double& total, hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
@@ -101,7 +110,7 @@ int host_threads(int nthreads) {
 // refinement_level array holds, mrgingham.cc:81-99); `do_refine` false: the boards stay as the grid finder made them.
 static int find_boards_sync_levels(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int gridn, int first, int last,
                                    double* h_boards, signed char* h_found_level, int nthreads, std::vector<int> open,
-                                   bool do_refine = true, signed char* h_levels = nullptr) {
+                                   bool do_refine = true, signed char* h_levels = nullptr, bool canonical = false) {
     int rc = 0;
     const int B = fr->nframes, N = gridn * gridn;
     const int cap = 4 * N + 64;  // candidates kept per frame for the grid finder
@@ -171,6 +180,7 @@ static int find_boards_sync_levels(mrgingham_amd_ctx* ctx, const mrgingham_amd_f
         std::atomic<int> next{0};
         auto worker = [&]() {
             GridScratch scratch;
+            const CanonicalRings rings(canonical);
             for (int k; (k = next.fetch_add(1)) < nb;) {
                 const int f = cur_idx[k];
                 if (h_found_level[f] >= 0 || h_cnt[k] < N) continue;
@@ -311,13 +321,19 @@ static void fb_grid_worker(mrgingham_amd_ctx::BoardsJob* job) {
     const int B = job->fr.nframes, N = job->gridn * job->gridn, cap = job->cap, nlev = job->nlev;
     const FbPinned pin = fb_layout(job->pin.p, nlev, B, cap, N);
     GridScratch scratch;
+    const CanonicalRings rings(job->grid_device);
+    // (with the device finder: its statuses and indices, [level][frame] like the counts)
+    const int32_t* const dev_st = job->grid_device ? (const int32_t*)job->pin_grid.p : nullptr;
+    const int32_t* const dev_idx = dev_st ? dev_st + fb_align((size_t)nlev * B * 4) / 4 : nullptr;
     const GridPhaseClock c0 = g_grid_clock;
     struct Leave {   // this thread's share of the batch's grid-finder time into the context's totals
         mrgingham_amd_ctx* ctx; GridPhaseClock c0;
+        long long fallbacks = 0;
         ~Leave() {
             if (!ctx) return;
             const GridPhaseClock& c = g_grid_clock;
             std::lock_guard<std::mutex> lk(ctx->fb_stat_mu);
+            ctx->fb_grid_fallbacks += fallbacks;
             ctx->fb_grid.graph_t += c.graph_t - c0.graph_t; ctx->fb_grid.adjacency_t += c.adjacency_t - c0.adjacency_t;
             ctx->fb_grid.sequences_t += c.sequences_t - c0.sequences_t; ctx->fb_grid.cycles_t += c.cycles_t - c0.cycles_t;
             ctx->fb_grid.calls += c.calls - c0.calls; ctx->fb_grid.found += c.found - c0.found;
@@ -329,7 +345,23 @@ static void fb_grid_worker(mrgingham_amd_ctx::BoardsJob* job) {
             if (n < N) continue;
             const std::vector<int32_t>& bg = job->big[(size_t)li * B + k];
             const int32_t* src = bg.empty() ? pin.xy + ((size_t)li * B + k) * cap * 2 : bg.data();
-            if (grid_of_candidates(src, n, job->gridn, job->h_boards + (size_t)k * N * 2, &scratch)) {
+            bool found;
+            const int st = dev_st && bg.empty() ? dev_st[(size_t)li * B + k] : -1;
+            if (st == 1) {  // the device's board: its candidates by index, scaled as find_grid.cc:353-354 scales them
+                const int32_t* idx = dev_idx + ((size_t)li * B + k) * N;
+                double* out = job->h_boards + (size_t)k * N * 2;
+                for (int i = 0; i < N; ++i) {
+                    out[2 * i] = (double)src[2 * idx[i]] / 1000.0;
+                    out[2 * i + 1] = (double)src[2 * idx[i] + 1] / 1000.0;
+                }
+                found = true;
+            } else if (st == 0) {
+                found = false;
+            } else {  // the host finder: no device finder, a list detected again at full capacity, or one the device declined
+                leave.fallbacks += dev_st && bg.empty();
+                found = grid_of_candidates(src, n, job->gridn, job->h_boards + (size_t)k * N * 2, &scratch);
+            }
+            if (found) {
                 job->h_found[k] = (signed char)job->levs[li];
                 if (job->h_levels) memset(job->h_levels + (size_t)k * N, job->levs[li], (size_t)N);
                 break;
@@ -483,7 +515,7 @@ static int fb_finish(mrgingham_amd_ctx* ctx, mrgingham_amd_ctx::BoardsJob& job) 
         mrgingham_amd_ctx* one = same_device_ctx(ctx);
         if (!one) return MRGINGHAM_AMD_ERR_DEVICE;
         rc = find_boards_sync_levels(one, &job.fr, job.gridn, lowest - 1, 0, job.h_boards, job.h_found, job.nthreads, open,
-                                     job.do_refine, job.h_levels);
+                                     job.do_refine, job.h_levels, job.grid_device);
         if (rc) ctx->err = one->err;
     }
     return rc;
@@ -540,7 +572,8 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
         std::vector<int> open(B);
         for (int f = 0; f < B; ++f) open[f] = f;
         fb_remember(ctx, ticket, find_boards_sync_levels(ctx, fr, gridn, first, last, h_boards, h_found_level, nthreads, open,
-                                                               do_refine, h_levels));
+                                                               do_refine, h_levels,
+                                                               ctx->fb_grid_device && !g_grid_debug && !g_grid_debug_sequence.on));
         return ticket;
     }
     // levels searched in the first pass: the one asked for, or 3, 2 and 1 (levels 2 and 1 speculatively: together they
@@ -549,6 +582,9 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
     const int top = image_pyramid_level >= 0 ? image_pyramid_level : 3;
     const int nlev = image_pyramid_level >= 0 ? 1 : 3;
     const int cap = 4 * N + 64;  // candidates kept per frame for the grid finder
+    // option "find_boards_grid": the lists of this pass are ordered on the device, behind their detection (not while the
+    // calling thread has the reference's debug dumps or its sequence trace on: those are the host finder's)
+    const bool grid_device = ctx->fb_grid_device && gridn <= kGfMaxGridn && !g_grid_debug && !g_grid_debug_sequence.on;
     // the refinement takes the sparse schedule where it pays: such a context keeps three scratch sets (choose_sets)
     if (sparse_possible(ctx, top)) ctx->sparse_seen = true;
     {   // a change of the rotation (another batch shape) synchronises and may free a set: no job may be in flight then
@@ -584,6 +620,12 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
             (rc = ensure(ctx, nj.d_pts0, fb_align((size_t)B * N * 16) + (size_t)B * N)))
             return rc;
         if ((rc = ensure_pinned(ctx, nj.pin, fb_layout(nullptr, nlev, B, cap, N).bytes, 4, false))) return rc;
+        if (grid_device) {  // statuses | indices of the device finder, one block on both sides
+            const size_t gb = fb_align((size_t)nlev * B * 4) + (size_t)nlev * B * N * 4;
+            if ((rc = ensure(ctx, nj.d_grid, gb)) || (rc = ensure_pinned(ctx, nj.pin_grid, gb, 4, false)) ||
+                (rc = ensure_find_grids(ctx, (ctx->cur + 1) % ctx->nsets, nlev * B)))
+                return rc;
+        }
         for (Event* e : {&nj.ev_a, &nj.ev_b, &nj.ev_a0, &nj.ev_b0}) MRG_HIP_CHECK(e->create(hipEventDefault));
     }
     begin_op(ctx, top);
@@ -602,6 +644,7 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
     job.h_levels = h_levels;
     job.do_refine = do_refine;
     job.refine_queued = false;
+    job.grid_device = grid_device;
     // The host part of the job before this one runs inside this call: its grid-finder threads are started first when
     // its candidates have already arrived (the steady state), so that they work while this thread queues the device
     // passes below; otherwise after them.
@@ -641,13 +684,21 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
         }
         launch_cc_detect_levels(lbs, dts, job.levs, douts, job.nlev, B, cc);
     }
+    int grid_rc = 0;
+    if (grid_device) {  // every list of the pass -- [level][frame], as the counts lie -- in one launch right behind it
+        int32_t* const d_st = (int32_t*)job.d_grid.p;
+        grid_rc = launch_find_grids(ctx, job.set, (const int32_t*)((char*)job.d_cnt.p + fb_align((size_t)job.nlev * B * 4)), (const int32_t*)job.d_cnt.p,
+                                    job.nlev * B, cap, gridn, d_st + fb_align((size_t)job.nlev * B * 4) / 4, d_st, cc);
+    }
     const FbPinned pin = fb_layout(job.pin.p, job.nlev, B, cap, N);
     if (e == hipSuccess)  // counts | candidates: one block on both sides
         e = hipMemcpyAsync(pin.cnt, job.d_cnt.p, fb_align((size_t)job.nlev * B * 4) + (size_t)job.nlev * B * cap * 8, hipMemcpyDeviceToHost, cc);
+    if (e == hipSuccess && grid_device)
+        e = hipMemcpyAsync(job.pin_grid.p, job.d_grid.p, fb_align((size_t)job.nlev * B * 4) + (size_t)job.nlev * B * N * 4, hipMemcpyDeviceToHost, cc);
     if (e == hipSuccess) e = hipEventRecord(job.ev_a, cc);
     end_op(ctx);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) job.state = 1;
+    if (e == hipSuccess && !grid_rc) job.state = 1;
     FB_LAP(2);
     ++ctx->fb_prof_n;
     // ... and while the device works on that: the (rest of the) host part of the job before this one
@@ -657,6 +708,7 @@ static int fb_submit(mrgingham_amd_ctx* ctx, const mrgingham_amd_frames* fr, int
         if (r) fb_remember(ctx, prev->ticket, fb_abandon(ctx, *prev, r));
     }
     if (e != hipSuccess) return fail_hip(ctx, e, "find_boards first pass", __FILE__, __LINE__);
+    if (grid_rc) return grid_rc;
     return ticket;
 }
 

@@ -267,6 +267,8 @@ struct mrgingham_amd_ctx {
     //     is allocated (chain.hip, boards.hip), added to by the kernels, zeroed again by the read-out.
     //   clk: two counters that add up over the probed launches until mrgingham_amd_sclk_mhz reads and zeroes them; zeroed
     //     where they are allocated (mrgingham_amd_set_kernel_timing).
+    //   grid_stat: eight counters of the device grid finder that add up until mrgingham_amd_find_grids_stats reads them;
+    //     zeroed where they are allocated (grid_find.hip).
     // No page-locked buffer is state: status_pin is read only behind the copy end_op queues (status_copied), a job's pin
     // only while the job is in flight, and the fill completes every job first.
     int scratch_fill = -1;
@@ -390,6 +392,11 @@ struct mrgingham_amd_ctx {
         // levels as they went in (what the dense repeat of a sparse refinement starts from)
         mrg::DevBuf d_cnt, d_pts, d_pts0;
         mrg::PinBuf pin;  // pinned host staging: counts, candidates | boards, levels, point counts
+        // option "find_boards_grid" 1 (as the job was submitted): the device finder's statuses | indices of every list of the
+        // first pass, [level][frame], on the device and in pinned host memory
+        bool grid_device = false;
+        mrg::DevBuf d_grid;
+        mrg::PinBuf pin_grid;
         // the host part in progress (fb_host_begin .. fb_host_end): candidate lists of frames re-run at full capacity,
         // the frame counter of the grid-finder threads
         std::vector<std::vector<int32_t>> big;
@@ -414,6 +421,17 @@ struct mrgingham_amd_ctx {
     double fb_dev_ms[2] = {0, 0};  // device milliseconds: first passes (submit .. candidates on the host), refinements
     std::mutex fb_stat_mu;
     mrg::GridPhaseClock fb_grid{0, 0, 0, 0, 0, 0};
+    // The device grid finder (grid_find.hip).  grid_slots: per scratch set, one GfFar (rings,
+    // adjacency lists) per workgroup of the launch -- scratch, written before it is read.  grid_stat: eight 64-bit counters
+    // the kernel adds to (lists, found, none, declined -1 .. -5) until mrgingham_amd_find_grids_stats reads them; STATE: see
+    // scratch_fill.  Options "find_grids_guard_bits" (the guard band is 2^-bits) and "find_boards_grid" (1: the pipelined
+    // find_boards orders the candidates of levels 3..1 on the device and its host threads finish what the device declined;
+    // every host finder call of such a job starts its rings at the canonical neighbour).  fb_grid_fallbacks: lists of such
+    // jobs that the host finder answered because the device had declined them (under fb_stat_mu).
+    mrg::DevBuf grid_slots[kMaxSets], grid_stat;
+    int find_grids_guard_bits = 33;
+    int fb_grid_device = 0;
+    long long fb_grid_fallbacks = 0;
     int pts_nframes = 0, pts_pitch = 0;
     // levels (and frame counts) whose status words must be checked at the next sync
     int pending_frames[kMaxSets][mrg::kMaxLevel + 1] = {};
@@ -589,6 +607,13 @@ int find_board_on_device(mrgingham_amd_ctx* ctx, const char* who, const mrgingha
                          int image_pyramid_level, bool do_refine, std::vector<PointD>& board, std::vector<signed char>& lv,
                          bool debug = false, const char* debug_image_filename = nullptr);
 void fb_drain(mrgingham_amd_ctx* ctx);
+
+// grid_find.hip: the scratch of a launch over nlists lists on scratch set `set` (launch_find_grids grows it itself; a
+// caller that must not allocate behind begin_op calls this in front of it); nlists candidate lists (capacity pairs apart, counts beside them) to board indices and statuses, one
+// launch on s over the slots of scratch set `set`
+int ensure_find_grids(mrgingham_amd_ctx* ctx, int set, int nlists);
+int launch_find_grids(mrgingham_amd_ctx* ctx, int set, const int32_t* d_xy, const int32_t* d_counts, int nlists, int capacity, int gridn,
+                      int32_t* d_index, int32_t* d_status, hipStream_t s);
 
 // accessors the chain path calls per level: inline
 static inline LevelScratch* cur_levels(mrgingham_amd_ctx* ctx) { return ctx->lvs[ctx->cur]; }
